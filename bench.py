@@ -12,7 +12,13 @@ scan + id map).  `value` = queries/s over all ranks; each rank owns a replica of
 on rank 0, broadcast once over RCCL) and its own 10 000 queries -> weak scaling, no per-query
 collective.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4] [--no-secondary]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up the index, warms up, times K steps and prints the one result line (`value`, `ms_per_step`);
+`--dump-outputs DIR` writes the last timed step's results (values.npy f32, ids.npy f64, [n_query, k]) into DIR.
+Everything else -- the stream peak, the list-scan roofline with its counter pass, recall, the CPU baseline and
+the oracle check, the strong-scaling prediction, the secondary pass below (N = 1), the other scaling mode and
+the replica check (N > 1) -- runs only with `--full`.
 
 `--gpus N` with N > 1 launches its own N ranks (torch.distributed.run, one per GPU, RCCL) when
 not already running under a launcher; under the driver's torchrun command it is one of the ranks.
@@ -21,7 +27,7 @@ rank; strong: ONE batch of --nq queries split over the ranks); at N > 1 the othe
 as well and reported under `other_scaling`, with the per-rank ms_per_step spread and the bytes of
 the one index broadcast.
 
-At N=1 the headline is timed first (only the stream peak is measured ahead of it); then a time-boxed secondary pass
+With --full at N=1 the headline is timed first (only the stream peak is measured ahead of it); then a time-boxed secondary pass
 (<= ~60 s, configs[0] with its 80-s CPU leg last) puts the other BASELINE.json configs on the record
 under the key "secondary" of the same JSON line, each with its own roofline:
   stream_peak  measured HBM streaming-read rate of this box (tpq_ubench_stream_read, 8 GiB)
@@ -204,17 +210,18 @@ def scanned_bytes(idx, queries, m):
     return tot * m
 
 
-def time_search(idx, queries, k, steps, warmup, barrier=None):
+def time_search(idx, queries, k, steps, warmup, barrier=None, diagnostics=True):
     """W untimed + K timed search() calls, barrier + synchronize on both sides; (wall seconds,
     mean scan-kernel ms per step from HIP events on the launch stream, query batches per step,
-    last result, per-step statistics of the scan kernel)"""
+    last result, per-step statistics of the scan kernel).  diagnostics=False (a plain run): no
+    events around the scan and no extra search for the redo count (scan ms and statistics stay empty)"""
     scan = idx._ivfpq_topk._scan
     for _ in range(warmup):
         idx.search(queries, k=k)
     torch.cuda.synchronize()
     if barrier is not None:
         barrier()
-    scan.record_events = []
+    scan.record_events = [] if diagnostics else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -223,7 +230,7 @@ def time_search(idx, queries, k, steps, warmup, barrier=None):
     if barrier is not None:
         barrier()
     dt = time.perf_counter() - t0
-    events = scan.record_events
+    events = scan.record_events or []
     scan.record_events = None
     nb = max(1, len(events) // max(steps, 1))  # query batches per search() call
     per_launch = [a.elapsed_time(b) for a, b in events]
@@ -240,7 +247,7 @@ def time_search(idx, queries, k, steps, warmup, barrier=None):
     # queries that took the exact redo (the candidate band overflowed, a table could not be scaled): one more,
     # untimed, search with the workspace kept; counted on every packed route (the one-launch finisher's own
     # redo branch, or the flag-gated exact kernel that ends the other routes) -- "slow and normally never taken"
-    if nb == 1:  # (every packed route leaves its mark: IVFPQTopkHip.last_redone)
+    if diagnostics and nb == 1:  # (every packed route leaves its mark: IVFPQTopkHip.last_redone)
         scan.keep_workspace = True
         try:
             idx.search(queries, k=k)
@@ -595,6 +602,31 @@ def ids_digest(vals, ids):
     h.update(vals.contiguous().cpu().numpy().tobytes())
     h.update(ids.contiguous().cpu().numpy().tobytes())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, vals, ids):
+    """--dump-outputs: what the last timed search() returned, as DIR/values.npy (f32) and DIR/ids.npy (f64: exact for
+    every id below 2^53), both [n_query, k].  Past 64 MiB in all, a fixed sample of query rows (seed 0, ascending) is
+    written instead, with its row numbers as DIR/rows.npy (f64).  Returns the record of what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    v = vals.detach().float().cpu().numpy()
+    i = ids.detach().cpu().numpy().astype(np.float64)
+    nq, k = v.shape
+    rows = None
+    max_rows = DUMP_LIMIT_BYTES // (k * (4 + 8) + 8)
+    if nq > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(nq, max_rows, replace=False))
+        v, i = v[rows], i[rows]
+    arrays = {"values": np.ascontiguousarray(v), "ids": np.ascontiguousarray(i)}
+    if rows is not None:
+        arrays["rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {n: list(a.shape) for n, a in arrays.items()},
+            "sampled_rows": rows is not None}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1175,7 +1207,17 @@ def parse_args(argv=None):
                     help="N > 1: timeout of the process groups (rendezvous, RCCL probe, broadcast)")
     ap.add_argument("--deadline", type=float, default=900.0,
                     help="N > 1: seconds after which rank 0 prints a JSON line with `error` and every rank exits")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: stream peak, list-scan roofline and its "
+                         "counter pass, recall, CPU baseline, oracle check, strong-scaling prediction, secondary pass "
+                         "(N = 1), other scaling mode and replica check (N > 1).  Off: set up, warm up, time --steps "
+                         "steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0): DIR/values.npy (f32) "
+                         "and DIR/ids.npy (f64), [n_query, k]; a fixed sample of rows past 64 MiB (DIR/rows.npy)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_traffic_pass:
         TRAFFIC_PASS["enabled"] = False
     C4_VARIANT["mode"] = args.c4_variant
@@ -1263,7 +1305,7 @@ def run(args, world, rank, done):
         secondary, stream_peak = secondary_pass(device, 1e9, set(args.secondary_only.split(",")))
         print(json.dumps({"secondary": secondary}))
         return
-    do_secondary = world == 1 and not args.no_secondary and args.workload == "c2"
+    do_secondary = world == 1 and args.full and not args.no_secondary and args.workload == "c2"
     stream_record = None
     if do_secondary:
         # The headline is timed FIRST, on a quiet chip: only the box's stream peak (a 60-ms read) is measured ahead of it.
@@ -1338,7 +1380,8 @@ def run(args, world, rank, done):
         """K timed steps in `mode`: (max-over-ranks seconds, per-rank seconds, scan ms, results, queries)"""
         q = make_queries(mode)
         done["stage"] = f"timed region ({mode} scaling)"
-        dt_, scan_ms_, nb_, v_, i_, stats_ = time_search(idx, q, args.k, args.steps, args.warmup, barrier)
+        dt_, scan_ms_, nb_, v_, i_, stats_ = time_search(idx, q, args.k, args.steps, args.warmup, barrier,
+                                                         diagnostics=args.full)
         stats_["launches_per_step"] = nb_
         per_rank = [dt_]
         if world > 1:  # (control plane: CPU tensors over gloo)
@@ -1356,19 +1399,22 @@ def run(args, world, rank, done):
                 "ms_per_step_rank_max": round(max(per_rank) / args.steps * 1e3, 4)}
 
     other = None
-    if world > 1:  # the mode `value` is NOT quoted in, first: the headline region runs last
+    if world > 1 and args.full:  # the mode `value` is NOT quoted in, first: the headline region runs last
         om = "strong" if args.scaling == "weak" else "weak"
         odt, oper, _, _, _, _, _ = timed(om)
         other = mode_summary(om, odt, oper)
     dt, per_rank_dt, scan_ms, vals, ids, queries, scan_stats = timed(args.scaling)
     headline = mode_summary(args.scaling, dt, per_rank_dt)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, vals, ids)
 
     # ---- N > 1: are the replicas equal?  Every rank searches ITS shard of the one shared batch (the strong-scaling
     # batch, rank 0's queries) and contributes a digest of the raw result bytes over the control plane; rank 0 searches
     # the whole batch alone and digests the same row ranges: equal digests <=> every replica returns, for its shard,
     # bit for bit what one GPU returns for the unsharded batch (no data-path collective: 16 bytes per rank)
     replica_check = None
-    if world > 1:
+    if world > 1 and args.full:
         done["stage"] = "replica check (digests of the shared batch)"
         qfull = full_queries("strong")
         b0, e0 = tpd.shard_bounds(qfull.shape[1], rank, world)
@@ -1389,16 +1435,18 @@ def run(args, world, rank, done):
         del qfull, v_s, i_s
 
     # ---- roofline of the dominant kernel (the list scan) --------------------------------------
-    algo_bytes = scanned_bytes(idx, queries, args.m)  # uint8 codes only: the irreducible read
-    kernel = ("scan_packed_kernel (m = 64, batches >= 1024: <1,64,false,-16>, four-wave workgroups over the 16-bit "
-              "selection table, + scan_finish_exact_kernel; kernel_ms brackets the whole scan call)"
-              if args.layout == "packed" else "scan_ref_kernel")
-    roofline = hbm_roofline(
-        algo_bytes, scan_ms, kernel, stream_peak, resident_bytes=idx._storage.numel(), stats=scan_stats,
-        bytes_per_query=round(algo_bytes / queries.shape[1], 1),
-        cell_imbalance=round(float((idx._cell_size.double() ** 2).sum().item()) * args.n_cells
-                             / float(idx._cell_size.sum().item()) ** 2, 3))
-    if args.layout == "packed" and args.workload == "c2":
+    roofline = None
+    if args.full:
+        algo_bytes = scanned_bytes(idx, queries, args.m)  # uint8 codes only: the irreducible read
+        kernel = ("scan_packed_kernel (m = 64, batches >= 1024: <1,64,false,-16>, four-wave workgroups over the 16-bit "
+                  "selection table, + scan_finish_exact_kernel; kernel_ms brackets the whole scan call)"
+                  if args.layout == "packed" else "scan_ref_kernel")
+        roofline = hbm_roofline(
+            algo_bytes, scan_ms, kernel, stream_peak, resident_bytes=idx._storage.numel(), stats=scan_stats,
+            bytes_per_query=round(algo_bytes / queries.shape[1], 1),
+            cell_imbalance=round(float((idx._cell_size.double() ** 2).sum().item()) * args.n_cells
+                                 / float(idx._cell_size.sum().item()) ** 2, 3))
+    if roofline is not None and args.layout == "packed" and args.workload == "c2":
         child = ["--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--nq", str(args.nq),
                  "--n-base", str(args.n_base), "--n-train", str(args.n_train), "--d", str(args.d), "--m", str(args.m),
                  "--n-cells", str(args.n_cells), "--n-probe", str(args.n_probe), "--k", str(args.k)]
@@ -1427,8 +1475,11 @@ def run(args, world, rank, done):
                    "index_broadcast_GBps": round(bcast_bytes / t_bcast / 1e9, 2) if t_bcast > 0 else None,
                    "ms_per_step_rank_min": headline["ms_per_step_rank_min"],
                    "ms_per_step_rank_max": headline["ms_per_step_rank_max"]},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if other is not None:
         out["other_scaling"] = other
     if replica_check is not None:
@@ -1452,14 +1503,14 @@ def run(args, world, rank, done):
     if rank == 0:
         out["train_s"] = round(t_train, 3)
         out["add_s"] = round(t_add, 3)
-        if base is not None:
+        if args.full and base is not None:
             # recall@k = the true nearest neighbour (exact L2 on the raw vectors) is in the top-k:
             # the reference benchmark's definition, on a 1000-query sample
             ns = min(1000, queries.shape[1])
             nn = gt_nn[:ns] if gt_nn is not None else exact_nn(queries[:, :ns], base)
             out["recall_gt@%d" % args.k] = round(float((ids[:ns] == nn[:, None]).any(dim=1).float().mean().item()), 4)
             out["recall_gt@1"] = round(float((ids[:ns, 0] == nn).float().mean().item()), 4)
-        if not args.no_cpu_baseline and world == 1 and args.workload == "c2":  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "c2":  # rank 0 at N=1 only
             cb, cpu_ids = cpu_baseline(idx, queries, args.k, min(args.cpu_sample, queries.shape[1]))
             out["cpu_baseline"] = cb
             gpu_ids = ids[:cpu_ids.shape[0]].cpu().numpy()
@@ -1469,7 +1520,7 @@ def run(args, world, rank, done):
         # the timed route checked at the size it was timed at: a sample of the batch vs the C oracle, bit for bit
         # (N > 1: the oracle on a 256-query sample of rank 0's batch -- the parity figure of the N-GPU line; the
         # CPU baseline itself stays an N = 1 record)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             oc = oracle_sample_check(idx, queries, vals, ids, args.k, n_sample=256 if world > 1 else 32)
             out["oracle_check"] = oc
             if world > 1:

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -28,7 +29,12 @@ def pytest_collection_modifyitems(config, items):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    """tests/golden/<name>.npz merged with its continuation files <name>.part<i>.npz (large fixtures are split so
+    that no committed file passes 1 MB: make_golden.py save_fixture)"""
+    out = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz"))):
+        out.update(np.load(part))
+    return out
 
 
 @pytest.fixture(scope="session")

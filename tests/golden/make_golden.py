@@ -21,6 +21,7 @@ What is reference-generated (key prefix ``ref_``):
   fx_container     CellContainer.add sequences incl. expand()      (CellContainer.py:249-367)
   fx_kmeans        MultiKMeans.get_labels / compute_centroids CPU   (MultiKMeans.py:334-380)
   fx_kmeans_fit    MultiKMeans.fit driver: 1/3 steps, tol exit, n_redo=2 (MultiKMeans.py:415-453)
+  fx_pin           the reference's outputs in oracle/pin_against_reference.py's checks (replayed without it)
 What is oracle-generated (key prefix ``orc_``): scan top-k (values, addresses, ids) --
 the reference has no CPU scan; those are regression vectors for the restatement,
 cross-checked in tests against ref_adc_exact.
@@ -40,6 +41,33 @@ from oracle._refimport import import_reference  # noqa: E402
 from oracle import ivfpq_oracle as orc  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+FILE_LIMIT = 1_000_000  # bytes: every committed file stays under 1 MB
+
+
+def save_fixture(name, out):
+    """<name>.npz, and when the compressed arrays pass FILE_LIMIT the largest ones in continuation files
+    <name>.part1.npz, <name>.part2.npz, ... (tests/conftest.py load_golden merges them back)"""
+    import glob
+    import io
+    for old in glob.glob(os.path.join(OUT, name + ".part*.npz")):
+        os.remove(old)
+
+    def packed_size(arrays):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **arrays)
+        return buf.tell()
+
+    files, rest = [], dict(out)
+    while packed_size(rest) > FILE_LIMIT:
+        part = {}
+        for k in sorted(rest, key=lambda k: -packed_size({k: rest[k]})):
+            if packed_size({**part, k: rest[k]}) <= FILE_LIMIT:
+                part[k] = rest.pop(k)
+        assert part and rest, f"{name}: an array alone passes {FILE_LIMIT} bytes"
+        files.append(part)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rest)
+    for i, part in enumerate(files, 1):
+        np.savez_compressed(os.path.join(OUT, f"{name}.part{i}.npz"), **part)
 
 
 def sift_like(rng, d, n, n_clusters=40):
@@ -124,7 +152,7 @@ def fx_index(torch, tq, name, d, m, n_cells, n, nq, initial_size, seed, n_probe,
             out[f"orc_vals_s{smart}_k{k}"] = v
             out[f"orc_addr_s{smart}_k{k}"] = a
             out[f"orc_ids_s{smart}_k{k}"] = orc.get_id_by_address(sd["_address2id"], a)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    save_fixture(name, out)
     print(name, "n_items", int(sd["_cell_size"].sum()), "cap", cap)
 
 
@@ -386,7 +414,7 @@ def fx_ties_and_tomb(torch, tq):
             v, a = orc.scan_topk(sd["_storage"], lut, sd["_is_empty"], cs, sz, npl, k)
             out[f"orc_vals_k{k}"], out[f"orc_addr_k{k}"] = v, a
             out[f"orc_ids_k{k}"] = orc.get_id_by_address(sd["_address2id"], a)
-        np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+        save_fixture(name, out)
         return out
 
     t = dump("fx_ties", {})
@@ -429,6 +457,19 @@ def fx_layout(torch, tq):
     print("fx_layout ok")
 
 
+def fx_pin():
+    """what the reference returned in oracle/pin_against_reference.py's checks (its fixed-seed inputs), so that
+    the same checks replay where the reference tree is not present (RecordedReference)."""
+    import warnings
+    from oracle import pin_against_reference
+    live = pin_against_reference.LiveReference()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        done = pin_against_reference.run(verbose=False, ref=live)
+    save_fixture("fx_pin", live.recorded)
+    print("fx_pin ok:", len(done), "checks,", len(live.recorded), "arrays")
+
+
 def main():
     tq = import_reference()
     import torch
@@ -449,6 +490,7 @@ def main():
         "fx_cosine": lambda: fx_cosine(torch, tq),
         "fx_ties_tomb": lambda: fx_ties_and_tomb(torch, tq),
         "fx_layout": lambda: fx_layout(torch, tq),
+        "fx_pin": fx_pin,
     }
     names = sys.argv[1:] or list(jobs)
     for n in names:

@@ -80,7 +80,7 @@ def test_bench_gpus2_self_launches_under_the_one_device_hook():
         env.pop(k, None)
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-         "--nq", "512", "--n-base", "60000", "--n-train", "20000", "--n-cells", "64", "--n-probe", "8"],
+         "--nq", "512", "--n-base", "60000", "--n-train", "20000", "--n-cells", "64", "--n-probe", "8", "--full"],
         env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -115,7 +115,7 @@ def test_bench_gpus2_strong_scaling_is_the_headline_when_asked():
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
          "--scaling", "strong", "--nq", "511", "--n-base", "60000", "--n-train", "20000", "--n-cells", "64",
-         "--n-probe", "8"],
+         "--n-probe", "8", "--full"],
         env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

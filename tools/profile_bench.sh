@@ -18,7 +18,7 @@ for W in $WORKLOADS; do
   OUT="${ROOT}/gpurun_out/${TAG}/${W}"
   mkdir -p "$OUT"
   case "$W" in
-    c2) BENCH="python ${ROOT}/bench.py --steps 20 --warmup 3 --no-secondary --no-traffic-pass"; KERNEL="scan_packed_kernel";;
+    c2) BENCH="python ${ROOT}/bench.py --steps 20 --warmup 3 --full --no-secondary --no-traffic-pass"; KERNEL="scan_packed_kernel";;
     c3) BENCH="python ${ROOT}/bench.py --secondary-only c3 --no-traffic-pass"; KERNEL="scan_packed_kernel";;
     c4) BENCH="python ${ROOT}/bench.py --secondary-only c4 --c4-variant warm --no-traffic-pass"; KERNEL="scan_packed_kernel";;
     c4cold) BENCH="python ${ROOT}/bench.py --secondary-only c4 --c4-variant cold --no-traffic-pass"; KERNEL="scan_packed_kernel";;

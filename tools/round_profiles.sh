@@ -10,10 +10,10 @@ cd "$ROOT"
 # 1. per workload: plain run, rocprofv3 --kernel-trace --stats, separate --pmc passes, summary
 bash tools/profile_bench.sh "$TAG" c2 c3 c4 c4cold c5 wide > "$OUT/${TAG}_profile_bench.log" 2>&1
 python tools/collect_profiles.py "$TAG" >> "$OUT/${TAG}_profile_bench.log" 2>&1
-# 2. the DRIVER's command, three times, with those summaries in place (its lines carry kernel_ms_profile /
+# 2. the full bench line (--full), three times, with those summaries in place (its lines carry kernel_ms_profile /
 #    profile_mismatch against them, and the traffic of their own counter pass)
 for i in 1 2 3; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_full_$i.json" 2> "$OUT/${TAG}_bench_full_$i.err"
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench_full_$i.json" 2> "$OUT/${TAG}_bench_full_$i.err"
 done
 cp "$OUT/${TAG}_bench_full_1.json" "profiles/${TAG}_bench_full.json"
 # 3. sweeps, the reference's grid, probe routes, small batches, large k, soaks, the 100 M build
