@@ -118,7 +118,9 @@ size_t tpq_ivfpq_scan_tickets_bytes(int nq);
  * applies exactly the rules of the entry points above (tests assert the route a shape takes; bench.py names the timed
  * kernel from it).  `has_lut`: a materialised table is passed (tpq_ivfpq_scan_topk[_packed]) rather than query +
  * codebook (tpq_ivfpq_search_fused); `has_packed`: the scan-layout copy is passed; `residual`: the residual entry point.
- * Returns one of TPQ_SCAN_ROUTE_*, or -1 for arguments the entry points reject. */
+ * Returns one of TPQ_SCAN_ROUTE_*, or -1 for arguments the entry points reject -- among them a scan-layout copy at an m
+ * without a scan-layout kernel, with a table or on the residual entry point (the fused entry point scans the reference
+ * layout then: TPQ_SCAN_ROUTE_REF).  The route returned is the one the entry point runs. */
 #define TPQ_SCAN_ROUTE_REF 0            /* scan_ref_kernel / scan_residual_kernel: the reference layout, exact */
 #define TPQ_SCAN_ROUTE_ONE_LAUNCH 1     /* scan_packed_kernel<.., RM > 0>: the scan workgroups finish their queries */
 #define TPQ_SCAN_ROUTE_LISTS 2          /* scan_packed_kernel + scan_merge_refine_kernel + the flag-gated exact redo */

@@ -220,3 +220,28 @@ def test_band_overflow_by_mass_ties_is_redone_and_counted():
     torch.cuda.synchronize()
     assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
     assert 200 <= redone <= 220, redone
+
+
+def test_queries_redone_is_none_on_the_reference_layout_route():
+    """k = 1020 with a table at m = 64 leaves no room for the candidate band: the packed entry point scans the reference
+    layout, which writes no ws_delta -- last_redone() says so instead of counting words nobody wrote"""
+    from torchpq_amd import kernels as K
+    g = torch.Generator(device=DEV)
+    g.manual_seed(11)
+    m, nc, cell, n_probe, k, nq = 64, 64, 400, 4, 1020, 8
+    storage = torch.randint(0, 256, (m // 4, nc * cell, 4), generator=g, device=DEV, dtype=torch.uint8)
+    lut = torch.randn(m, nq, 256, generator=g, device=DEV)
+    start = torch.arange(nc, device=DEV) * cell
+    sizes = torch.full((nc,), cell, device=DEV, dtype=torch.long)
+    cells = torch.rand(nq, nc, generator=g, device=DEV).argsort(1)[:, :n_probe].contiguous()
+    cs, sz = start[cells].contiguous(), sizes[cells].contiguous()
+    npl = torch.full((nq,), n_probe, device=DEV, dtype=torch.long)
+    scan = K.IVFPQTopkHip(m=m)
+    scan.keep_workspace = True
+    got = scan.topk(storage, lut, None, cs, sz, npl, n_candidates=k, packed=K.PackCodesHip()(storage))
+    torch.cuda.synchronize()
+    assert scan.last_route() == "reference_layout"
+    assert scan.last_redone(nq) is None
+    ref = scan.topk(storage, lut, None, cs, sz, npl, n_candidates=k)
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])

@@ -225,3 +225,25 @@ def test_scan_route_rules():
     assert r(64, 10000, 100, packed=False) == "reference_layout"
     assert r(64, 10000, 1020, has_lut=True) == "reference_layout"   # no room for the candidate band next to k
     assert r(64, 0, 100) == "rejected"
+    # a scan-layout copy at an m without a scan-layout kernel: the entry points with a table and the residual one reject
+    # the call, the fused one scans the reference layout (the Python wrapper never passes such a copy: asked directly)
+    from torchpq_amd import _lib
+    lib = _lib.load()
+    assert 36 not in K.PACKED_M
+    #                              nq,   k, n_split, m, ds, n_probe, hint, has_lut, has_packed, tickets, residual
+    assert lib.tpq_ivfpq_scan_route(10000, 100, 1, 36, 2, 32, 0, 1, 1, 0, 0) == -1
+    assert lib.tpq_ivfpq_scan_route(10000, 100, 1, 36, 2, 32, 0, 0, 1, 0, 1) == -1
+    assert lib.tpq_ivfpq_scan_route(10000, 100, 1, 36, 2, 32, 0, 0, 1, 0, 0) == 0
+    # every valid call at an instantiated m is planned onto a route that exists (the dump routes only with a pair of
+    # list registers that has an instantiation: the route reported is the one that runs)
+    for m in K.PACKED_M:
+        for k in (1, 56, 100, 248, 249, 300, 504, 505, 1000, 1024):
+            for nq in (16, 1023, 1024, 10000):
+                for has_lut, residual, ds in ((True, False, 0), (False, False, 1), (False, False, 2), (False, False, 4),
+                                              (True, True, 0), (False, True, 2)):
+                    for n_split, tickets in ((1, False), (8, False), (8, True)):
+                        for hint in (None, 1000, 32 * 244, 32 * 977, 64 * 6103):
+                            got = r(m, nq, k, ds=ds, n_split=n_split, hint=hint, has_lut=has_lut, residual=residual,
+                                    tickets=tickets)
+                            assert got in K.IVFPQTopkHip.ROUTES.values() and got != "rejected", \
+                                (m, k, nq, has_lut, residual, ds, n_split, tickets, hint, got)

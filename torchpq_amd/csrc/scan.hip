@@ -73,6 +73,63 @@ static int dispatch_ref(const ScanArgs& a, int R, hipStream_t st) {
   }
 }
 
+static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st) {
+  const int R = list_regs(a.k);
+  const bool build_part1 = !ra.full && !ra.part1;
+  const size_t lds = scan_lds_bytes_ref(a.m, R, a.max_nprobe, build_part1 ? a.m * a.ds + a.m : 0);
+  auto go = [&](auto kernel) -> int {
+    int rc2 = set_lds(kernel, lds, "scan_residual_kernel");
+    if (rc2) return rc2;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.nq), dim3(kScanThreads), lds, st, a, ra);
+    TPQ_LAUNCH_CHECK("scan_residual_kernel");
+    return TPQ_OK;
+  };
+  switch (R) {
+    case 1: return go(scan_residual_kernel<1>);
+    case 2: return go(scan_residual_kernel<2>);
+    case 4: return go(scan_residual_kernel<4>);
+    case 8: return go(scan_residual_kernel<8>);
+    default: return go(scan_residual_kernel<16>);
+  }
+}
+
+static int run_ref(ScanArgs a, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  int rc = validate(a);
+  if (rc || a.nq == 0) return rc;
+  const int R = list_regs(a.k);
+  if (a.n_split > 1) {
+    rc = need_ws(workspace, workspace_bytes, ws_bytes_for(a.nq, R, a.n_split), "ivfpq_scan");
+    if (rc) return rc;
+    fill_ws(a, workspace, R, a.n_split);
+  }
+  return dispatch_ref(a, R, st);
+}
+
+// exact redo of the (normally zero) queries a packed route flagged: the reference-layout kernels, one workgroup per query
+static int redo_flagged(const ScanArgs& a, const ResidualArgs* ra, hipStream_t st) {
+  ScanArgs b = a;
+  b.n_split = 1;
+  b.only_flagged = a.flags;
+  return ra ? run_residual_ref(b, *ra, st) : dispatch_ref(b, list_regs(a.k), st);
+}
+
+// the per-M translation units (scan_packed.hip)
+struct PackedUnit {
+  int m;
+  int (*packed)(const ScanArgs& a, const ResidualArgs* ra, int RL, int R, hipStream_t st);
+  int (*pool)(const ScanArgs& a, int RL, hipStream_t st);
+  int (*dump)(const ScanArgs& a, int RL, int Rf, int mode, hipStream_t st);
+  int (*dump_occupancy)(int mode);
+};
+static const PackedUnit* packed_unit(int m) {
+#define TPQ_UNIT(M) {M, dispatch_packed_##M, dispatch_pool_##M, dispatch_dump_##M, dump_occupancy_##M},
+  static const PackedUnit units[] = {TPQ_PACKED_M_LIST(TPQ_UNIT)};
+#undef TPQ_UNIT
+  for (const PackedUnit& u : units)
+    if (u.m == m) return &u;
+  return nullptr;
+}
+
 }  // namespace tpq
 
 using namespace tpq;
@@ -82,9 +139,9 @@ extern "C" size_t tpq_ivfpq_scan_workspace_bytes(int nq, int k, int n_split, int
   if (n_split < 1) n_split = 1;
   int R = list_regs_packed(k) > list_regs(k) ? list_regs_packed(k) : list_regs(k);
   if (R > 16) R = 16;
-  // covers both kernels -- and, at m = 64, the dump route's split tail: 4 parts x 4 waves of lists per query
+  // covers both kernels -- and, on the dump routes, the split tail: 4 parts x 4 waves of lists per query
   size_t lists = ws_bytes_for(nq, R, n_split * packed_waves(m));
-  if ((m == 64 || m == 32 || m == 16 || m == 8) && dump_finish_regs(k, 1) <= kDumpMaxR) {
+  if ((dump_built(m, kDumpSel16) || dump_built(m, kDumpF32)) && dump_finish_regs(k, 1) <= kDumpMaxR) {
     const int rp = list_regs_packed(k);
     const size_t tail = ws_bytes_for(nq, rp < 2 ? rp : 2, 16), whole = ws_bytes_for(nq, rp < 4 ? rp : 4, 4);
     lists = tail > lists ? tail : lists;
@@ -94,9 +151,6 @@ extern "C" size_t tpq_ivfpq_scan_workspace_bytes(int nq, int k, int n_split, int
   return lists > pools ? lists : pools;
 }
 
-static int run_ref(ScanArgs a, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
-static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
-                      tpq_stream_t stream);
 #ifdef TPQ_SCAN_PROFILE
 // private instrumentation build: phase timestamps of scan_packed_kernel (tools/scan_phase_profile.py)
 static unsigned long long* g_scan_prof = nullptr;
@@ -122,7 +176,7 @@ static bool fuse_enabled() {
 // INVARIANT (captured graphs replay with the SAME epoch and the same workspace): every path that raises flags also
 // consumes them before the call's last kernel ends -- the fused finisher and scan_ref_kernel / scan_residual_kernel
 // reset a flag they act on; scan_pool_merge_kernel and scan_finish_exact_kernel only skip (or raise) and rely on the
-// dispatch_ref launch that follows them IN THE SAME CALL.  A call that returns an error between those two launches
+// redo_flagged launch that follows them IN THE SAME CALL.  A call that returns an error between those two launches
 // leaves flags raised: harmless for the next call (another epoch), and a capture that saw a failed launch is dead
 // anyway.  A stale word that happens to equal the epoch costs one needless exact redo, never a wrong result.
 static int fresh_epoch() {
@@ -147,7 +201,7 @@ static int dump_route(const ScanArgs& a, bool residual, int R) {
   if (e && atoi(e) == 0) return 0;
   // (the finish kernel takes a query's lists as at most 16 chunks of 64 keys: four waves x RL <= 4, eight x RL <= 2)
   const int rl4 = list_regs_scan(a.k, a.m, a.max_nprobe, a.slots_hint, 4);
-  if (a.m == 8 || a.m == 16 || a.m == 32) {
+  if (dump_built(a.m, kDumpF32)) {
     // Short codes (round 6): the fp32 table their four-wave workgroups stream over anyway; the finish kernel takes the
     // exact entries from the codebook in LDS (fused calls, m * ds <= 128) or from the caller's table.  k <= 248: the
     // pools keep the larger k (TPQ_SCAN_DUMP_SHORT_K=n in variant builds moves the limit for A/B).
@@ -163,7 +217,7 @@ static int dump_route(const ScanArgs& a, bool residual, int R) {
   }
   // m = 64: the 16-bit table.  The finish kernel recomputes the survivors' table entries from the codebook, held in
   // LDS next to nothing else: fused calls (query + codebook) only, m * ds <= 128
-  if (a.lut || a.m != 64 || a.ds > 2) return 0;
+  if (a.lut || !dump_built(a.m, kDumpSel16) || a.ds > 2) return 0;
   const int rl8 = list_regs_scan(a.k, a.m, a.max_nprobe, a.slots_hint);
   // Lists of 4 registers in four-wave workgroups only where eight waves would need them as well (short cells, k > 256):
   // folding into a 256-entry list is what a large k costs, and four waves see twice the candidates each.
@@ -177,41 +231,37 @@ static int dump_route(const ScanArgs& a, bool residual, int R) {
   return 0;
 }
 
-// The batch's last round of workgroups (ScanArgs::unsplit): the chip holds 4 dump-mode workgroups per CU; the
-// nq mod slots queries left after the full rounds are dealt in 4 (or 2) parts each when those parts fit one round and
-// the finish kernel can take their lists (<= 16 chunks of 64 keys per query) -- 1 250 queries: 1 024 whole + 226 x 4.
-static int device_cus() {
-  // (per-device cache; relaxed atomics: concurrent first calls from several host threads write the same value)
-  static std::atomic<int> cached[64] = {};
+// Per-device caches of device properties (relaxed atomics: concurrent first calls from several host threads write the
+// same value); `query` runs on the current device, `fallback` stands in when it fails.
+template <int N, class Query>
+static int device_cached(std::atomic<int> (&cache)[64][N], int i, int fallback, Query query) {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  int n = cached[dev].load(std::memory_order_relaxed);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fallback;
+  int n = cache[dev][i].load(std::memory_order_relaxed);
   if (n <= 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev].store(n, std::memory_order_relaxed);
+    n = query(dev);
+    if (n <= 0) n = fallback;
+    cache[dev][i].store(n, std::memory_order_relaxed);
   }
   return n;
 }
+static int device_cus() {
+  static std::atomic<int> cus[64][1] = {};
+  return device_cached(cus, 0, 256, [](int dev) {
+    int n = 0;
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 0;
+  });
+}
 // workgroup slots of the dump-mode scan kernel on this device: CUs x the workgroups of it a CU holds -- from the occupancy
 // query of the kernel's smallest instantiation (the "4 per CU" used to be an assumption)
-static int dump_slots(int m, int mode) {
-  static std::atomic<int> per_cu[3][4] = {};  // [mode][m class]
-  const int mi = mode == kDumpSel16 ? 0 : (mode == kDumpF32 ? 1 : 2), ci = m == 64 ? 0 : (m == 32 ? 1 : (m == 16 ? 2 : 3));
-  int n = per_cu[mi][ci].load(std::memory_order_relaxed);
-  if (n <= 0) {
-    n = 4;
-    int q = 0;
-    switch (m) {
-#define TPQ_CASE_M(M) case M: q = dump_occupancy_##M(mode); break;
-      TPQ_PACKED_M_LIST(TPQ_CASE_M)
-#undef TPQ_CASE_M
-      default: break;
-    }
-    if (q > 0) n = q;
-    per_cu[mi][ci].store(n, std::memory_order_relaxed);
-  }
-  return n * device_cus();
+static int dump_slots(const PackedUnit& u, int mode) {
+  static std::atomic<int> per_cu[64][3 * 4] = {};  // [device][mode x m class]
+  const int mi = mode == kDumpSel16 ? 0 : (mode == kDumpF32 ? 1 : 2), ci = u.m == 64 ? 0 : (u.m == 32 ? 1 : (u.m == 16 ? 2 : 3));
+  return device_cached(per_cu, mi * 4 + ci, 4, [&](int) { return u.dump_occupancy(mode); }) * device_cus();
 }
+// The batch's last round of workgroups (ScanArgs::unsplit): the chip holds 4 dump-mode workgroups per CU; the
+// nq mod slots queries left after the full rounds are dealt in 4 (or 2) parts each when those parts fit one round and
+// the finish kernel can take their lists (<= 16 chunks of 64 keys per query) -- 1 250 queries: 1 024 whole + 226 x 4.
 static void dump_tail(int nq, int nw, int RL, int slots, int* unsplit, int* parts) {
   *unsplit = nq;
   *parts = 1;
@@ -227,13 +277,175 @@ static void dump_tail(int nq, int nw, int RL, int slots, int* unsplit, int* part
   }
 }
 
-static bool has_packed_kernel(int m) {
-#define TPQ_IS_M(M) if (m == M) return true;
-  TPQ_PACKED_M_LIST(TPQ_IS_M)
-#undef TPQ_IS_M
-  return false;
+// What a packed call runs, decided once per call by plan_scan -- a pure host function (no HIP call: the route query,
+// tpq_ivfpq_scan_route, answers without a GPU) -- and executed by run_packed without re-deriving any of it.  Two things
+// stay with the executor because they need the device or the caller's buffer: the dump routes' split tail (dump_tail,
+// from the device's workgroup slots) and, when the caller's workspace is too small for it, the tail kept whole.  Both
+// change the parts a query is dealt in, never the route.
+struct ScanPlan {
+  int route = -1;            // TPQ_SCAN_ROUTE_*, -1 = the entry point rejects the call
+  int R = 0;                 // registers of the merged list (list_regs_packed(k))
+  int RL = 0;                // registers of the per-wave lists (pools: of the threshold lists)
+  int Rf = 0;                // dump routes: registers of the finish kernel's exact list
+  int mode = 0;              // dump routes: kDumpF32 / kDumpSel16 / kDumpSel16W8
+  int waves = 0;             // waves per scan workgroup
+  int n_split = 1;           // workgroups per query (the dump routes: 1 before the split tail)
+  bool fuse = false;         // one-launch finish
+  bool small_lists = false;  // per-wave lists shorter than k + kBandSlack
+};
+
+static ScanPlan plan_scan(const ScanArgs& a, bool residual) {
+  const int m = a.m, k = a.k;
+  ScanPlan p;
+  p.n_split = a.n_split;
+  if (!packed_unit(m)) {
+    // no scan-layout kernel at this m: the fused entry point scans the reference layout, the others reject the call
+    if (!residual && !a.lut) p.route = TPQ_SCAN_ROUTE_REF;
+    return p;
+  }
+  p.R = list_regs_packed(k);
+  p.waves = packed_waves(m);
+  const bool lds_fits =
+      scan_lds_bytes_packed(m, p.R > 16 ? 16 : p.R, a.max_nprobe, fused_floats_of(a), residual) <= 160 * 1024;
+  // k within kBandSlack of 1024 (no room for the candidate band), or a probe table that no longer
+  // fits next to the LUT: scan exactly with the reference-layout kernel
+  if (p.R > 16 || !lds_fits) {
+    p.route = TPQ_SCAN_ROUTE_REF;
+    if (residual) p.n_split = 1;
+    return p;
+  }
+  // (measured against the sorted lists of the three-launch path, C2 shape, 10 000 queries: m = 64, k = 600 / 1000:
+  // 6.1 / 6.9 ms against 7.1 / 8.3; m = 120 (1 000 queries), k = 1000: 2.0 against 3.4 -- and k = 600: 1.9 against 1.6;
+  // m = 16, 32: within 2 %; k = 300, 500 at m = 64: 4.1 / 4.5 against 3.6 / 4.0)
+  const bool pools = !residual && p.R >= pool_min_list_regs(m) && (p.waves < 16 || k > 768) && fuse_enabled();
+  // large batches: dump_route.  (Where the pools apply as well -- k in (248, 504] of the short codes -- the pools keep the
+  // call: dump_route's own k limit for m <= 32, kDumpShortMaxK, says so; variant builds move it for the A/B.)  A pair of
+  // list registers without an instantiation (TPQ_DUMP_PAIRS) declines the route: ADVICE r5, a change of the list-size
+  // heuristics must not fail a search.
+  const int Rf = dump_finish_regs(k, a.slots_hint), mode = dump_route(a, residual, Rf);
+  if (mode && !(is_sel16(mode) && pools)) {
+    const int nw = scan_waves(m, mode), RL = list_regs_scan(k, m, a.max_nprobe, a.slots_hint, nw);
+    if (dump_pair_built(mode, RL, Rf)) {
+      p.route = mode == kDumpF32 ? TPQ_SCAN_ROUTE_DUMP_F32
+                                 : (mode == kDumpSel16 ? TPQ_SCAN_ROUTE_DUMP_SEL16 : TPQ_SCAN_ROUTE_DUMP_SEL16_W8);
+      p.mode = mode, p.waves = nw, p.RL = RL, p.Rf = Rf, p.n_split = 1;
+      return p;
+    }
+  }
+  // the largest k, plain PQ: pool mode (scan_device.h) -- threshold lists of ceil(k / waves) entries, unsorted pools,
+  // one ranking kernel per query; flagged queries (a pool or the ranking buffer overflowed) redone exactly
+  // (the ranking kernel takes a query's lists into LDS: fewer workgroups per query when they would not fit)
+  if (pools) {
+    p.route = TPQ_SCAN_ROUTE_POOLS;
+    p.RL = pool_list_regs(k, m);
+    if (p.n_split > pool_max_split(m, k)) p.n_split = pool_max_split(m, k);
+    return p;
+  }
+  p.RL = list_regs_scan(k, m, a.max_nprobe, a.slots_hint);
+  p.small_lists = p.RL < p.R;
+  // the scan workgroups finish the query themselves (merge, write, exact redo): one launch instead of three.
+  // (k <= 248, plain PQ; a query split over several workgroups needs the caller's tickets)
+  p.fuse = !residual && fuse_enabled() && fuse_fits(m, p.R) && p.waves * p.RL >= p.R && (a.n_split == 1 || a.tickets);
+  p.route = p.fuse ? TPQ_SCAN_ROUTE_ONE_LAUNCH : TPQ_SCAN_ROUTE_LISTS;
+  return p;
 }
-static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st);
+
+extern "C" int tpq_ivfpq_scan_route(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                    int has_lut, int has_packed, int has_tickets, int residual) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return TPQ_SCAN_ROUTE_REF;
+  ScanArgs a{};
+  static const float dummy_lut = 0.f;
+  static int32_t dummy_tickets = 0;
+  a.lut = has_lut ? &dummy_lut : nullptr;   // (only tested against nullptr)
+  a.ds = has_lut ? 0 : ds;
+  a.nq = nq; a.k = k; a.n_split = n_split; a.m = m; a.max_nprobe = max_nprobe;
+  a.slots_hint = slots_hint;
+  a.tickets = has_tickets ? &dummy_tickets : nullptr;
+  return plan_scan(a, residual != 0).route;
+}
+
+static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
+                      tpq_stream_t stream) {
+  int rc = validate(a);
+  if (rc) return rc;
+  TPQ_REQUIRE(a.packed != nullptr, "ivfpq_scan_packed: null packed pointer");
+  if (a.nq == 0) return TPQ_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const ScanPlan p = plan_scan(a, ra != nullptr);
+  if (p.route == TPQ_SCAN_ROUTE_REF) {
+    a.n_split = p.n_split;
+    return ra ? run_residual_ref(a, *ra, st) : run_ref(a, workspace, workspace_bytes, st);
+  }
+  if (p.route < 0) {
+    set_error("ivfpq_scan_packed: no scan-layout kernel instantiated for n_subvectors=%d; use "
+              "tpq_ivfpq_scan_topk", a.m);
+    return TPQ_ERR_UNSUPPORTED;
+  }
+  const PackedUnit& u = *packed_unit(a.m);
+  const int nq = a.nq;
+  a.n_split = p.n_split;
+  a.small_lists = p.small_lists;
+  a.fuse = p.fuse;
+  if (!p.fuse) a.tickets = nullptr;
+  // flags: raised == equal to this call's epoch; no zeroing pass (it was a launch of its own)
+  a.epoch = fresh_epoch();
+#ifdef TPQ_SCAN_PROFILE
+  a.prof = g_scan_prof;
+#endif
+  switch (p.route) {
+    case TPQ_SCAN_ROUTE_POOLS: {
+      const int n_lists = p.n_split * p.waves;
+      rc = need_ws(workspace, workspace_bytes, pool_ws_bytes(nq, a.k, a.m, n_lists), "ivfpq_scan_packed");
+      if (rc) return rc;
+      fill_ws_pool(a, workspace, n_lists);
+      rc = u.pool(a, p.RL, st);
+      break;
+    }
+    // large batches of plain PQ, k <= 504: dump mode (scan_device.h) -- the scan workgroups stream over the selection
+    // table (m = 64: 16-bit, 32 KiB, four workgroups per CU; m = 8, 16, 32: the fp32 table) and end with their lists of
+    // fast values, one wave per query finishes
+    case TPQ_SCAN_ROUTE_DUMP_F32:
+    case TPQ_SCAN_ROUTE_DUMP_SEL16:
+    case TPQ_SCAN_ROUTE_DUMP_SEL16_W8: {
+      int unsplit = nq, parts = 1;
+      if (p.mode != kDumpSel16W8) dump_tail(nq, p.waves, p.RL, dump_slots(u, p.mode), &unsplit, &parts);
+      // (a caller's workspace sized by an older rule: the tail stays whole)
+      if (parts > 1 && (!workspace || workspace_bytes < ws_bytes_for(nq, p.RL, parts * p.waves))) unsplit = nq, parts = 1;
+      a.n_split = parts;
+      a.unsplit = parts > 1 ? unsplit : 0;  // (0 with one part per query: "all queries split 1 way")
+      rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, p.RL, parts * p.waves), "ivfpq_scan_packed");
+      if (rc) return rc;
+      fill_ws(a, workspace, p.RL, parts * p.waves);
+      rc = u.dump(a, p.RL, p.Rf, p.mode, st);
+      break;
+    }
+    default: {  // TPQ_SCAN_ROUTE_ONE_LAUNCH, TPQ_SCAN_ROUTE_LISTS
+      const int n_lists = p.n_split * p.waves;
+      rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, p.RL, n_lists), "ivfpq_scan_packed");
+      if (rc) return rc;
+      fill_ws(a, workspace, p.RL, n_lists);
+      rc = u.packed(a, ra, p.RL, p.R, st);
+      if (p.fuse) return rc;  // (the fused finish redoes them itself)
+    }
+  }
+  if (rc) return rc;
+  return redo_flagged(a, ra, st);
+}
+
+// ---- entry points ------------------------------------------------------------------------------------
+// the arguments every scan entry point shares, set by name (the rest of ScanArgs stays zero)
+static ScanArgs scan_args(const uint8_t* codes, const uint8_t* packed, const float* lut, const uint8_t* is_empty,
+                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                          float* out_vals, int64_t* out_addr, const int64_t* address2id, int64_t* out_ids,
+                          int64_t n_slots, int nq, int max_nprobe, int m, int k, int n_split) {
+  ScanArgs a{};
+  a.codes = codes; a.packed = packed; a.lut = lut; a.is_empty = is_empty;
+  a.cell_start = cell_start; a.cell_size = cell_size; a.n_probe_list = n_probe_list;
+  a.out_vals = out_vals; a.out_addr = out_addr; a.address2id = address2id; a.out_ids = out_ids;
+  a.n_slots = n_slots; a.nq = nq; a.max_nprobe = max_nprobe; a.m = m; a.k = k; a.n_split = n_split;
+  return a;
+}
 
 extern "C" size_t tpq_ivfpq_scan_tickets_bytes(int nq) { return nq > 0 ? (size_t)nq * sizeof(int32_t) : 0; }
 
@@ -250,13 +462,12 @@ extern "C" int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8
   TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER,
               "ivfpq_search_fused: bad metric %d", metric);
   TPQ_REQUIRE(ds >= 1 && ds <= 1024, "ivfpq_search_fused: bad sub-vector length %d", ds);
-  ScanArgs a{codes, packed, nullptr, query, codebook, ds, metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0,
-             is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, address2id, out_ids,
-             nullptr, nullptr, nullptr, nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split};
-  a.tickets = tickets;
-  a.slots_hint = slots_hint;
-  if (packed && has_packed_kernel(m)) return run_packed(a, nullptr, workspace, workspace_bytes, stream);
-  return run_ref(a, workspace, workspace_bytes, stream);
+  ScanArgs a = scan_args(codes, packed, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  a.query = query; a.codebook = codebook; a.ds = ds; a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
+  a.tickets = tickets; a.slots_hint = slots_hint;
+  return packed ? run_packed(a, nullptr, workspace, workspace_bytes, stream)
+                : run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int tpq_ivfpq_search_fused(const uint8_t* packed, const uint8_t* codes,
@@ -280,24 +491,9 @@ extern "C" int tpq_ivfpq_scan_topk(const uint8_t* codes, const float* lut, const
                                    const int64_t* address2id, int64_t* out_ids, int64_t n_slots,
                                    int nq, int max_nprobe, int m, int k, int n_split,
                                    void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
-  ScanArgs a{codes, nullptr, lut, nullptr, nullptr, 0, 0, is_empty, cell_start, cell_size,
-             n_probe_list, out_vals, out_addr, address2id, out_ids, nullptr, nullptr, nullptr,
-             nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split};
-  return run_ref(a, workspace, workspace_bytes, stream);
-}
-
-static int run_ref(ScanArgs a, void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
-  int rc = validate(a);
-  if (rc) return rc;
-  if (a.nq == 0) return TPQ_OK;
-  const int nq = a.nq, k = a.k, n_split = a.n_split;
-  const int R = list_regs(k);
-  if (n_split > 1) {
-    rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, R, n_split), "ivfpq_scan");
-    if (rc) return rc;
-    fill_ws(a, workspace, R, n_split);
-  }
-  return dispatch_ref(a, R, reinterpret_cast<hipStream_t>(stream));
+  const ScanArgs a = scan_args(codes, nullptr, lut, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                               address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  return run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int tpq_ivfpq_scan_topk_packed_tickets(const uint8_t* packed, const uint8_t* codes,
@@ -309,11 +505,9 @@ extern "C" int tpq_ivfpq_scan_topk_packed_tickets(const uint8_t* packed, const u
                                                   int m, int k, int n_split, void* workspace,
                                                   size_t workspace_bytes, int32_t* tickets,
                                                   int64_t slots_hint, tpq_stream_t stream) {
-  ScanArgs a{codes, packed, lut, nullptr, nullptr, 0, 0, is_empty, cell_start, cell_size,
-             n_probe_list, out_vals, out_addr, address2id, out_ids, nullptr, nullptr, nullptr,
-             nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split};
-  a.tickets = tickets;
-  a.slots_hint = slots_hint;
+  ScanArgs a = scan_args(codes, packed, lut, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  a.tickets = tickets; a.slots_hint = slots_hint;
   return run_packed(a, nullptr, workspace, workspace_bytes, stream);
 }
 
@@ -330,211 +524,6 @@ extern "C" int tpq_ivfpq_scan_topk_packed(const uint8_t* packed, const uint8_t* 
                                             k, n_split, workspace, workspace_bytes, nullptr, 0, stream);
 }
 
-// Which kernels a packed call runs (the order of the tests is run_packed's): TPQ_SCAN_ROUTE_* of torchpq_amd.h.
-// `dump_regs`: registers of the finish kernel's exact list on the dump routes.
-static int packed_route(const ScanArgs& a, bool residual, int* dump_regs = nullptr) {
-  const int m = a.m, k = a.k;
-  const int R = list_regs_packed(k);
-  if (!has_packed_kernel(m)) return TPQ_SCAN_ROUTE_REF;
-  const bool lds_fits =
-      scan_lds_bytes_packed(m, R > 16 ? 16 : R, a.max_nprobe, fused_floats_of(a), residual) <= 160 * 1024;
-  // k within kBandSlack of 1024 (no room for the candidate band), or a probe table that no longer
-  // fits next to the LUT: scan exactly with the reference-layout kernel
-  if (R > 16 || !lds_fits) return TPQ_SCAN_ROUTE_REF;
-  // (measured against the sorted lists of the three-launch path, C2 shape, 10 000 queries: m = 64, k = 600 / 1000:
-  // 6.1 / 6.9 ms against 7.1 / 8.3; m = 120 (1 000 queries), k = 1000: 2.0 against 3.4 -- and k = 600: 1.9 against 1.6;
-  // m = 16, 32: within 2 %; k = 300, 500 at m = 64: 4.1 / 4.5 against 3.6 / 4.0)
-  const bool pools = !residual && R >= pool_min_list_regs(m) && (packed_waves(m) < 16 || k > 768) && fuse_enabled();
-  // large batches: dump_route.  (Where the pools apply as well -- k in (248, 504] of the short codes -- the pools keep the
-  // call: dump_route's own k limit for m <= 32, kDumpShortMaxK, says so; variant builds move it for the A/B.)
-  {
-    const int Rf = dump_finish_regs(k, a.slots_hint);
-    if (dump_regs) *dump_regs = Rf;
-    const int mode = dump_route(a, residual, Rf);
-    if (mode == kDumpSel16 && !pools) return TPQ_SCAN_ROUTE_DUMP_SEL16;
-    if (mode == kDumpSel16W8 && !pools) return TPQ_SCAN_ROUTE_DUMP_SEL16_W8;
-    if (mode == kDumpF32) return TPQ_SCAN_ROUTE_DUMP_F32;
-  }
-  if (pools) return TPQ_SCAN_ROUTE_POOLS;
-  const int RL = list_regs_scan(k, m, a.max_nprobe, a.slots_hint);
-  if (!residual && fuse_enabled() && fuse_fits(m, R) && packed_waves(m) * RL >= R && (a.n_split == 1 || a.tickets))
-    return TPQ_SCAN_ROUTE_ONE_LAUNCH;
-  return TPQ_SCAN_ROUTE_LISTS;
-}
-
-extern "C" int tpq_ivfpq_scan_route(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
-                                    int has_lut, int has_packed, int has_tickets, int residual) {
-  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
-  if (!has_packed) return TPQ_SCAN_ROUTE_REF;
-  ScanArgs a{};
-  static const float dummy_lut = 0.f;
-  static int32_t dummy_tickets = 0;
-  a.lut = has_lut ? &dummy_lut : nullptr;   // (only tested against nullptr)
-  a.ds = has_lut ? 0 : ds;
-  a.nq = nq; a.k = k; a.n_split = n_split; a.m = m; a.max_nprobe = max_nprobe;
-  a.slots_hint = slots_hint;
-  a.tickets = has_tickets ? &dummy_tickets : nullptr;
-  return packed_route(a, residual != 0);
-}
-
-static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
-                      tpq_stream_t stream) {
-  int rc = validate(a);
-  if (rc) return rc;
-  TPQ_REQUIRE(a.packed != nullptr, "ivfpq_scan_packed: null packed pointer");
-  if (a.nq == 0) return TPQ_OK;
-  const int nq = a.nq, k = a.k, n_split = a.n_split, m = a.m;
-  int32_t* const caller_tickets = a.tickets;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int R = list_regs_packed(k);
-  if (!has_packed_kernel(m)) {
-    set_error("ivfpq_scan_packed: no scan-layout kernel instantiated for n_subvectors=%d; use "
-              "tpq_ivfpq_scan_topk", m);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  int Rf = 0;
-  int route = packed_route(a, ra != nullptr, &Rf);
-  if (route == TPQ_SCAN_ROUTE_REF) {
-    // k within kBandSlack of 1024 (no room for the candidate band), or a probe table that no longer
-    // fits next to the LUT: scan exactly with the reference-layout kernel
-    if (ra) {
-      a.n_split = 1;
-      return run_residual_ref(a, *ra, st);
-    }
-    const int Rr = list_regs(k);
-    if (n_split > 1) {
-      rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, Rr, n_split), "ivfpq_scan_packed");
-      if (rc) return rc;
-      fill_ws(a, workspace, Rr, n_split);
-    }
-    return dispatch_ref(a, Rr, st);
-  }
-  const int n_lists = n_split * packed_waves(m);
-  if (route == TPQ_SCAN_ROUTE_POOLS) {
-    // the largest k, plain PQ: pool mode (scan_device.h) -- threshold lists of ceil(k / waves) entries, unsorted pools,
-    // one ranking kernel per query; flagged queries (a pool or the ranking buffer overflowed) redone exactly
-    // (the ranking kernel takes a query's lists into LDS: fewer workgroups per query when they would not fit)
-    if (a.n_split > pool_max_split(m, k)) a.n_split = pool_max_split(m, k);
-    const int n_lists_p = a.n_split * packed_waves(m);
-    rc = need_ws(workspace, workspace_bytes, pool_ws_bytes(nq, k, m, n_lists_p), "ivfpq_scan_packed");
-    if (rc) return rc;
-    fill_ws_pool(a, workspace, n_lists_p);
-    a.epoch = fresh_epoch();
-    a.fuse = 0;
-    a.tickets = nullptr;
-    a.small_lists = 0;
-#ifdef TPQ_SCAN_PROFILE
-    a.prof = g_scan_prof;
-#endif
-    switch (m) {
-#define TPQ_CASE_M(M) case M: rc = dispatch_pool_##M(a, pool_list_regs(k, m), st); break;
-      TPQ_PACKED_M_LIST(TPQ_CASE_M)
-#undef TPQ_CASE_M
-      default: rc = TPQ_ERR_UNSUPPORTED; break;
-    }
-    if (rc) return rc;
-    ScanArgs b = a;
-    b.n_split = 1;
-    b.only_flagged = a.flags;
-    return dispatch_ref(b, list_regs(k), st);
-  }
-  // large batches of plain PQ, k <= 504: dump mode (scan_device.h) -- the scan workgroups stream over the selection table
-  // (m = 64: 16-bit, 32 KiB, four workgroups per CU; m = 8, 16, 32: the fp32 table) and end with their lists of fast
-  // values, one wave per query finishes
-  if (route == TPQ_SCAN_ROUTE_DUMP_SEL16 || route == TPQ_SCAN_ROUTE_DUMP_SEL16_W8 || route == TPQ_SCAN_ROUTE_DUMP_F32) {
-    const int mode = route == TPQ_SCAN_ROUTE_DUMP_SEL16 ? kDumpSel16
-                                                        : (route == TPQ_SCAN_ROUTE_DUMP_F32 ? kDumpF32 : kDumpSel16W8);
-    const int nw = mode == kDumpSel16W8 ? packed_waves(m) : 4;
-    const int RLd = list_regs_scan(k, m, a.max_nprobe, a.slots_hint, nw);
-    int unsplit = nq, parts = 1;
-    if (mode != kDumpSel16W8) dump_tail(nq, nw, RLd, dump_slots(m, mode), &unsplit, &parts);
-    // (a caller's workspace sized by an older rule: the tail stays whole)
-    if (parts > 1 && (!workspace || workspace_bytes < ws_bytes_for(nq, RLd, parts * nw))) unsplit = nq, parts = 1;
-    a.n_split = parts;
-    a.unsplit = parts > 1 ? unsplit : 0;  // (0 with one part per query: "all queries split 1 way")
-    rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, RLd, parts * nw), "ivfpq_scan_packed");
-    if (rc) return rc;
-    fill_ws(a, workspace, RLd, parts * nw);
-    a.epoch = fresh_epoch();
-    a.fuse = 0;
-    a.tickets = nullptr;
-    a.small_lists = 0;
-#ifdef TPQ_SCAN_PROFILE
-    a.prof = g_scan_prof;
-#endif
-    switch (m) {
-#define TPQ_CASE_M(M) case M: rc = dispatch_dump_##M(a, RLd, Rf, mode, st); break;
-      TPQ_PACKED_M_LIST(TPQ_CASE_M)
-#undef TPQ_CASE_M
-      default: rc = TPQ_ERR_UNSUPPORTED; break;
-    }
-    if (rc == TPQ_OK) {
-      ScanArgs b = a;  // exact redo of the (normally zero) flagged queries
-      b.n_split = 1;
-      b.only_flagged = a.flags;
-      return dispatch_ref(b, list_regs(k), st);
-    }
-    // TPQ_ERR_UNSUPPORTED = no instantiation for (mode, RLd, Rf) at this m, reported before any launch: the sorted
-    // lists below take the call (a change of the list-size heuristics must not fail a search)
-    if (rc != TPQ_ERR_UNSUPPORTED) return rc;
-    a.n_split = n_split;
-    a.unsplit = 0;
-    a.tickets = caller_tickets;
-    const int RLs = list_regs_scan(k, m, a.max_nprobe, a.slots_hint);
-    route = (fuse_enabled() && fuse_fits(m, R) && packed_waves(m) * RLs >= R && (n_split == 1 || a.tickets))
-                ? TPQ_SCAN_ROUTE_ONE_LAUNCH : TPQ_SCAN_ROUTE_LISTS;
-  }
-  // registers of the per-wave lists (<= R)
-  const int RL = list_regs_scan(k, m, a.max_nprobe, a.slots_hint);
-  a.small_lists = RL < R ? 1 : 0;
-  rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, RL, n_lists), "ivfpq_scan_packed");
-  if (rc) return rc;
-  fill_ws(a, workspace, RL, n_lists);
-#ifdef TPQ_SCAN_PROFILE
-  a.prof = g_scan_prof;
-#endif
-  // flags: raised == equal to this call's epoch; no zeroing pass (it was a launch of its own)
-  a.epoch = fresh_epoch();
-  // the scan workgroups finish the query themselves (merge, write, exact redo): one launch instead of three.
-  // (k <= 248, plain PQ; a query split over several workgroups needs the caller's tickets)
-  a.fuse = route == TPQ_SCAN_ROUTE_ONE_LAUNCH ? 1 : 0;
-  if (!a.fuse) a.tickets = nullptr;
-  switch (m) {
-#define TPQ_CASE_M(M) case M: rc = dispatch_packed_##M(a, ra, RL, R, st); break;
-    TPQ_PACKED_M_LIST(TPQ_CASE_M)
-#undef TPQ_CASE_M
-    default: rc = TPQ_ERR_UNSUPPORTED; break;
-  }
-  if (rc) return rc;
-  if (a.fuse) return TPQ_OK;  // (the fused finish redoes them itself)
-  // exact redo of the (normally zero) queries whose candidate band overflowed
-  ScanArgs b = a;
-  b.n_split = 1;
-  b.only_flagged = a.flags;
-  if (ra) return run_residual_ref(b, *ra, st);
-  return dispatch_ref(b, list_regs(k), st);
-}
-
-static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st) {
-  const int R = list_regs(a.k);
-  const bool build_part1 = !ra.full && !ra.part1;
-  const size_t lds = scan_lds_bytes_ref(a.m, R, a.max_nprobe, build_part1 ? a.m * a.ds + a.m : 0);
-  auto go = [&](auto kernel) -> int {
-    int rc2 = set_lds(kernel, lds, "scan_residual_kernel");
-    if (rc2) return rc2;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)a.nq), dim3(kScanThreads), lds, st, a, ra);
-    TPQ_LAUNCH_CHECK("scan_residual_kernel");
-    return TPQ_OK;
-  };
-  switch (R) {
-    case 1: return go(scan_residual_kernel<1>);
-    case 2: return go(scan_residual_kernel<2>);
-    case 4: return go(scan_residual_kernel<4>);
-    case 8: return go(scan_residual_kernel<8>);
-    default: return go(scan_residual_kernel<16>);
-  }
-}
-
 extern "C" int tpq_ivfpq_scan_topk_residual(const uint8_t* codes, const float* part1,
                                             const float* part2, const float* full_lut,
                                             const int64_t* cells, const float* base_sims,
@@ -544,9 +533,8 @@ extern "C" int tpq_ivfpq_scan_topk_residual(const uint8_t* codes, const float* p
                                             const int64_t* address2id, int64_t* out_ids,
                                             int64_t n_slots, int nq, int max_nprobe, int m, int k,
                                             tpq_stream_t stream) {
-  ScanArgs a{codes, nullptr, part1 ? part1 : full_lut, nullptr, nullptr, 0, 0, is_empty, cell_start,
-             cell_size, n_probe_list, out_vals, out_addr, address2id, out_ids, nullptr, nullptr,
-             nullptr, nullptr, nullptr, n_slots, nq, max_nprobe, m, k, 1};
+  const ScanArgs a = scan_args(codes, nullptr, part1 ? part1 : full_lut, is_empty, cell_start, cell_size, n_probe_list,
+                               out_vals, out_addr, address2id, out_ids, n_slots, nq, max_nprobe, m, k, 1);
   int rc = validate(a);
   if (rc) return rc;
   TPQ_REQUIRE(base_sims != nullptr, "ivfpq_scan_residual: base_sims is required");
@@ -569,10 +557,10 @@ extern "C" int tpq_ivfpq_scan_topk_residual_packed(
               "ivfpq_scan_residual_packed: need part1 or (query, codebook, ds)");
   TPQ_REQUIRE(part2 && slot_term && cell_bound && cells && base_sims,
               "ivfpq_scan_residual_packed: null pointer argument");
-  // euclid = 2: the in-workgroup LUT is part1 = 2 q_j.r_jc
-  ScanArgs a{codes, packed, part1, query, codebook, ds, 2, is_empty, cell_start, cell_size,
-             n_probe_list, out_vals, out_addr, address2id, out_ids, nullptr, nullptr, nullptr,
-             nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split};
+  ScanArgs a = scan_args(codes, packed, part1, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  a.query = query; a.codebook = codebook; a.ds = ds;
+  a.euclid = 2;  // the in-workgroup LUT is part1 = 2 q_j.r_jc
   ResidualArgs ra{part1, part2, nullptr, cells, base_sims, slot_term, cell_bound};
   return run_packed(a, &ra, workspace, workspace_bytes, stream);
 }

@@ -82,6 +82,24 @@ constexpr int kDumpF32 = -8;     // fp32 table in LDS (m KiB), the permuted-orde
 constexpr int kDumpSel16 = -16;  // 16-bit fixed-point table (m / 2 KiB), an exact integer sum as the selection key
 constexpr int kDumpSel16W8 = -17;  // the same with the eight waves of the other paths (k in (248, 504]: lists of <= 2 registers)
 constexpr bool is_sel16(int RM) { return RM == kDumpSel16 || RM == kDumpSel16W8; }
+// which m take which dump mode: m = 64 the 16-bit table (both forms), m = 8, 16, 32 (round 6) the fp32 table
+constexpr bool dump_built(int m, int mode) {
+  return is_sel16(mode) ? m == 64 : (mode == kDumpF32 && (m == 8 || m == 16 || m == 32));
+}
+// the (RL = registers of the scan's per-wave lists, Rf = of the finish kernel's exact list) pairs instantiated per dump
+// mode -- what list_regs_scan / dump_finish_regs produce today; plan_scan (scan.hip) declines the route for any other
+#define TPQ_DUMP_PAIRS(X)                                                                                     \
+  X(kDumpSel16W8, 1, 8) X(kDumpSel16W8, 2, 8) X(kDumpSel16W8, 2, 16)                                          \
+  X(kDumpF32, 1, 1) X(kDumpF32, 1, 2) X(kDumpF32, 2, 2) X(kDumpF32, 1, 4) X(kDumpF32, 2, 4) X(kDumpF32, 4, 4) \
+  X(kDumpF32, 2, 8) X(kDumpF32, 4, 8) X(kDumpF32, 4, 16)                                                      \
+  X(kDumpSel16, 1, 1) X(kDumpSel16, 1, 2) X(kDumpSel16, 2, 2) X(kDumpSel16, 1, 4) X(kDumpSel16, 2, 4)         \
+  X(kDumpSel16, 2, 8) X(kDumpSel16, 4, 8)
+constexpr bool dump_pair_built(int mode, int RL, int Rf) {
+#define TPQ_IS_PAIR(MODE, A, B) if (mode == MODE && RL == A && Rf == B) return true;
+  TPQ_DUMP_PAIRS(TPQ_IS_PAIR)
+#undef TPQ_IS_PAIR
+  return false;
+}
 constexpr int kDumpMinQueries = 1024;  // batches that fill the chip's 4 x 256 workgroup slots at least once
 constexpr int kDumpShortMaxK = 248;    // m = 8, 16, 32 (kDumpF32): the pools take the larger k
 constexpr int kDumpLutMinSlots = 24576;  // ... with a caller's table: from this many expected slots per query on

@@ -84,14 +84,16 @@ class IVFPQTopkHip:
     def last_redone(self, n_query):
         """diagnostics (synchronises; needs keep_workspace): queries of the last packed scan that were redone exactly --
         by the one-launch finisher's own redo branch (ws_delta[q] == 1) or, on the routes that end with the flag-gated
-        exact kernel (the large-batch route over the 16-bit table, the pools, the three-launch path: ws_delta holds a
-        selection band there), by that kernel, which leaves kRedoneMark = -1 (csrc/scan_device.h)"""
+        exact kernel (the large-batch routes, the pools, the three-launch path: ws_delta holds a selection band there),
+        by that kernel, which leaves kRedoneMark = -1 (csrc/scan_device.h).  None on the reference-layout route, which
+        writes no ws_delta."""
         ws = self.last_workspace
-        if ws is None:
+        route = self.last_route()
+        if ws is None or route in (None, "reference_layout", "rejected"):
             return None
         off = (n_query * 4 + 255) // 256 * 256
         d = ws[off:off + 4 * n_query].view(torch.float32)
-        return int(((d == 1.0) | (d == -1.0)).sum().item())
+        return int((d == (1.0 if route == "one_launch_finish" else -1.0)).sum().item())
 
     ROUTES = {0: "reference_layout", 1: "one_launch_finish", 2: "sorted_lists", 3: "pools", 8: "dump_f32",
               16: "dump_sel16", 17: "dump_sel16_w8", -1: "rejected"}
