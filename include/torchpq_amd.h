@@ -482,6 +482,33 @@ int tpq_pq_decode(const float* codebook, const uint8_t* codes, float* out, int m
 int tpq_scatter_codes(const uint8_t* codes, const int64_t* address, uint8_t* storage,
                       uint8_t* packed, int m, int64_t n, int64_t n_slots, tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * IVFPQRIndex re-rank step (Jegou et al., "Searching in one billion vectors: re-rank with source coding")
+ * stands in for IVFPQR.topk's second half   torchpq/legacy/IVFPQR.py:408-473
+ * (the reference's new-API class, torchpq/index/IVFPQRIndex.py, has no search).
+ *
+ * storage      u8  [(m+m_r)/4][capacity][4]  rows 0..m-1 the first-stage code, rows m..m+m_r-1 the re-rank code
+ * codebook     f32 [m][ds][256]     first-stage codebook (ds = d/m); may be NULL when !use_residual
+ * codebook_r   f32 [m_r][ds_r][256] re-rank codebook (ds_r = d/m_r)
+ * query        f32 [d][nq]          (pre-normalised by the host for TPQ_METRIC_INNER)
+ * cand_address i64 [nq][k1]         candidates of the list scan; < 0 or >= capacity = none
+ * out_vals f32 / out_address i64 / out_ids i64 [nq][k]; address2id and out_ids are both given or both NULL.
+ *
+ * Value of a candidate with codes c[0..m), c_r[0..m_r) (all fp32, no fma unless stated, i ascending):
+ *   use_residual:  r_i = codebook[i/ds][i%ds][c[i/ds]] + codebook_r[i/ds_r][i%ds_r][c_r[i/ds_r]];
+ *       TPQ_METRIC_NEG_SQ_L2:  t = q_i - r_i;  acc = acc - t*t      (acc starts at 0.f)
+ *       TPQ_METRIC_INNER:      acc = acc + q_i * r_i
+ *   !use_residual: v = 0.f; for j ascending: v += LUT_r[j][c_r[j]], LUT_r the table tpq_adc_lut builds from
+ *       codebook_r (fma chains over the sub-vector; 2*dot - |q_j|^2 - |c|^2 for the L2 metric), built in the kernel.
+ * Output per query: the k best candidates by (value descending, address ascending); positions beyond the
+ * real candidates are (-inf, -1, -1).  1 <= k <= k1 <= 1024 and capacity < 2^31 - 1, else TPQ_ERR_UNSUPPORTED;
+ * storage and the codebooks are 16-byte aligned.  No workspace.
+ * ------------------------------------------------------------------------- */
+int tpq_ivfpqr_rerank(const uint8_t* storage, int64_t capacity, int m, int m_r, const float* codebook,
+                      const float* codebook_r, const float* query, int d, int nq, const int64_t* cand_address,
+                      int k1, int k, int use_residual, int distance, const int64_t* address2id, float* out_vals,
+                      int64_t* out_address, int64_t* out_ids, tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

@@ -32,7 +32,7 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in lloyd.hip kmeans.hip assign_fast.hip select.hip scan.hip kmeans_split.hip container.hip lut.hip pack.hip ubench.hip api.cpp; do
+for src in lloyd.hip kmeans.hip assign_fast.hip select.hip scan.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   if stale "$obj" "${HERE}/${src}"; then
     cmds+=("'$HIPCC' ${FLAGS[*]} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/${src}' -o '$obj' ${EXTRA_FLAGS:-}")

@@ -287,6 +287,10 @@ class IVFPQIndex(CellContainer):
         return (part1[:, None] + part2.permute(1, 2, 0, 3)).contiguous()
 
     # ---- search (reference :407-524) ---------------------------------------------------------------
+    def _scan_codes(self):
+        """the code rows the list scan reads, [n_subvectors / 4, capacity, 4] (IVFPQRIndex stores more rows)"""
+        return self._storage
+
     def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False,
                      _extents=None):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
@@ -314,7 +318,7 @@ class IVFPQIndex(CellContainer):
                 fused = self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector
                 part1 = None if fused else self.precomputed_adc_residual_precomputed(x)[0]
                 topk_val, topk_address, topk_ids = self._ivfpq_topk._scan.topk_residual_packed(
-                    data=self._storage, packed=self.packed_storage(), part2=self._part2_by_cell,
+                    data=self._scan_codes(), packed=self.packed_storage(), part2=self._part2_by_cell,
                     slot_term=slot_term, cell_bound=cell_bound, cells=cells, base_sims=base_sims,
                     is_empty=is_empty, cell_start=cell_start, cell_size=cell_size,
                     n_probe_list=n_probe_list, n_candidates=k, part1=part1,
@@ -324,13 +328,13 @@ class IVFPQIndex(CellContainer):
             elif self.use_precomputed:
                 part1, part2 = self.precomputed_adc_residual_precomputed(x)
                 topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_residual_precomputed(
-                    data=self._storage, part1=part1, part2=part2, cells=cells, base_sims=base_sims,
+                    data=self._scan_codes(), part1=part1, part2=part2, cells=cells, base_sims=base_sims,
                     cell_start=cell_start, cell_size=cell_size, is_empty=is_empty,
                     n_probe_list=n_probe_list, k=k, address2id=self._address2id)
             else:
                 precomputed = self.precomputed_adc_residual(x, cells)
                 topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_residual(
-                    data=self._storage, base_sims=base_sims, precomputed=precomputed,
+                    data=self._scan_codes(), base_sims=base_sims, precomputed=precomputed,
                     cell_start=cell_start, cell_size=cell_size, is_empty=is_empty,
                     n_probe_list=n_probe_list, k=k, address2id=self._address2id)
             if return_address:
@@ -347,7 +351,7 @@ class IVFPQIndex(CellContainer):
         # 1-KiB-per-sub-quantizer LUT row from HBM: a win while the sub-vectors are short
         if self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector:
             topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_fused(
-                data=self._storage, query=x, codebook=self.pq_codec.codebook, cell_start=cell_start,
+                data=self._scan_codes(), query=x, codebook=self.pq_codec.codebook, cell_start=cell_start,
                 cell_size=cell_size, is_empty=self._is_empty if self._has_holes else None,
                 n_probe_list=n_probe_list, k=k, distance=self.distance, packed=packed,
                 address2id=self._address2id, slots_hint=slots_hint)
@@ -356,7 +360,7 @@ class IVFPQIndex(CellContainer):
             return topk_val, topk_ids
         precomputed = self.pq_codec.precompute_adc(x)
         topk_val, topk_address, topk_ids = self._ivfpq_topk.topk(
-            data=self._storage, precomputed=precomputed, cell_start=cell_start,
+            data=self._scan_codes(), precomputed=precomputed, cell_start=cell_start,
             cell_size=cell_size, is_empty=self._is_empty if self._has_holes else None,
             n_probe_list=n_probe_list, k=k, packed=packed, address2id=self._address2id,
             slots_hint=slots_hint)

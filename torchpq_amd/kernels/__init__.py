@@ -16,7 +16,7 @@ __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "packed_chunk_width", "PACKED_M",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "packed_chunk_width", "PACKED_M",
 ]
 
 # n_subvectors with an instantiated scan-layout kernel (= TPQ_PACKED_M_LIST in csrc/scan_device.h)
@@ -1022,3 +1022,54 @@ class PackCodesHip:
             check(load().tpq_ivfpq_pack_codes(ptr(storage), ptr(packed), cap, m, begin, end,
                                               stream_ptr(storage.device)), "tpq_ivfpq_pack_codes")
         return packed
+
+
+class IVFPQRerankHip:
+    """The re-rank step of IVFPQRIndex (tpq_ivfpqr_rerank; the second half of the legacy IVFPQR.topk,
+    legacy/IVFPQR.py:408-473): the candidates of the list scan re-valued from both codes of their slot,
+    the best k kept."""
+
+    def __call__(self, storage, n_subvectors, codebook, codebook_r, query, cand_address, k, use_residual=True,
+                 distance="euclidean", address2id=None):
+        """
+          storage: [(m + m_r) // 4, capacity, 4] uint8, first the m first-stage rows, then the m_r re-rank rows
+          codebook [m, ds, 256] / codebook_r [m_r, ds_r, 256] float32 (codebook may be None when not use_residual)
+          query: [d, n_query] float32 (normalised by the caller for "cosine")
+          cand_address: [n_query, k1] int64, -1 = no candidate
+          address2id: optional [capacity] int64; when given a third tensor (ids) is returned
+        returns (values [n_query, k] descending, address [n_query, k][, ids]); unfilled = (-inf, -1, -1)
+        """
+        m = n_subvectors
+        g, capacity, cs = storage.shape
+        m_r, ds_r, kk = codebook_r.shape
+        d, n_query = query.shape
+        k1 = cand_address.shape[1]
+        assert cs == 4 and storage.dtype == torch.uint8 and g * 4 == m + m_r
+        assert kk == 256 and d == m_r * ds_r and d % m == 0
+        assert cand_address.shape == (n_query, k1) and cand_address.dtype == torch.int64
+        assert query.dtype == codebook_r.dtype == torch.float32
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= k1 <= 1024
+        if use_residual:
+            assert codebook.shape == (m, d // m, 256) and codebook.dtype == torch.float32
+            codebook = codebook.contiguous()
+        else:
+            codebook = None
+        if address2id is not None:
+            assert address2id.shape == (capacity,) and address2id.dtype == torch.int64
+        query = query.contiguous()
+        codebook_r = codebook_r.contiguous()
+        cand_address = cand_address.contiguous()
+        require_gpu(storage, codebook, codebook_r, query, cand_address, address2id)
+        device = storage.device
+        values = torch.empty(n_query, k, device=device, dtype=torch.float32)
+        address = torch.empty(n_query, k, device=device, dtype=torch.int64)
+        ids = torch.empty(n_query, k, device=device, dtype=torch.int64) if address2id is not None else None
+        if n_query:
+            metric = _lib.METRIC_NEG_SQ_L2 if distance == "euclidean" else _lib.METRIC_INNER
+            with torch.cuda.device(device):
+                check(load().tpq_ivfpqr_rerank(
+                    ptr(storage), capacity, m, m_r, ptr(codebook), ptr(codebook_r), ptr(query), d, n_query,
+                    ptr(cand_address), k1, k, int(bool(use_residual)), metric, ptr(address2id), ptr(values),
+                    ptr(address), ptr(ids), stream_ptr(device)), "tpq_ivfpqr_rerank")
+        return (values, address) if ids is None else (values, address, ids)
