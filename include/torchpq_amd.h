@@ -501,7 +501,10 @@ int tpq_scatter_codes(const uint8_t* codes, const int64_t* address, uint8_t* sto
  *   !use_residual: v = 0.f; for j ascending: v += LUT_r[j][c_r[j]], LUT_r the table tpq_adc_lut builds from
  *       codebook_r (fma chains over the sub-vector; 2*dot - |q_j|^2 - |c|^2 for the L2 metric), built in the kernel.
  * Output per query: the k best candidates by (value descending, address ascending); positions beyond the
- * real candidates are (-inf, -1, -1).  1 <= k <= k1 <= 1024 and capacity < 2^31 - 1, else TPQ_ERR_UNSUPPORTED;
+ * real candidates are (-inf, -1, -1); a real candidate whose value is -inf keeps its address and id and stands
+ * ahead of them.  A query with a NaN or +-Inf component (or one whose products overflow) still returns: its own
+ * row then holds, in no pinned order, -1 or candidates of that row, none more often than cand_address names it,
+ * and the rows of the finite queries are what they are without it.  1 <= k <= k1 <= 1024 and capacity < 2^31 - 1, else TPQ_ERR_UNSUPPORTED;
  * storage and the codebooks are 16-byte aligned.  No workspace.
  * ------------------------------------------------------------------------- */
 int tpq_ivfpqr_rerank(const uint8_t* storage, int64_t capacity, int m, int m_r, const float* codebook,

@@ -7,50 +7,14 @@ import pytest
 import torch
 
 import ivfpqr_oracle as rorc
+from tests_support import (DEV, N, T, _case, _check_search, _clustered, _expected_search, _normalize,
+                           _run_and_compare)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 # (m, m_r, d): sub-vector lengths (ds, ds_r) = (2, 2), (4, 2), (1, 1), (4, 8), and (6, 2) with d not a multiple of 16
 SHAPES = [(8, 8, 16), (16, 32, 64), (64, 64, 64), (32, 16, 128), (4, 12, 24)]
 K1_K = [(1, 1), (7, 3), (64, 64), (200, 100), (1024, 512), (1024, 1024)]
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def _case(seed, m, m_r, d, cap, nq, k1, distance):
-    rng = np.random.default_rng(seed)
-    storage = rng.integers(0, 256, ((m + m_r) // 4, cap, 4), dtype=np.uint8)
-    cb = rng.standard_normal((m, d // m, 256)).astype(np.float32)
-    cb_r = (0.3 * rng.standard_normal((m_r, d // m_r, 256))).astype(np.float32)
-    query = rng.standard_normal((d, nq)).astype(np.float32)
-    if distance == "cosine":
-        query = (query / np.linalg.norm(query, axis=0, keepdims=True)).astype(np.float32)
-    cand = np.argsort(rng.random((nq, cap)), axis=1)[:, :k1].astype(np.int64)   # distinct per row
-    # rows with fewer than k real candidates (holes anywhere in the row), and rows with none
-    short = rng.random(nq) < 0.3
-    cand[short[:, None] & (rng.random((nq, k1)) < 0.7)] = -1
-    cand[rng.random(nq) < 0.1] = -1
-    if nq >= 3:
-        cand[1] = -1
-    a2i = rng.permutation(cap).astype(np.int64) * 3 + 1
-    return storage, cb, cb_r, query, cand, a2i
-
-
-def _run_and_compare(storage, cb, cb_r, query, cand, a2i, k, use_residual, distance, m):
-    from torchpq_amd.kernels import IVFPQRerankHip
-    v, a, i = IVFPQRerankHip()(T(storage), m, T(cb) if use_residual else None, T(cb_r), T(query), T(cand), k,
-                               use_residual=use_residual, distance=distance, address2id=T(a2i))
-    ev, ea, ei = rorc.rerank(storage, cb, cb_r, query, cand, k, use_residual, distance, a2i)
-    assert np.array_equal(N(a), ea)
-    assert np.array_equal(N(v).view(np.uint32), ev.view(np.uint32))
-    assert np.array_equal(N(i), ei)
 
 
 @pytest.mark.parametrize("distance", ["euclidean", "cosine"])
@@ -134,42 +98,6 @@ def test_rerank_under_a_captured_graph():
 
 
 # ---- the index -----------------------------------------------------------------------------------------
-def _clustered(seed, d, n, nq, n_centers=40, spread=4.0):
-    rng = np.random.default_rng(seed)
-    centers = rng.standard_normal((d, n_centers)) * spread
-    base = (centers[:, rng.integers(0, n_centers, n)] + rng.standard_normal((d, n))).astype(np.float32)
-    queries = (base[:, rng.choice(n, nq, replace=False)] + 0.3 * rng.standard_normal((d, nq))).astype(np.float32)
-    return base, queries
-
-
-def _expected_search(idx, x, k):
-    """tests/ivfpqr_oracle.search driven by the index's own coarse step (the pattern of test_gpu_index.py)"""
-    x = np.asarray(x, dtype=np.float32)
-    if idx.distance == "cosine":
-        x = N(_normalize(idx, T(x)))
-    _, cells, npl = idx.probe(T(x))
-    return rorc.search(x, N(idx.pq_codec.codebook), N(idx.pq_rerank_codec.codebook), N(idx._storage),
-                       N(idx._is_empty), N(idx._cell_start), N(idx._cell_size), N(idx._address2id), N(cells),
-                       N(npl), k, idx.rerank_factor, idx.use_residual, idx.distance)
-
-
-def _normalize(idx, x):
-    from torchpq_amd import util
-    return util.normalize(x, dim=0)
-
-
-def _check_search(idx, queries, k):
-    v, i, a = idx.search(T(queries), k=k, return_address=True)
-    ev, ei, ea = _expected_search(idx, queries, k)
-    assert v.shape == (queries.shape[1], k) and v.dtype == torch.float32 and i.dtype == torch.int64
-    assert np.array_equal(N(a), ea)
-    assert np.array_equal(N(v).view(np.uint32), ev.view(np.uint32))
-    assert np.array_equal(N(i), ei)
-    v2, i2 = idx.search(T(queries), k=k)
-    assert torch.equal(v2, v) and torch.equal(i2, i)
-    return N(v), N(i)
-
-
 def _build(distance="euclidean", use_residual=True, d=32, m=8, m_r=8, n_cells=128, n=6000, seed=0, **kw):
     from torchpq_amd.index import IVFPQRIndex
     base, queries = _clustered(seed, d, n, 60)

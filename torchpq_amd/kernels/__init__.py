@@ -456,6 +456,8 @@ class AdcLutHip:
         require_gpu(query, codebook)
         nq = query.shape[1]
         lut = torch.empty(m, nq, 256, device=query.device, dtype=torch.float32)
+        if nq == 0:   # (an empty tensor has no address to hand to the library)
+            return lut
         metric = _lib.METRIC_NEG_SQ_L2 if distance == "euclidean" else _lib.METRIC_INNER
         with torch.cuda.device(query.device):
             check(load().tpq_adc_lut(ptr(query), ptr(codebook), ptr(lut), m, ds, nq, metric,
