@@ -1,4 +1,5 @@
-"""GPU: one Lloyd iteration on prepared data (tpq_lloyd_prepare / tpq_lloyd_step, csrc/lloyd.hip).
+"""GPU: one Lloyd iteration on prepared data (tpq_lloyd_prepare / tpq_lloyd_step, csrc/lloyd.hip; the kernels of the
+fp16 cascade: csrc/cascade_core.hip) and tpq_coarse_assign through the same cascade (csrc/assign_cascade.hip).
 
 The step replaces the get_labels -> compute_centroids pair of the reference's driver
 (torchpq/clustering/MultiKMeans.py:415-453; max_sim_tn kernels/cuda/max_sim.cu:182-309;
@@ -240,6 +241,26 @@ def test_coarse_assign_cascade_labels_are_the_fp32_arg_max(kind, d, m, n, monkey
         _, el = c_oracle.max_sim(x, cent, "euclidean", "expanded")
         assert np.array_equal(N(lab), el[0])
     assert 0 <= op.last_rechecked() <= m
+
+
+@pytest.mark.parametrize("d,m,n", [(32, 2048, 512),    # two chunks of 256 centroids: the candidate route, count1
+                                   (32, 2048, 256),    # one chunk: levels 2 and 3, count2
+                                   (160, 1024, 300)])  # wide: the GEMM-shaped route, its own count1
+def test_coarse_assign_rechecked_count_is_read_from_the_route_taken(d, m, n, monkeypatch):
+    """which counter last_rechecked() reads follows from the route the call took (one predicate decides both, and
+    the routes that end in candidate pairs share that tail): gaussian data leaves a few percent of the points to
+    the exact step on every route, so a counter read at the wrong offset shows up as 0 or as garbage"""
+    import torchpq_amd.kernels as K
+    monkeypatch.setattr(K.CoarseAssignHip, "default_route", "cascade")  # (small problems take other paths by default)
+    rng = np.random.default_rng(hash((d, m, n)) % 2 ** 31)
+    x, cent = _data("gauss", 1, d, m, n, rng)
+    A, B = T(x[0]), T(cent[0])
+    op = K.CoarseAssignHip(distance="euclidean")
+    lab = op(A, B)
+    _, l32 = K.MaxSimHip(distance="euclidean")(A, B, dim=1)
+    assert torch.equal(lab, l32)
+    print("rechecked", (d, m, n), op.last_rechecked())
+    assert 0 < op.last_rechecked() < m
 
 
 def test_coarse_assign_cascade_ties_and_flags(monkeypatch):

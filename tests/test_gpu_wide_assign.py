@@ -1,4 +1,4 @@
-"""GPU: tpq_coarse_assign on wide vectors (128 < d <= 1024: csrc/lloyd.hip, "Wide vectors").
+"""GPU: tpq_coarse_assign on wide vectors (128 < d <= 1024: csrc/assign_cascade.hip, "Wide vectors").
 
 The coarse assign of IVFPQIndex.add / KMeans.predict (torchpq/clustering/KMeans.py:440-452 ->
 kernels/MaxSimCuda.py:296-340, max_sim.cu:182-309) at descriptor widths beyond SIFT's (GIST: 960).

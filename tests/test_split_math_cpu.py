@@ -90,7 +90,7 @@ def test_recheck_key_orders_like_value_desc_then_index_asc():
     assert np.array_equal((np.uint64(0xFFFFFFFF) - (key & np.uint64(0xFFFFFFFF))).astype(np.uint32), idx)
 
 
-# ---- round 3: the fp16 cascade (csrc/lloyd.hip) and the rank merge (scan_device.h) ----------
+# ---- round 3: the fp16 cascade (csrc/fp16_cascade.h, cascade_core.hip, assign_cascade.hip) and the rank merge (scan_device.h) ----------
 def test_level_1_dropped_piece_bound_holds_with_the_measured_norms():
     """|sum_k (a_k C_k - ah_k Ch_k)| <= |a - ah| (|Ch| + |C - Ch|) + |a| |C - Ch| for fp16 hi pieces (what emit()
     and gdecide_kernel bound level 1 with), and it is well below the worst case 2^-11 (|a| + |c|)^2"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""tpq_coarse_assign on wide vectors (128 < d <= 1024, the GEMM-shaped cascade of lloyd.hip) against the
+"""tpq_coarse_assign on wide vectors (128 < d <= 1024, the GEMM-shaped cascade of assign_cascade.hip) against the
 fp32 kernel: labels (must be equal), share of points pass 1 leaves undecided, candidate pairs per such point, time.
 
     python tools/wide_check.py [--shapes d,m,n;d,m,n...] [--data gauss|clustered] [--metric euclidean|inner]

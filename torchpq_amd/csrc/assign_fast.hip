@@ -34,19 +34,9 @@
 //      worst case and surplus blocks leave at once).
 #include <type_traits>
 
-#include "common.h"
+#include "fp16_cascade.h"  // lloyd_assign*, lloyd_wide_supported (assign_cascade.hip), launch_max_sim_list (kmeans.hip)
 
 namespace tpq {
-// the three-level fp16 cascade of lloyd.hip for one problem with many centroids (euclidean, d <= 128)
-int lloyd_assign_supported(int d, int64_t m, int n, int route);
-size_t lloyd_assign_workspace_bytes(int d, int64_t m, int n);
-size_t lloyd_assign_count_offset(int d, int64_t m, int n);
-int lloyd_wide_supported(int d, int64_t m, int n);
-int lloyd_assign(const float* A, const float* B, float* vals, int64_t* inds, int d, int64_t m, int n, int euclid, char* ws,
-                 hipStream_t st);
-int launch_max_sim_list(const float* A, const float* B, float* vals, int64_t* inds, int l, int d, int m, int n,
-                        int euclid, const int* list, const int* count, unsigned long long* keys, float* Ac, int cap,
-                        hipStream_t st);  // kmeans.hip
 namespace afast {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -952,7 +942,7 @@ extern "C" int tpq_coarse_assign_route(const float* A, const float* B, float* va
     check_hip(hipMemsetAsync(ws, 0, 4, st), "coarse_assign memset");
     return tpq_max_sim(A, B, vals ? vals : reinterpret_cast<float*>(ws + 256), inds, 1, d, (int)m, n, metric, stream);
   }
-  if (d > 128 || (euclid && lloyd_assign_supported(d, m, n, route))) {  // the fp16 cascade (lloyd.hip)
+  if (d > 128 || (euclid && lloyd_assign_supported(d, m, n, route))) {  // the fp16 cascade (assign_cascade.hip)
     char* cws = ws + af_old_total(d, m, n);
     int rc = lloyd_assign(A, B, vals, inds, d, m, n, euclid, cws, st);
     if (rc) return rc;

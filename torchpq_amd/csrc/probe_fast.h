@@ -1,4 +1,4 @@
-// Interface between tpq_ivfpq_coarse_probe (select.hip) and the fp16 selection pass of lloyd.hip: the coarse step of
+// Interface between tpq_ivfpq_coarse_probe (select.hip) and the fp16 selection pass of probe_sims.hip: the coarse step of
 // search() at many cells (IVF4096 / IVF16384 of the reference's benchmark grid), where the fp32-MFMA similarity GEMM
 // (75 TF/s) was 40-85 % of a search.  The reference offers a reduced-precision coarse GEMM behind use_tensor_core /
 // fp16_scale_mode (torchpq/metric.py:47-73, index/IVFPQIndex.py:98-125) and accepts its errors; here the fp16 pass only
