@@ -1,4 +1,4 @@
-"""GPU: the large-batch route of the packed scan at m = 64 (csrc/scan_device.h "dump mode": the scan workgroups stream
+"""GPU: the large-batch route of the packed scan at m = 64 (csrc/scan_packed_kernel.h "dump mode": the scan workgroups stream
 over the 16-bit selection table and end with their lists of fast values, scan_finish_exact_kernel evaluates the band's
 survivors exactly) against the reference-layout kernel, values and addresses bit for bit
 (replaces ivfpq_topk.cu:822-971, kernels/IVFPQTopkCuda.py:81-142).

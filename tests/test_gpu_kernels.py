@@ -65,10 +65,13 @@ def test_scan_matches_golden(K, name, layout, request):
                 assert np.array_equal(N(i), fx[f"orc_ids_s{smart}_k{k}"]), (smart, k, n_split)
 
 
-def _random_index(rng, m, n_cells, mean_size, n_tomb=0, dup_frac=0.0):
-    """Ragged cells (some empty) with slack, random codes; optional tombstones / duplicate codes."""
-    sizes = rng.poisson(mean_size, n_cells).astype(np.int64)
-    sizes[rng.random(n_cells) < 0.1] = 0
+def _random_index(rng, m, n_cells, mean_size, n_tomb=0, dup_frac=0.0, sizes=None):
+    """Ragged cells (some empty) with slack, random codes; optional tombstones / duplicate codes.
+    `sizes`: the cells' sizes, given instead of drawn."""
+    if sizes is None:
+        sizes = rng.poisson(mean_size, n_cells).astype(np.int64)
+        sizes[rng.random(n_cells) < 0.1] = 0
+    sizes = np.asarray(sizes, np.int64)
     caps = sizes + rng.integers(0, 9, n_cells)
     start = np.cumsum(caps) - caps
     cap = int(caps.sum()) + 5
@@ -111,6 +114,7 @@ def _random_index(rng, m, n_cells, mean_size, n_tomb=0, dup_frac=0.0):
     (96, 100, 10, 2, "packed", 7, 0.0),
     (128, 100, 10, 1, "packed", 0, 0.0),
     (128, 500, 10, 3, "packed", 0, 0.3),
+    (64, 510, 12, 1, "packed", 0, 0.0),    # k in (504, 512] at m = 64: the pools of 1 024 entries (with counting rounds)
 ])
 def test_scan_random_vs_oracle(K, m, k, n_probe, n_split, layout, tomb, dup):
     rng = np.random.default_rng(hash((m, k, n_probe, n_split)) % 2**32)
@@ -138,10 +142,49 @@ def test_scan_random_vs_oracle(K, m, k, n_probe, n_split, layout, tomb, dup):
         assert np.array_equal(N(v2), ev) and np.array_equal(N(a2), ea)
 
 
+@pytest.mark.parametrize("m,k,n_probe,mean,tomb,route,nw,tile", [
+    (16, 40, 8, 300, 0, "dump_f32", 4, 256),        # cells of 2 tiles: 14 or 16 tiles per workgroup
+    (64, 100, 5, 150, 25, "dump_sel16", 4, 64),     # cells of 3 tiles: 12 or 15 tiles per workgroup; tombstones
+    (64, 300, 4, 450, 0, "dump_sel16_w8", 8, 64),   # cells of 7 or 8 tiles: 21 .. 32 tiles per workgroup
+])
+def test_scan_large_batch_routes_vs_oracle(K, m, k, n_probe, mean, tomb, route, nw, tile):
+    """The large-batch routes (the scan workgroup ends with its waves' lists of fast values; scan_finish_exact_kernel
+    does the rest) against the ORACLE, bit for bit: 1 024 queries (the routes' threshold), the LUT built in the
+    workgroups, cells of unequal size -- one empty, none a multiple of the tile (`tile` slots: 64 x slots per lane) --
+    and per-query probe counts.  A query that probes all its cells is between 2 NW + 1 and 4 NW + 1 tiles (NW = `nw`
+    waves per workgroup, one workgroup per query): the tile pipeline's prologue, steady state and both exits.  The
+    shape is asserted, not hoped for."""
+    rng = np.random.default_rng(m * 1000 + k)
+    n_cells, nq, ds = 40, 1024, 2
+    sizes = mean - 20 + (np.arange(n_cells) * 7) % 41
+    sizes[sizes % tile == 0] += 1
+    sizes[0] = 0
+    storage, is_empty, start, sizes, a2i = _random_index(rng, m, n_cells, mean, tomb, 0.0, sizes=sizes)
+    cb = (rng.standard_normal((m, ds, 256)) * 20).astype(np.float32)
+    q = (rng.standard_normal((m * ds, nq)) * 20).astype(np.float32)
+    cells = np.stack([rng.permutation(n_cells)[:n_probe] for _ in range(nq)])
+    cells[0, 0] = 0 if 0 not in cells[0] else cells[0, 0]  # (query 0 probes the empty cell for sure)
+    npl = rng.integers(0, n_probe + 1, nq).astype(np.int64)
+    npl[:900] = n_probe
+    cs, sz = start[cells], sizes[cells]
+    assert (sizes[1:] % tile != 0).all() and len(set(sizes.tolist())) > 10
+    tiles = ((sz + tile - 1) // tile)[npl == n_probe].sum(axis=1)
+    assert 2 * nw + 1 <= tiles.min() and tiles.max() <= 4 * nw + 1, (tiles.min(), tiles.max())
+    ev, ea = c_oracle.scan_topk(storage, c_oracle.adc_lut(q, cb, "euclidean"), is_empty, cs, sz, npl, k)
+    scan = K.IVFPQTopkHip(m=m)
+    st = T(storage)
+    v, a, i = scan.topk_fused(st, T(q), T(cb), T(is_empty) if tomb else None, T(cs), T(sz), T(npl), n_candidates=k,
+                              packed=K.PackCodesHip()(st), address2id=T(a2i), n_split=1, slots_hint=n_probe * mean)
+    assert scan.last_route() == route
+    assert np.array_equal(N(v), ev)
+    assert np.array_equal(N(a), ea)
+    assert np.array_equal(N(i), orc.get_id_by_address(a2i, ea))
+
+
 @pytest.mark.parametrize("m,k,n_split", [(64, 256, 1), (64, 200, 2), (16, 100, 1), (32, 500, 1)])
 def test_scan_short_lists_overflow_is_redone_exactly(K, m, k, n_split):
     """The packed scan sizes its per-wave candidate lists for 2k entries over the workgroup
-    (scan_device.h list_regs_scan), counting on the round-robin tile deal to spread the top-k.  Here
+    (scan_host.h list_regs_scan), counting on the round-robin tile deal to spread the top-k.  Here
     every one of the 1024 best vectors of query 0 sits in a 64-slot block whose tile goes to wave 0
     (blocks 2048 slots apart: tile index = 0 mod 32 for 64-, 128- and 256-slot tiles), so wave 0's list
     overflows with live candidates; the query must be flagged and redone by the exact kernel, and

@@ -2,7 +2,7 @@
 
 The packed routes select with a fast sum (another association order; a 16-bit fixed-point table on the large-batch
 routes of m = 64) and keep what lies within a band of the running k-th value for the exact ascending-j chain; the band is
-2 * delta_rel * sum_j max|LUT_j| (csrc/scan_device.h; the residual scan adds |base| + cell_bound[cell]).  Bit-equality
+2 * delta_rel * sum_j max|LUT_j| (csrc/scan_packed_kernel.h; the residual scan adds |base| + cell_bound[cell]).  Bit-equality
 with the oracle therefore rests on band >= |fast - exact|, which zero-mean tables never strain: here the tables carry a
 large common offset (tests_support.offset_lut / offset_query_codebook), so that the bound is far above the spread of the
 candidates -- test_scan_band_inputs_cpu.py shows, without a kernel, that the order then changes the top-k members.

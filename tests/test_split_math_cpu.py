@@ -90,7 +90,7 @@ def test_recheck_key_orders_like_value_desc_then_index_asc():
     assert np.array_equal((np.uint64(0xFFFFFFFF) - (key & np.uint64(0xFFFFFFFF))).astype(np.uint32), idx)
 
 
-# ---- round 3: the fp16 cascade (csrc/fp16_cascade.h, cascade_core.hip, assign_cascade.hip) and the rank merge (scan_device.h) ----------
+# ---- round 3: the fp16 cascade (csrc/fp16_cascade.h, cascade_core.hip, assign_cascade.hip) and the rank merge (scan_shared.h) ----------
 def test_level_1_dropped_piece_bound_holds_with_the_measured_norms():
     """|sum_k (a_k C_k - ah_k Ch_k)| <= |a - ah| (|Ch| + |C - Ch|) + |a| |C - Ch| for fp16 hi pieces (what emit()
     and gdecide_kernel bound level 1 with), and it is well below the worst case 2^-11 (|a| + |c|)^2"""
@@ -127,7 +127,7 @@ def test_bound_norms_travel_as_bf16_rounded_up():
 
 
 def test_rank_merge_places_every_entry_once_with_duplicates_ranked_by_list():
-    """scan_device.h rank_merge: position = own position + per other list the entries that precede it (strictly
+    """scan_shared.h rank_merge: position = own position + per other list the entries that precede it (strictly
     better, or equal in an earlier list) -- a permutation of the merged order even with equal keys"""
     rng = np.random.default_rng(9)
     for L, LEN in ((8, 64), (4, 128), (3, 64)):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B of the slots per lane and tile (scan_device.h packed_slots): product against a -DTPQ_SLOTS_LOG2 variant.
+# Same-box A/B of the slots per lane and tile (scan_packed_kernel.h packed_slots): product against a -DTPQ_SLOTS_LOG2 variant.
 #   bash tools/ab_slots.sh s2 "12 16 20 24 28 40 48 56"
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 V="$1"

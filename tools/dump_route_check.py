@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The large-batch routes of the packed scan (dump mode + scan_finish_exact_kernel, csrc/scan_device.h) against the
+"""The large-batch routes of the packed scan (dump mode + scan_finish_exact_kernel, csrc/scan_packed_kernel.h, scan_finish.h) against the
 reference-layout kernel -- values and addresses bit for bit -- and their time, on synthetic uniform indexes; both
 LUT sources (the materialised table, the table built in the workgroup from query + codebook).
 

@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Refactor gate: do two revisions of the HIP sources compile to the same device code, kernel by kernel?
+
+For each translation unit, the parent's source (taken from git) and the working tree's are compiled to gfx950 device
+assembly with build.sh's flags; kernels are paired by symbol and compared as text -- instruction and label lines plus
+the `.amdhsa_` block (registers, LDS, scratch, wave limits), comments stripped, local labels renumbered in order of
+appearance.  Prints the kernel count per unit and every kernel that differs, is missing or is new; exit status 1 if any.
+
+    python tools/isa_diff.py [--parent HEAD] [--jobs 8] [--cache DIR] [unit ...]
+
+A unit is a file of torchpq_amd/csrc, `scan_packed.hip:64` for one per-M unit; default: scan.hip and scan_packed.hip
+at every M of build.sh.  --cache keeps the parent's assembly, per revision, between runs (one check per step of a refactor).
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join("torchpq_amd", "csrc")
+
+
+def compile_asm(csrc, unit, flags, out):
+    src, _, m = unit.partition(":")
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, *([f"-DTPQ_PACKED_M={m}"] if m else []),
+           "-x", "hip", "--cuda-device-only", "-S", os.path.join(csrc, src), "-o", out]
+    r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)  # (warnings are dropped; a failed compile shows them)
+    if r.returncode:
+        sys.exit(f"{unit}: hipcc failed ({csrc})\n{r.stderr[-4000:]}")
+
+
+def kernels(path):
+    """{symbol: normalised text} of every kernel of one assembly file: its body, then its .amdhsa_ block"""
+    bodies, blocks, cur = {}, {}, None
+    for line in open(path):
+        line = line.split(";")[0].rstrip()
+        head = line.split()[0] if line.strip() else ""
+        if head == ".amdhsa_kernel":  # (the block follows the kernel's last instruction, ahead of its .Lfunc_end)
+            cur = blocks.setdefault(line.split()[1], [])
+        elif head == ".end_amdhsa_kernel" or head.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is None:
+            if head.endswith(":") and line[0] not in ". \t":
+                cur = bodies.setdefault(head[:-1], [])
+        elif head and (not head.startswith(".") or head.endswith(":") or head.startswith(".amdhsa_")):
+            cur.append(" ".join(line.split()))  # an instruction, a label, or a line of the resource block
+    out = {}
+    for name, blk in blocks.items():
+        labels = {}
+        out[name] = re.sub(r"\.L[A-Za-z_]+\d+(?:_\d+)?", lambda t: labels.setdefault(t.group(0), f".L{len(labels)}"),
+                           "\n".join(bodies[name] + blk))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--parent", default="HEAD")
+    ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--cache", default=None, help="directory that keeps the parent's assembly")
+    ap.add_argument("units", nargs="*")
+    a = ap.parse_args()
+    text = open(os.path.join(ROOT, CSRC, "build.sh")).read()
+    flags = re.search(r"FLAGS=\((.*?)\)", text, re.S).group(1).split()
+    ms = re.search(r"for m in ([\d ]+);", text).group(1).split()
+    units = a.units or ["scan.hip"] + [f"scan_packed.hip:{m}" for m in ms]
+    with tempfile.TemporaryDirectory() as td:
+        rev = subprocess.check_output(["git", "-C", ROOT, "rev-parse", a.parent], text=True).strip()
+        old = os.path.join(a.cache or td, rev)  # (the parent's assembly, kept per revision)
+        os.makedirs(old, exist_ok=True)
+        subprocess.run(f"git -C '{ROOT}' archive {rev} | tar -x -C '{td}'", shell=True, check=True)
+        asm = {u: u.replace(":", "_") + ".s" for u in units}
+        jobs = [(os.path.join(td, CSRC), u, flags, os.path.join(old, f)) for u, f in asm.items()
+                if not os.path.exists(os.path.join(old, f))]
+        jobs += [(os.path.join(ROOT, CSRC), u, flags, os.path.join(td, f)) for u, f in asm.items()]
+        with ThreadPoolExecutor(a.jobs) as ex:
+            list(ex.map(lambda j: compile_asm(*j), jobs))
+        bad = 0
+        for u, f in asm.items():
+            ko, kn = kernels(os.path.join(old, f)), kernels(os.path.join(td, f))
+            diff = [f"missing {k}" for k in ko if k not in kn] + [f"new {k}" for k in kn if k not in ko] + \
+                   [f"differs {k}" for k in ko if k in kn and ko[k] != kn[k]]
+            print("\n  ".join([f"{u}: {len(ko)} kernels before, {len(kn)} after, {len(diff)} not identical"] + diff))
+            bad += len(diff)
+    print("identical" if not bad else f"{bad} kernel(s) not identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Builds libtorchpq_amd.so for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
 # Incremental: every object carries the compiler's own dependency list (build/<obj>.d, -MD), so a change to
-# scan_device.h rebuilds the scan units only -- not the k-means / cascade units, which take the longest; fp16_cascade.h
+# one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
+# k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip alone; fp16_cascade.h
 # rebuilds the four cascade units (cascade_core, assign_cascade, probe_sims, lloyd) and assign_fast; probe_fast.h
 # rebuilds probe_sims and select.
 # FORCE=1 rebuilds everything; JOBS=n bounds the parallel compiles (default: the host's cores).

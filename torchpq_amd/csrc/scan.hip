@@ -31,6 +31,7 @@
 #include <chrono>
 
 #include "scan_device.h"
+#include "scan_ref.h"
 
 namespace tpq {
 
@@ -184,7 +185,7 @@ static int fresh_epoch() {
   return (int)(((uint32_t)(ns ^ (ns >> 29)) * 0x9e3779b1u) | 1u);
 }
 
-// large batches of plain PQ at m = 64, k <= 504: dump mode over the 16-bit table (scan_device.h).
+// large batches of plain PQ at m = 64, k <= 504: dump mode over the 16-bit table (scan_packed_kernel.h, scan_finish.h).
 // (variants: TPQ_SCAN_DUMP=0 keeps the one-launch finish / the lists)
 // returns 0 (not this route), kDumpSel16 (four-wave workgroups) or kDumpSel16W8 (eight-wave workgroups: k in (248, 504]
 // where four waves would need longer lists than eight -- long cells; lists of <= 2 registers, 16 chunks per query)
@@ -332,7 +333,7 @@ static ScanPlan plan_scan(const ScanArgs& a, bool residual) {
       return p;
     }
   }
-  // the largest k, plain PQ: pool mode (scan_device.h) -- threshold lists of ceil(k / waves) entries, unsorted pools,
+  // the largest k, plain PQ: pool mode (scan_packed_kernel.h) -- threshold lists of ceil(k / waves) entries, unsorted pools,
   // one ranking kernel per query; flagged queries (a pool or the ranking buffer overflowed) redone exactly
   // (the ranking kernel takes a query's lists into LDS: fewer workgroups per query when they would not fit)
   if (pools) {
@@ -402,7 +403,7 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
       rc = u.pool(a, p.RL, st);
       break;
     }
-    // large batches of plain PQ, k <= 504: dump mode (scan_device.h) -- the scan workgroups stream over the selection
+    // large batches of plain PQ, k <= 504: dump mode (scan_packed_kernel.h) -- the scan workgroups stream over the selection
     // table (m = 64: 16-bit, 32 KiB, four workgroups per CU; m = 8, 16, 32: the fp32 table) and end with their lists of
     // fast values, one wave per query finishes
     case TPQ_SCAN_ROUTE_DUMP_F32:

@@ -53,7 +53,7 @@ __host__ __device__ constexpr int lut_dword(int m, int j, int c) {
   return k.base * 256 + c * k.size + (j - k.base);
 }
 
-// 16-bit selection table (scan_device.h "sel16"): HALFWORD of entry (j, c).  A 64-block keeps the two halves of its
+// 16-bit selection table (scan_lut.h "sel16"): HALFWORD of entry (j, c).  A 64-block keeps the two halves of its
 // sub-quantizers interleaved -- halfword c*64 + 2*(j' & 31) + (j' >> 5), j' = j - base -- so that the dword, hence the
 // bank, is c*32 + (j' & 31): the 32 lanes of a half-wave (32 distinct j' & 31) read 32 distinct banks.  Smaller blocks
 // (tails of an m that is not a multiple of 64) are laid out plainly.

@@ -1,6 +1,6 @@
 // Scan-layout list scan: one translation unit per sub-quantizer count, compiled with
 // -DTPQ_PACKED_M=<M> (build.sh) so the 5 x 2 x 5 kernel instantiations build in parallel.
-// Device code: scan_device.h; C ABI: scan.hip.
+// Device code: scan_device.h (one header per stage; the kernel itself: scan_packed_kernel.h); C ABI: scan.hip.
 #include "scan_device.h"
 
 #ifndef TPQ_PACKED_M
@@ -8,6 +8,9 @@
 #endif
 
 namespace tpq {
+
+// delta = 1.05 * 2 (M-1) u * sum_j max|LUT_j|,  u = 2^-24   (residual: M+1 roundings, see the kernel)
+constexpr float delta_rel(int M, bool RES) { return 1.05f * 2.0f * 5.9604645e-8f * (float)(RES ? M + 1 : M - 1); }
 
 template <int RL, int R, int M, bool RES>
 static int launch_packed(ScanArgs a, ResidualArgs ra, hipStream_t st) {
@@ -19,19 +22,16 @@ static int launch_packed(ScanArgs a, ResidualArgs ra, hipStream_t st) {
     if (a.fuse) {  // fused finish: one launch (scan.hip decides)
       int rc = set_lds(scan_packed_kernel<RL, M, false, R>, lds, "scan_packed_kernel (fused finish)");
       if (rc) return rc;
-      const float delta_rel = 1.05f * 2.0f * 5.9604645e-8f * (float)(M - 1);
       hipLaunchKernelGGL((scan_packed_kernel<RL, M, false, R>), dim3((unsigned)a.nq * a.n_split),
-                         dim3(packed_waves(M) * 64), lds, st, a, ra, delta_rel);
+                         dim3(packed_waves(M) * 64), lds, st, a, ra, delta_rel(M, false));
       TPQ_LAUNCH_CHECK("scan_packed_kernel (fused finish)");
       return TPQ_OK;
     }
   }
   int rc = set_lds(scan_packed_kernel<RL, M, RES>, lds, "scan_packed_kernel");
   if (rc) return rc;
-  // delta = 1.05 * 2 (M-1) u * sum_j max|LUT_j|,  u = 2^-24   (residual: M+1 roundings, see kernel)
-  const float delta_rel = 1.05f * 2.0f * 5.9604645e-8f * (float)(RES ? M + 1 : M - 1);
   hipLaunchKernelGGL((scan_packed_kernel<RL, M, RES>), dim3((unsigned)a.nq * a.n_split),
-                     dim3(packed_waves(M) * 64), lds, st, a, ra, delta_rel);
+                     dim3(packed_waves(M) * 64), lds, st, a, ra, delta_rel(M, RES));
   TPQ_LAUNCH_CHECK("scan_packed_kernel");
   const int n_lists = a.n_split * packed_waves(M);
   // merge waves per query: the largest power of two <= min(8, n_lists / 2) that divides n_lists
@@ -53,9 +53,8 @@ static int launch_pool(ScanArgs a, hipStream_t st) {
   const size_t lds = scan_lds_bytes_packed(M, RL, a.max_nprobe, fused_floats_of(a), false);
   int rc = set_lds(scan_packed_kernel<RL, M, false, RM>, lds, "scan_packed_kernel (pool mode)");
   if (rc) return rc;
-  const float delta_rel = 1.05f * 2.0f * 5.9604645e-8f * (float)(M - 1);
   hipLaunchKernelGGL((scan_packed_kernel<RL, M, false, RM>), dim3((unsigned)a.nq * a.n_split),
-                     dim3(packed_waves(M) * 64), lds, st, a, ResidualArgs{}, delta_rel);
+                     dim3(packed_waves(M) * 64), lds, st, a, ResidualArgs{}, delta_rel(M, false));
   TPQ_LAUNCH_CHECK("scan_packed_kernel (pool mode)");
   constexpr int NW = packed_waves(M), LEN = 64 * (NW == 4 ? 8 : 4);
   const size_t mlds = (size_t)a.n_split * NW * LEN * 8 + (size_t)((a.k + 63) / 64 * 64) * 8;
@@ -66,7 +65,15 @@ static int launch_pool(ScanArgs a, hipStream_t st) {
   return TPQ_OK;
 }
 
-// dump modes (scan_device.h): the scan ends with the waves' lists of fast values; scan_finish_exact_kernel, one wave per
+// the finish kernel at 4, 8 or 16 chunks of 64 keys per query, by the T = splits x waves x list registers a query comes in
+template <int RM, int M, int DS, bool FROM_LUT, class Go>
+static int finish_by_chunks(int T, Go&& go) {
+  return T <= 4 ? go(scan_finish_exact_kernel<RM, M, DS, 4, FROM_LUT>)
+                : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, DS, 8, FROM_LUT>)
+                          : go(scan_finish_exact_kernel<RM, M, DS, 16, FROM_LUT>));
+}
+
+// dump modes (scan_packed_kernel.h): the scan ends with the waves' lists of fast values; scan_finish_exact_kernel, one wave per
 // query, evaluates the band's survivors exactly and writes the result.  m = 64: the 16-bit table (kDumpSel16 / W8);
 // m = 8, 16, 32 (round 6): the fp32 table the four-wave workgroups of the short codes stream over anyway (kDumpF32) --
 // what they gain is the early end of the scan workgroup.
@@ -96,24 +103,13 @@ static int launch_finish(const ScanArgs& a, int nw_scan, int RL, hipStream_t st)
   };
   const int T = a.n_split * nw_scan * RL;  // (16: the split tail of a batch, ScanArgs::unsplit)
   if constexpr (dump_built(M, kDumpSel16)) {
-    if (a.ds == 1)
-      return T <= 4 ? go(scan_finish_exact_kernel<RM, M, 1, 4>)
-                    : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, 1, 8>) : go(scan_finish_exact_kernel<RM, M, 1, 16>));
-    return T <= 4 ? go(scan_finish_exact_kernel<RM, M, 2, 4>)
-                  : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, 2, 8>) : go(scan_finish_exact_kernel<RM, M, 2, 16>));
+    if (a.ds == 1) return finish_by_chunks<RM, M, 1, false>(T, go);
+    return finish_by_chunks<RM, M, 2, false>(T, go);
   } else {
-    if (from_lut)
-      return T <= 4 ? go(scan_finish_exact_kernel<RM, M, 0, 4, true>)
-                    : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, 0, 8, true>)
-                              : go(scan_finish_exact_kernel<RM, M, 0, 16, true>));
+    if (from_lut) return finish_by_chunks<RM, M, 0, true>(T, go);
     // (the sub-vector length of a 128-dimensional index compiled in: SIFT's m = 32 -> ds = 4; others read it)
-    constexpr int DSF = 128 / M;
-    if (a.ds == DSF)
-      return T <= 4 ? go(scan_finish_exact_kernel<RM, M, DSF, 4>)
-                    : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, DSF, 8>)
-                              : go(scan_finish_exact_kernel<RM, M, DSF, 16>));
-    return T <= 4 ? go(scan_finish_exact_kernel<RM, M, 0, 4>)
-                  : (T <= 8 ? go(scan_finish_exact_kernel<RM, M, 0, 8>) : go(scan_finish_exact_kernel<RM, M, 0, 16>));
+    if (a.ds == 128 / M) return finish_by_chunks<RM, M, 128 / M, false>(T, go);
+    return finish_by_chunks<RM, M, 0, false>(T, go);
   }
 }
 
@@ -122,15 +118,14 @@ static int launch_dump(ScanArgs a, hipStream_t st) {
   const size_t lds = scan_lds_bytes_dump(M, is_sel16(MODE), scan_waves(M, MODE), a.max_nprobe, fused_floats_of(a));
   int rc = set_lds(scan_packed_kernel<RL, M, false, MODE>, lds, "scan_packed_kernel (dump mode)");
   if (rc) return rc;
-  const float delta_rel = 1.05f * 2.0f * 5.9604645e-8f * (float)(M - 1);
   constexpr int NW = scan_waves(M, MODE);
   const unsigned blocks = (unsigned)a.unsplit + (unsigned)(a.nq - a.unsplit) * (unsigned)a.n_split;
   hipLaunchKernelGGL((scan_packed_kernel<RL, M, false, MODE>), dim3(blocks), dim3(NW * 64), lds, st, a,
-                     ResidualArgs{}, delta_rel);
+                     ResidualArgs{}, delta_rel(M, false));
   TPQ_LAUNCH_CHECK("scan_packed_kernel (dump mode)");
   return launch_finish<(R < 2 ? 2 : R), M>(a, NW, RL, st);
 }
-// the pairs of TPQ_DUMP_PAIRS (scan_device.h), in its order; scan.hip plans no other (plan_scan)
+// the pairs of TPQ_DUMP_PAIRS (scan_args.h), in its order; scan.hip plans no other (plan_scan)
 template <int M, int MODE>
 static int dispatch_dump_mode(const ScanArgs& a, int RL, int R, hipStream_t st) {
   if constexpr (dump_built(M, MODE)) {

@@ -85,7 +85,7 @@ class IVFPQTopkHip:
         """diagnostics (synchronises; needs keep_workspace): queries of the last packed scan that were redone exactly --
         by the one-launch finisher's own redo branch (ws_delta[q] == 1) or, on the routes that end with the flag-gated
         exact kernel (the large-batch routes, the pools, the three-launch path: ws_delta holds a selection band there),
-        by that kernel, which leaves kRedoneMark = -1 (csrc/scan_device.h).  None on the reference-layout route, which
+        by that kernel, which leaves kRedoneMark = -1 (csrc/scan_args.h).  None on the reference-layout route, which
         writes no ws_delta."""
         ws = self.last_workspace
         route = self.last_route()
@@ -122,7 +122,7 @@ class IVFPQTopkHip:
         if self.n_cus is None:
             self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
         # four 4-wave workgroups per CU for short codes (m <= 32), two 8-wave ones while the LUT is
-        # <= 64 KiB, one 16-wave workgroup above (csrc/scan_device.h packed_waves)
+        # <= 64 KiB, one 16-wave workgroup above (csrc/scan_packed_kernel.h packed_waves)
         target = (4 if self.m <= 32 else 2 if self.m <= 64 else 1) * self.n_cus
         if n_query >= target:
             return 1
