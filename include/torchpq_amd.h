@@ -512,6 +512,37 @@ int tpq_ivfpqr_rerank(const uint8_t* storage, int64_t capacity, int m, int m_r, 
                       int k1, int k, int use_residual, int distance, const int64_t* address2id, float* out_vals,
                       int64_t* out_address, int64_t* out_ids, tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * IVFFlatIndex list scan + top-k: the probed cells hold the vectors themselves (no reference counterpart; the
+ * index every IVF library ships between exact search and IVFPQ).
+ *
+ * vectors      f32 [d][n_slots]     dimension-major, slot-contiguous: CellContainer._storage of code_size = 4 d
+ *                                   (u8 [d][n_slots][4]) read as fp32 -- row i holds the four bytes of component i
+ * query        f32 [d][nq]          (pre-normalised by the host for TPQ_METRIC_INNER)
+ * is_empty     u8  [n_slots] or NULL (1 = tombstone)
+ * cell_start / cell_size i64 [nq][max_nprobe]; n_probe_list i64 [nq], clamped to [0, max_nprobe]; a probe whose
+ *              start equals the previous probe's start is skipped, as in tpq_ivfpq_scan_topk
+ * out_vals f32 / out_addr i64 [nq][k]
+ *
+ * Value of a slot with vector x (all fp32, no fma, i ascending, acc starts at 0.f):
+ *       TPQ_METRIC_NEG_SQ_L2:  t = q_i - x_i;  acc = acc - t*t
+ *       TPQ_METRIC_INNER:      acc = acc + q_i * x_i
+ * Output per query: the k best live slots of its probed cells by (value descending, address ascending);
+ * tombstoned slots, slots outside [start, start + size) or outside the storage, and slots whose value is NaN never
+ * enter; positions beyond the candidates are (-inf, -1); a slot whose value is -inf keeps its address and stands
+ * ahead of them.  A query with a NaN or +-Inf component (or one whose products overflow) still returns: which slots
+ * its own row holds is not pinned, and the rows of the other queries are what they are without it.
+ * 1 <= k <= 1024; n_slots < 2^31 - 1, else TPQ_ERR_UNSUPPORTED; any d >= 1 (the only LDS that grows with d is the
+ * query itself).  n_split >= 1 workgroups share a query's tiles (small batches; the caller picks it from nq and
+ * the CU count) and a second launch merges their lists through the caller's workspace of
+ * tpq_ivfflat_scan_workspace_bytes(nq, k, n_split) bytes (0 when n_split == 1).  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+size_t tpq_ivfflat_scan_workspace_bytes(int nq, int k, int n_split);
+int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_t* is_empty,
+                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                          float* out_vals, int64_t* out_addr, int64_t n_slots, int d, int nq, int max_nprobe, int k,
+                          int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

@@ -1,5 +1,5 @@
 // Device code of the IVF list scan (shared by scan.hip and the per-M scan_packed.hip units), one header per stage;
-// scan.hip adds scan_ref.h (the reference-layout kernels), which the per-M units do not parse.
+// scan.hip and scan_flat.hip add scan_ref.h (the reference-layout kernels, the split merge), which the per-M units do not parse.
 #pragma once
 #include "scan_args.h"           // ScanArgs, ResidualArgs, the modes of scan_packed_kernel (kDump*, TPQ_DUMP_PAIRS), TPQ_PROF, lds_poll_*
 #include "scan_shared.h"         // wait_vmcnt, probe table, store_list / merge_list / write_final / finish_query, fused LUT, rank_merge

@@ -1,4 +1,4 @@
-// IVF list scan: the reference-layout kernels (exact; plain and residual PQ) and their split merge.  scan.hip only.
+// IVF list scan: the reference-layout kernels (exact; plain and residual PQ) and their split merge.  scan.hip and scan_flat.hip (the merge) only.
 #pragma once
 #include "scan_shared.h"
 

@@ -1,0 +1,157 @@
+"""IVFFlatIndex: coarse quantizer and inverted lists with the vectors stored as they are.
+
+Recall is limited only by `n_probe`, not by a product quantizer.  The container is CellContainer unchanged: a vector
+of d floats is stored as code_size = 4 d bytes, row i holding the four bytes of component i, so `_storage` is uint8
+[d, capacity, 4] and `_storage.view(torch.float32)` is [d, capacity, 1] -- dimension-major and slot-contiguous, the
+layout FlatIndex uses, fully coalesced for the list scan (tpq_ivfflat_scan_topk, csrc/scan_flat.hip), which reads
+it in place.  add / expand / remove / tombstones / `_address2id` / state_dict are the container's.
+
+The coarse step is IVFPQIndex's (index/_coarse.py).
+"""
+import torch
+
+from .. import util
+from ..codec import VQCodec
+from ..container import CellContainer
+from ..fn import Topk
+from ..kernels import CoarseProbeHip, CoarseSelectHip, IVFFlatTopkHip, SmartProbingHip
+from ._coarse import CoarseProbeMixin
+
+
+class IVFFlatIndex(CoarseProbeMixin, CellContainer):
+    def __init__(self, d_vector, n_cells=128, initial_size=None, expand_step_size=128, expand_mode="double",
+                 distance="euclidean", device="cuda:0", verbose=0):
+        assert d_vector >= 1
+        assert distance in ("euclidean", "cosine")
+        if torch.device(device).type == "cuda":
+            assert torch.cuda.is_available(), "cuda is not available"
+        super().__init__(code_size=4 * d_vector, n_cells=n_cells, dtype="uint8", device=device,
+                         initial_size=initial_size, expand_step_size=expand_step_size,
+                         expand_mode=expand_mode, use_inverse_id_mapping=True, contiguous_size=4,
+                         verbose=verbose)
+        self.d_vector = d_vector
+        self.distance = distance
+        self.verbose = verbose
+        self.n_probe = 1
+        self.use_cublas = True
+        self.use_fused_probe = True     # coarse sims + select + list extents + probe count: one call
+        self._use_smart_probing = True
+        self._smart_probing_temperature = 30.0
+        self.max_query_batch = 32768    # bounds the coarse step's [n_query, n_cells] matrix
+
+        self.vq_codec = VQCodec(n_clusters=n_cells, n_redo=1, max_iter=15, tol=1e-4,
+                                distance="euclidean", init_mode="random", verbose=verbose)
+        self._flat_topk = IVFFlatTopkHip()
+        self._topk = Topk()
+        self._smart_probing = SmartProbingHip()
+        self._coarse_select = CoarseSelectHip()
+        self._coarse_probe = CoarseProbeHip()
+        self.to(device)
+
+    def _after_load_state_dict(self):
+        self.to(self.device)
+        super()._after_load_state_dict()
+
+    # ---- the byte layout -----------------------------------------------------------------------------
+    @staticmethod
+    def vectors_to_codes(x):
+        """[d, n] float32 -> the container's code rows [4 d, n] uint8: row 4 i + b is byte b of component i"""
+        d, n = x.shape
+        return x.contiguous().view(torch.uint8).reshape(d, n, 4).transpose(1, 2).reshape(4 * d, n)
+
+    @staticmethod
+    def codes_to_vectors(codes):
+        """[4 d, n] uint8 -> [d, n] float32 (the inverse of vectors_to_codes)"""
+        d4, n = codes.shape
+        return codes.reshape(d4 // 4, 4, n).transpose(1, 2).contiguous().view(torch.float32).reshape(d4 // 4, n)
+
+    def _vectors(self):
+        """the stored vectors as the scan reads them, [d_vector, capacity] float32 (a view of `_storage`)"""
+        return self._storage.view(torch.float32)[:, :, 0]
+
+    # ---- train / add -----------------------------------------------------------------------------------
+    def train(self, x, force_retrain=False):
+        """x [d_vector, n_data] f32: the coarse k-means (n_cells) only."""
+        if self.vq_codec.is_trained and not force_retrain:
+            self.print_message("index is already trained", 1)
+            return
+        assert len(x.shape) == 2
+        assert x.shape[0] == self.d_vector
+        x = x.to(self.device)
+        if self.distance == "cosine":
+            x = util.normalize(x, dim=0)
+        self.print_message("start training VQ codec...", 1)
+        self.vq_codec.train(x.contiguous())
+        self.print_message("index is trained successfully!", 1)
+
+    def add(self, x, ids=None, return_address=False):
+        """x [d_vector, n] f32 (stored normalised for "cosine"), optional ids [n] int64 (default arange + max_id
+        + 1); returns ids (and the slot addresses if return_address)."""
+        assert len(x.shape) == 2
+        assert x.shape[0] == self.d_vector
+        assert x.dtype == torch.float32
+        assert self.vq_codec.is_trained, "index is not trained"
+        x = x.to(self.device)
+        if self.distance == "cosine":
+            x = util.normalize(x)
+        x = x.contiguous()
+        assigned_cells = self.vq_codec.encode(x)
+        return super().add(self.vectors_to_codes(x), cells=assigned_cells, ids=ids, return_address=return_address)
+
+    def reconstruct(self, ids=None, address=None):
+        """the stored vectors [d_vector, n] f32 of `ids` (or of slot addresses): bit for bit what add() stored
+        (the normalised vector for "cosine"); zero columns for unknown ids / invalid addresses"""
+        if ids is not None:
+            address = self.get_address_by_id(ids.to(self.device))
+        elif address is None:
+            raise RuntimeError("Need either ids or address")
+        address = address.to(self.device)
+        live = (address >= 0) & (address < self.capacity)
+        live &= self._is_empty[torch.where(live, address, torch.zeros_like(address))] == 0
+        address = torch.where(live, address, torch.full_like(address, -1))
+        return self.codes_to_vectors(self.get_data_by_address(address))
+
+    # ---- search ----------------------------------------------------------------------------------------
+    def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
+        """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
+        (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
+        the coarse step already gathered them.)"""
+        n_query = x.shape[1]
+        if n_probe_list is None:
+            n_probe_list = torch.full((n_query,), cells.shape[1], device=self.device, dtype=torch.long)
+        if _extents is None:
+            cell_start = self._cell_start[cells]
+            cell_size = self._cell_size[cells]
+        else:
+            cell_start, cell_size = _extents
+        # expected slots per query (host-side estimate, no sync): bounds the per-query split
+        slots_hint = cells.shape[1] * self.capacity // max(self.n_cells, 1)
+        vals, address = self._flat_topk(
+            self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, k,
+            is_empty=self._is_empty if self._has_holes else None, distance=self.distance, slots_hint=slots_hint)
+        ids = self.get_id_by_address(address)
+        return (vals, ids, address) if return_address else (vals, ids)
+
+    def graphed_search(self, n_query, k=1):
+        raise NotImplementedError("GraphedSearch captures IVFPQIndex.search only")
+
+    def search(self, x, k=1, return_address=False):
+        """x [d_vector, n_query] f32 -> (values f32 [n_query, k] descending, ids int64 [n_query, k][, address]);
+        values are -squared-L2 (euclidean) or the cosine similarity to the stored vectors; (-inf, -1) pads."""
+        assert len(x.shape) == 2
+        assert x.shape[0] == self.d_vector
+        assert 0 < k <= 1024
+        assert self.vq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        x = x.to(self.device)
+        if self.distance == "cosine":
+            x = util.normalize(x, dim=0)
+        n_query = x.shape[1]
+        out = []
+        for q0 in range(0, max(n_query, 1), self.max_query_batch):
+            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
+            topk_sims, cells, n_probe_list, extents = self._probe_with_extents(xb)
+            out.append(self.search_cells(x=xb, cells=cells, base_sims=topk_sims, n_probe_list=n_probe_list, k=k,
+                                         return_address=True, _extents=extents))
+        vals, ids, address = (out[0] if len(out) == 1 else (torch.cat(t, 0) for t in zip(*out)))
+        return (vals, ids, address) if return_address else (vals, ids)

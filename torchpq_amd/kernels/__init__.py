@@ -16,7 +16,7 @@ __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "packed_chunk_width", "PACKED_M",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "packed_chunk_width", "PACKED_M",
 ]
 
 # n_subvectors with an instantiated scan-layout kernel (= TPQ_PACKED_M_LIST in csrc/scan_device.h)
@@ -1075,3 +1075,69 @@ class IVFPQRerankHip:
                     ptr(cand_address), k1, k, int(bool(use_residual)), metric, ptr(address2id), ptr(values),
                     ptr(address), ptr(ids), stream_ptr(device)), "tpq_ivfpqr_rerank")
         return (values, address) if ids is None else (values, address, ids)
+
+
+class IVFFlatTopkHip:
+    """The list scan of IVFFlatIndex (tpq_ivfflat_scan_topk, csrc/scan_flat.hip): the probed cells hold the vectors
+    themselves; value and order are defined in include/torchpq_amd.h."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    def _n_split(self, n_query, device, slots_hint=None):
+        """Workgroups per query so that a small batch still fills the chip (two 8-wave workgroups per CU);
+        ``slots_hint`` (expected slots scanned per query) caps it so that every wave still walks >= 4 tiles."""
+        if self.n_cus is None:
+            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+        target = 2 * self.n_cus
+        if n_query >= target:
+            return 1
+        split = max(1, min(64, target // max(n_query, 1)))
+        if slots_hint is not None:
+            split = max(1, min(split, int(slots_hint) // (64 * 8 * 4)))
+        return split
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          vectors: [d, n_slots] float32 (or [d, n_slots, 1]: CellContainer._storage.view(torch.float32))
+          query: [d, n_query] float32 (normalised by the caller for "cosine")
+          cell_start / cell_size: [n_query, max_n_probe] int64; n_probe_list: [n_query] int64
+          is_empty: [n_slots] uint8, or None when no slot inside a cell is a tombstone
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        if vectors.dim() == 3:
+            assert vectors.shape[2] == 1
+            vectors = vectors[:, :, 0]
+        d, n_slots = vectors.shape
+        n_query, n_probe = cell_start.shape
+        assert query.shape == (d, n_query)
+        assert vectors.dtype == query.dtype == torch.float32
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        query = query.contiguous()
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list)
+        device = vectors.device
+        values = torch.empty(n_query, k, device=device, dtype=torch.float32)
+        address = torch.empty(n_query, k, device=device, dtype=torch.int64)
+        if n_query == 0:
+            return values, address
+        lib = load()
+        if n_split is None:
+            n_split = self._n_split(n_query, device, slots_hint)
+        self.last_n_split = n_split
+        ws_bytes = lib.tpq_ivfflat_scan_workspace_bytes(n_query, k, n_split)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+        metric = _lib.METRIC_NEG_SQ_L2 if distance == "euclidean" else _lib.METRIC_INNER
+        with torch.cuda.device(device):
+            check(lib.tpq_ivfflat_scan_topk(
+                ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+                ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric, n_split, ptr(ws), ws_bytes,
+                stream_ptr(device)), "tpq_ivfflat_scan_topk")
+        return values, address
