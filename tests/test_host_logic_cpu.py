@@ -23,6 +23,26 @@ def test_scan_split_heuristic():
     assert big._n_split(1, "cuda:0", slots_hint=64 * 1024) == 16
 
 
+def test_flat_scan_split_heuristic():
+    """two 8-wave workgroups per CU, and at least 4 tiles of 64 slots per wave"""
+    from torchpq_amd.kernels import IVFFlatTopkHip
+    scan = IVFFlatTopkHip()
+    scan.n_cus = 256
+    assert scan._n_split(512, "cuda:0") == 1
+    assert scan._n_split(256, "cuda:0") == 2
+    assert scan._n_split(1, "cuda:0") == 64
+    assert scan._n_split(1, "cuda:0", slots_hint=32 * 1024) == 16
+    assert scan._n_split(1, "cuda:0", slots_hint=100) == 1
+
+
+def test_kernels_all_resolves():
+    import torchpq_amd.kernels as K
+    assert len(set(K.__all__)) == len(K.__all__)
+    for name in K.__all__:
+        assert getattr(K, name) is not None, name
+    assert {"CoarseAssignHip", "MaxSimSelectHip", "LloydStepHip"} <= set(K.__all__)
+
+
 def test_scan_layout_policy_and_instantiated_m():
     from torchpq_amd.index import IVFPQIndex
     from torchpq_amd.kernels import PACKED_M, packed_chunk_width

@@ -69,13 +69,18 @@ class CellContainer(BaseContainer):
     def n_items(self):
         return self._cell_size.sum().item()
 
+    def _scan_codes(self):
+        """the code rows a list scan reads, [rows, capacity, 4] (IVFPQRIndex stores more rows than it scans)"""
+        return self._storage
+
     def packed_storage(self):
-        """The scan-layout codes, (re)built if stale."""
-        if self._packed is None or self._packed.shape[1] != self._storage.shape[1]:
+        """The scan-layout copy of `_scan_codes()`, (re)built if stale."""
+        codes = self._scan_codes()
+        if self._packed is None or self._packed.shape[1] != codes.shape[1]:
             self._packed = None
             self._packed_valid = False
         if not self._packed_valid:
-            self._packed = self._pack_codes_hip(self._storage, self._packed)
+            self._packed = self._pack_codes_hip(codes, self._packed)
             self._packed_valid = True
         return self._packed
 

@@ -10,11 +10,8 @@ The coarse step is IVFPQIndex's (index/_coarse.py).
 """
 import torch
 
-from .. import util
-from ..codec import VQCodec
 from ..container import CellContainer
-from ..fn import Topk
-from ..kernels import CoarseProbeHip, CoarseSelectHip, IVFFlatTopkHip, SmartProbingHip
+from ..kernels import IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
 
 
@@ -32,20 +29,9 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         self.d_vector = d_vector
         self.distance = distance
         self.verbose = verbose
-        self.n_probe = 1
         self.use_cublas = True
-        self.use_fused_probe = True     # coarse sims + select + list extents + probe count: one call
-        self._use_smart_probing = True
-        self._smart_probing_temperature = 30.0
-        self.max_query_batch = 32768    # bounds the coarse step's [n_query, n_cells] matrix
-
-        self.vq_codec = VQCodec(n_clusters=n_cells, n_redo=1, max_iter=15, tol=1e-4,
-                                distance="euclidean", init_mode="random", verbose=verbose)
+        self._init_coarse(n_cells, verbose)
         self._flat_topk = IVFFlatTopkHip()
-        self._topk = Topk()
-        self._smart_probing = SmartProbingHip()
-        self._coarse_select = CoarseSelectHip()
-        self._coarse_probe = CoarseProbeHip()
         self.to(device)
 
     def _after_load_state_dict(self):
@@ -75,26 +61,17 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         if self.vq_codec.is_trained and not force_retrain:
             self.print_message("index is already trained", 1)
             return
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
+        x = self._prepare(x)
         self.print_message("start training VQ codec...", 1)
-        self.vq_codec.train(x.contiguous())
+        self.vq_codec.train(x)
         self.print_message("index is trained successfully!", 1)
 
     def add(self, x, ids=None, return_address=False):
         """x [d_vector, n] f32 (stored normalised for "cosine"), optional ids [n] int64 (default arange + max_id
         + 1); returns ids (and the slot addresses if return_address)."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
         assert x.dtype == torch.float32
+        x = self._prepare(x)
         assert self.vq_codec.is_trained, "index is not trained"
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x)
-        x = x.contiguous()
         assigned_cells = self.vq_codec.encode(x)
         return super().add(self.vectors_to_codes(x), cells=assigned_cells, ids=ids, return_address=return_address)
 
@@ -116,19 +93,11 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
         (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
         the coarse step already gathered them.)"""
-        n_query = x.shape[1]
-        if n_probe_list is None:
-            n_probe_list = torch.full((n_query,), cells.shape[1], device=self.device, dtype=torch.long)
-        if _extents is None:
-            cell_start = self._cell_start[cells]
-            cell_size = self._cell_size[cells]
-        else:
-            cell_start, cell_size = _extents
-        # expected slots per query (host-side estimate, no sync): bounds the per-query split
-        slots_hint = cells.shape[1] * self.capacity // max(self.n_cells, 1)
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
         vals, address = self._flat_topk(
             self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, k,
-            is_empty=self._is_empty if self._has_holes else None, distance=self.distance, slots_hint=slots_hint)
+            is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
         ids = self.get_id_by_address(address)
         return (vals, ids, address) if return_address else (vals, ids)
 
@@ -138,20 +107,11 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
     def search(self, x, k=1, return_address=False):
         """x [d_vector, n_query] f32 -> (values f32 [n_query, k] descending, ids int64 [n_query, k][, address]);
         values are -squared-L2 (euclidean) or the cosine similarity to the stored vectors; (-inf, -1) pads."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
+        x = self._prepare(x)
         assert 0 < k <= 1024
         assert self.vq_codec.is_trained, "index is not trained"
         assert 1 <= self.n_probe <= self.n_cells
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
-        n_query = x.shape[1]
-        out = []
-        for q0 in range(0, max(n_query, 1), self.max_query_batch):
-            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
-            topk_sims, cells, n_probe_list, extents = self._probe_with_extents(xb)
-            out.append(self.search_cells(x=xb, cells=cells, base_sims=topk_sims, n_probe_list=n_probe_list, k=k,
-                                         return_address=True, _extents=extents))
-        vals, ids, address = (out[0] if len(out) == 1 else (torch.cat(t, 0) for t in zip(*out)))
+        vals, ids, address = self._search_batches(x, lambda xb, sims, cells, n_probe_list, extents: self.search_cells(
+            x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=True,
+            _extents=extents))
         return (vals, ids, address) if return_address else (vals, ids)

@@ -9,10 +9,10 @@ library math is the coarse query x cell-centroid GEMM and the one-off residual t
 import torch
 
 from .. import util
-from ..codec import PQCodec, VQCodec
+from ..codec import PQCodec
 from ..container import CellContainer
-from ..fn import IVFPQTopk, Topk
-from ..kernels import CoarseProbeHip, CoarseSelectHip, SmartProbingHip
+from ..fn import IVFPQTopk
+from ..kernels import PACKED_M, ResidualPart1Hip, ResidualSlotTermsHip
 from ._coarse import CoarseProbeMixin
 
 
@@ -48,7 +48,6 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         self.distance = distance
         self.verbose = verbose
         self.pq_use_residual = pq_use_residual
-        self.n_probe = 1
         # residual search keeps a [n_cells, m, 256] table when it fits 4 GiB (IVFPQIndex.py:52-55)
         self._use_precomputed = bool(pq_use_residual and
                                      (n_cells * 256 * n_subvectors * 4) <= 4 * 1024 ** 3)
@@ -56,24 +55,15 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         self._part2_by_cell = None       # [n_cells, m, 256] contiguous copy for the scan kernels
         self._slot_terms = None          # (codes version, slot_term [capacity], cell_bound [n_cells])
         self._use_cublas = True
-        self._use_smart_probing = True
-        self._smart_probing_temperature = 30.0
         self._use_tensor_core = False
         self._fp16_scale_mode = "a"
         self.use_packed_layout = True   # MI355X scan layout (bank-conflict-free LDS look-ups)
         self.use_fused_lut = True       # build the ADC LUT inside the scan workgroups (no HBM table)
-        self.use_fused_probe = True     # coarse sims + select + list extents + probe count: one call
-        self.max_query_batch = 32768    # bounds the [m, nq, 256] LUT (m=64: 2 GiB per batch)
 
-        self.vq_codec = VQCodec(n_clusters=n_cells, n_redo=1, max_iter=15, tol=1e-4,
-                                distance="euclidean", init_mode="random", verbose=verbose)
+        self._init_coarse(n_cells, verbose)
         self.pq_codec = PQCodec(d_vector=d_vector, n_subvectors=n_subvectors, n_clusters=256,
                                 distance=distance, verbose=verbose)
         self._ivfpq_topk = IVFPQTopk(n_subvectors=n_subvectors, contiguous_size=self.contiguous_size)
-        self._topk = Topk()
-        self._smart_probing = SmartProbingHip()
-        self._coarse_select = CoarseSelectHip()
-        self._coarse_probe = CoarseProbeHip()
         self.to(device)
 
     # ---- knobs (reference :89-232) ---------------------------------------------------------------
@@ -146,7 +136,6 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     def _residual_slot_terms(self):
         """(slot_term, cell_bound) of the packed residual scan, rebuilt when the codes changed"""
         if self._slot_terms is None or self._slot_terms[0] != self._codes_version:
-            from ..kernels import ResidualSlotTermsHip
             st, cb = ResidualSlotTermsHip()(self._storage, self._part2_by_cell, self._cell_start,
                                             self._cell_size)
             self._slot_terms = (self._codes_version, st, cb)
@@ -183,12 +172,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         if self.vq_codec.is_trained and self.pq_codec.is_trained and not force_retrain:
             self.print_message("index is already trained", 1)
             return
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
-        x = x.contiguous()
+        x = self._prepare(x)
         self.print_message("start training VQ codec...", 1)
         code = self.vq_codec.train(x)
         self.print_message("start training PQ codec...", 1)
@@ -203,12 +187,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
 
     def encode(self, x):
         """x [d_vector, n] f32 -> PQ codes [n_subvectors, n] uint8"""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x)
-        x = x.contiguous()
+        x = self._prepare(x)
         if self.pq_use_residual:  # (pq_code, vq_code) of the residual x - centroid (:276-281)
             return self._encode_raw(x)
         return self.pq_codec.encode(x)
@@ -229,12 +208,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     def add(self, x, ids=None, return_address=False):
         """x [d_vector, n] f32, optional ids [n] int64 (default arange + max_id + 1);
         returns ids (and the slot addresses if return_address)."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x)
-        x = x.contiguous()
+        x = self._prepare(x)
         if self.pq_use_residual:
             codes, assigned_cells = self._encode_raw(x)
         else:
@@ -250,7 +224,6 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     # ---- residual tables (reference :366-405) -----------------------------------------------------
     def precomputed_adc_residual_precomputed(self, x):
         """(part1 [n_query, m, 256] = 2 q_j.r_jc,  part2 [n_cells, m, 256])"""
-        from ..kernels import ResidualPart1Hip
         part1 = ResidualPart1Hip()(x, self.pq_codec.codebook)
         if self._precomputed_part2 is None:
             self.precompute_part2()
@@ -269,86 +242,57 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         return (part1[:, None] + part2.permute(1, 2, 0, 3)).contiguous()
 
     # ---- search (reference :407-524) ---------------------------------------------------------------
-    def _scan_codes(self):
-        """the code rows the list scan reads, [n_subvectors / 4, capacity, 4] (IVFPQRIndex stores more rows)"""
-        return self._storage
+    def _scan_layout(self):
+        """the scan-layout copy of the codes for the plain scan, or None where the reference layout is kept (the
+        class attributes above)"""
+        m = self.n_subvectors
+        if self.use_packed_layout and m in PACKED_M and (
+                m >= self.packed_min_subvectors or m <= self.packed_max_short_subvectors):
+            return self.packed_storage()
+        return None
 
     def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False,
                      _extents=None):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
         (`_extents`: the cells' (start, size) when the coarse step already gathered them.)"""
-        n_query = x.shape[1]
-        if n_probe_list is None:
-            n_probe_list = torch.full((n_query,), cells.shape[1], device=self.device, dtype=torch.long)
-        if _extents is None:
-            cell_start = self._cell_start[cells]
-            cell_size = self._cell_size[cells]
-        else:
-            cell_start, cell_size = _extents
-        # expected slots per query (host-side estimate, no sync): bounds the per-query split
-        slots_hint = cells.shape[1] * self.capacity // max(self.n_cells, 1)
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        lists = dict(data=self._scan_codes(), cell_start=cell_start, cell_size=cell_size, is_empty=is_empty,
+                     n_probe_list=n_probe_list, address2id=self._address2id)
+        # the fused paths re-read the codebook (m*ds KiB, L2-resident) per workgroup instead of a
+        # 1-KiB-per-sub-quantizer LUT row from HBM: a win while the sub-vectors are short
+        fused = self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector
         if self.pq_use_residual:
             assert base_sims is not None, "base_sims is required when pq_use_residual is True"
-            is_empty = self._is_empty if self._has_holes else None
-            from ..kernels import PACKED_M
             if self.use_precomputed and self.use_packed_layout and self.n_subvectors in PACKED_M:
                 # scan layout: part1[q] staged once per query (built in the workgroup while the
                 # sub-vectors are short), the cell-dependent half folded into a per-slot constant
                 if self._precomputed_part2 is None:
                     self.precompute_part2()
                 slot_term, cell_bound = self._residual_slot_terms()
-                fused = self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector
                 part1 = None if fused else self.precomputed_adc_residual_precomputed(x)[0]
-                topk_val, topk_address, topk_ids = self._ivfpq_topk._scan.topk_residual_packed(
-                    data=self._scan_codes(), packed=self.packed_storage(), part2=self._part2_by_cell,
-                    slot_term=slot_term, cell_bound=cell_bound, cells=cells, base_sims=base_sims,
-                    is_empty=is_empty, cell_start=cell_start, cell_size=cell_size,
-                    n_probe_list=n_probe_list, n_candidates=k, part1=part1,
-                    query=x if fused else None,
-                    codebook=self.pq_codec.codebook if fused else None,
-                    address2id=self._address2id, slots_hint=slots_hint)
+                found = self._ivfpq_topk._scan.topk_residual_packed(
+                    packed=self.packed_storage(), part2=self._part2_by_cell, slot_term=slot_term,
+                    cell_bound=cell_bound, cells=cells, base_sims=base_sims, n_candidates=k, part1=part1,
+                    query=x if fused else None, codebook=self.pq_codec.codebook if fused else None,
+                    slots_hint=slots_hint, **lists)
             elif self.use_precomputed:
                 part1, part2 = self.precomputed_adc_residual_precomputed(x)
-                topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_residual_precomputed(
-                    data=self._scan_codes(), part1=part1, part2=part2, cells=cells, base_sims=base_sims,
-                    cell_start=cell_start, cell_size=cell_size, is_empty=is_empty,
-                    n_probe_list=n_probe_list, k=k, address2id=self._address2id)
+                found = self._ivfpq_topk.topk_residual_precomputed(
+                    part1=part1, part2=part2, cells=cells, base_sims=base_sims, k=k, **lists)
             else:
-                precomputed = self.precomputed_adc_residual(x, cells)
-                topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_residual(
-                    data=self._scan_codes(), base_sims=base_sims, precomputed=precomputed,
-                    cell_start=cell_start, cell_size=cell_size, is_empty=is_empty,
-                    n_probe_list=n_probe_list, k=k, address2id=self._address2id)
-            if return_address:
-                return topk_val, topk_ids, topk_address
-            return topk_val, topk_ids
-        packed = None
-        if self.use_packed_layout:
-            from ..kernels import PACKED_M
-            if self.n_subvectors in PACKED_M and (
-                    self.n_subvectors >= self.packed_min_subvectors
-                    or self.n_subvectors <= self.packed_max_short_subvectors):
-                packed = self.packed_storage()
-        # the fused path re-reads the codebook (m*ds KiB, L2-resident) per workgroup instead of a
-        # 1-KiB-per-sub-quantizer LUT row from HBM: a win while the sub-vectors are short
-        if self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector:
-            topk_val, topk_address, topk_ids = self._ivfpq_topk.topk_fused(
-                data=self._scan_codes(), query=x, codebook=self.pq_codec.codebook, cell_start=cell_start,
-                cell_size=cell_size, is_empty=self._is_empty if self._has_holes else None,
-                n_probe_list=n_probe_list, k=k, distance=self.distance, packed=packed,
-                address2id=self._address2id, slots_hint=slots_hint)
-            if return_address:
-                return topk_val, topk_ids, topk_address
-            return topk_val, topk_ids
-        precomputed = self.pq_codec.precompute_adc(x)
-        topk_val, topk_address, topk_ids = self._ivfpq_topk.topk(
-            data=self._scan_codes(), precomputed=precomputed, cell_start=cell_start,
-            cell_size=cell_size, is_empty=self._is_empty if self._has_holes else None,
-            n_probe_list=n_probe_list, k=k, packed=packed, address2id=self._address2id,
-            slots_hint=slots_hint)
-        if return_address:
-            return topk_val, topk_ids, topk_address
-        return topk_val, topk_ids
+                found = self._ivfpq_topk.topk_residual(
+                    base_sims=base_sims, precomputed=self.precomputed_adc_residual(x, cells), k=k, **lists)
+        elif fused:
+            found = self._ivfpq_topk.topk_fused(
+                packed=self._scan_layout(), query=x, codebook=self.pq_codec.codebook, k=k, distance=self.distance,
+                slots_hint=slots_hint, **lists)
+        else:
+            found = self._ivfpq_topk.topk(
+                packed=self._scan_layout(), precomputed=self.pq_codec.precompute_adc(x), k=k,
+                slots_hint=slots_hint, **lists)
+        topk_val, topk_address, topk_ids = found
+        return (topk_val, topk_ids, topk_address) if return_address else (topk_val, topk_ids)
 
     def graphed_search(self, n_query, k=1):
         """search() for a fixed batch shape captured in one HIP graph (low-latency serving)"""
@@ -359,24 +303,10 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         """x [d_vector, n_query] f32 -> (values f32 [n_query, k] descending, ids int64 [n_query, k]);
         values are -squared-L2 (euclidean) or cosine similarity of the PQ reconstruction.
         `return_address` is accepted and ignored, as in the reference (:521)."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
+        x = self._prepare(x)
         assert 0 < k <= 1024
         assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
         assert 1 <= self.n_probe <= self.n_cells
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
-        n_query = x.shape[1]
-        vals, ids = [], []
-        for q0 in range(0, max(n_query, 1), self.max_query_batch):
-            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
-            topk_sims, cells, n_probe_list, extents = self._probe_with_extents(xb)
-            v, i = self.search_cells(x=xb, cells=cells, base_sims=topk_sims,
-                                     n_probe_list=n_probe_list, k=k, return_address=False,
-                                     _extents=extents)
-            vals.append(v)
-            ids.append(i)
-        if len(vals) == 1:
-            return vals[0], ids[0]
-        return torch.cat(vals, 0), torch.cat(ids, 0)
+        return self._search_batches(x, lambda xb, sims, cells, n_probe_list, extents: self.search_cells(
+            x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=False,
+            _extents=extents))

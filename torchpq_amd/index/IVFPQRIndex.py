@@ -71,19 +71,9 @@ class IVFPQRIndex(IVFPQIndex):
 
     # ---- the scan reads the first-stage rows only ----------------------------------------------------
     def _scan_codes(self):
-        """[n_subvectors / 4, capacity, 4]: a contiguous leading view of the container's rows"""
+        """[n_subvectors / 4, capacity, 4]: a contiguous leading view of the container's rows (the scan-layout
+        copy then holds the FIRST-STAGE rows only)"""
         return self._storage[:self.n_subvectors // self.contiguous_size]
-
-    def packed_storage(self):
-        """The scan-layout copy of the FIRST-STAGE rows, (re)built if stale."""
-        codes = self._scan_codes()
-        if self._packed is None or self._packed.shape[1] != codes.shape[1]:
-            self._packed = None
-            self._packed_valid = False
-        if not self._packed_valid:
-            self._packed = self._pack_codes_hip(codes, self._packed)
-            self._packed_valid = True
-        return self._packed
 
     def set_data_by_address(self, data, address):
         # the container's scatter would update the scan-layout copy as if it held all code_size rows:
@@ -101,12 +91,7 @@ class IVFPQRIndex(IVFPQIndex):
                 and not force_retrain):
             self.print_message("index is already trained", 1)
             return
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
-        x = x.contiguous()
+        x = self._prepare(x)
         self.print_message("start training VQ codec...", 1)
         self.vq_codec.train(x)
         self.print_message("start training PQ codec...", 1)
@@ -127,12 +112,7 @@ class IVFPQRIndex(IVFPQIndex):
 
     def encode(self, x):
         """x [d_vector, n] f32 -> codes [n_subvectors + n_subvectors_rerank, n] uint8"""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x)
-        return self._encode_normalised(x.contiguous())
+        return self._encode_normalised(self._prepare(x))
 
     def decode(self, x):
         """codes [n_subvectors + n_subvectors_rerank, n] uint8 -> [d_vector, n] f32"""
@@ -147,12 +127,7 @@ class IVFPQRIndex(IVFPQIndex):
     def add(self, x, ids=None, return_address=False):
         """x [d_vector, n] f32, optional ids [n] int64 (default arange + max_id + 1);
         returns ids (and the slot addresses if return_address)."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x)
-        x = x.contiguous()
+        x = self._prepare(x)
         assigned_cells = self.vq_codec.encode(x)
         # (the reference's `super(IVFPQIndex, self).add`, :217, names a class its file never imports)
         return super(IVFPQIndex, self).add(self._encode_normalised(x), cells=assigned_cells, ids=ids,
@@ -167,29 +142,22 @@ class IVFPQRIndex(IVFPQIndex):
         [, address int64 [n_query, k]]).  The list scan of IVFPQIndex returns k * rerank_factor candidates by
         the first code; they are re-ranked by -|q - (decode(c) + decode_r(c_r))|^2 (the dot product for
         "cosine"), or by the ADC value of the re-rank code alone when not use_residual."""
-        assert len(x.shape) == 2
-        assert x.shape[0] == self.d_vector
+        x = self._prepare(x)
         assert 0 < k <= 1024
         k1 = k * self.rerank_factor
         assert k1 <= 1024, f"k * rerank_factor = {k1} exceeds the list scan's limit of 1024 candidates"
         assert (self.vq_codec.is_trained and self.pq_codec.is_trained
                 and self.pq_rerank_codec.is_trained), "index is not trained"
         assert 1 <= self.n_probe <= self.n_cells
-        x = x.to(self.device)
-        if self.distance == "cosine":
-            x = util.normalize(x, dim=0)
-        n_query = x.shape[1]
-        out = []
-        for q0 in range(0, max(n_query, 1), self.max_query_batch):
-            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
-            topk_sims, cells, n_probe_list, extents = self._probe_with_extents(xb)
-            _, _, candidates = self.search_cells(x=xb, cells=cells, base_sims=topk_sims,
-                                                 n_probe_list=n_probe_list, k=k1, return_address=True,
-                                                 _extents=extents)
+
+        def per_batch(xb, sims, cells, n_probe_list, extents):
+            _, _, candidates = self.search_cells(x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k1,
+                                                 return_address=True, _extents=extents)
             v, a, i = self._rerank(self._storage, self.n_subvectors, self.pq_codec.codebook,
                                    self.pq_rerank_codec.codebook, xb, candidates, k,
                                    use_residual=self.use_residual, distance=self.distance,
                                    address2id=self._address2id)
-            out.append((v, i, a))
-        vals, ids, address = (out[0] if len(out) == 1 else (torch.cat(t, 0) for t in zip(*out)))
+            return v, i, a
+
+        vals, ids, address = self._search_batches(x, per_batch)
         return (vals, ids, address) if return_address else (vals, ids)

@@ -1,15 +1,63 @@
 """The coarse step of the IVF indexes (IVFPQIndex and its subclasses, IVFFlatIndex): the probed cells of a query batch.
 
-The host class provides `vq_codec` (a trained VQCodec), `n_probe`, `device`, the container's `_cell_start` /
-`_cell_size`, the switches `use_cublas` and `use_fused_probe`, `_use_smart_probing` / `_smart_probing_temperature`,
-and the kernel wrappers `_coarse_probe`, `_coarse_select`, `_topk`, `_smart_probing`.
+The host class is a CellContainer with `d_vector`, `distance` and the switch `use_cublas`; `_init_coarse` sets up the
+rest.  Besides the coarse step, the halves of `add` / `search` / `search_cells` that the IVF indexes share live here:
+the preparation of a [d_vector, n] input, the preamble of a list scan, the loop over query batches.
 """
 import torch
 
 from .. import metric, util
+from ..codec import VQCodec
+from ..fn import Topk
+from ..kernels import CoarseProbeHip, CoarseSelectHip, SmartProbingHip
 
 
 class CoarseProbeMixin:
+    def _init_coarse(self, n_cells, verbose):
+        """the coarse-step members; called where the index registers its sub-modules (`vq_codec` comes first in
+        every state_dict())"""
+        self.n_probe = 1
+        self._use_smart_probing = True
+        self._smart_probing_temperature = 30.0
+        self.use_fused_probe = True     # coarse sims + select + list extents + probe count: one call
+        # bounds what a batch allocates: the coarse step's [n_query, n_cells] matrix, IVFPQIndex's [m, nq, 256] LUT
+        # (m=64: 2 GiB per batch)
+        self.max_query_batch = 32768
+        self.vq_codec = VQCodec(n_clusters=n_cells, n_redo=1, max_iter=15, tol=1e-4,
+                                distance="euclidean", init_mode="random", verbose=verbose)
+        self._topk = Topk()
+        self._smart_probing = SmartProbingHip()
+        self._coarse_select = CoarseSelectHip()
+        self._coarse_probe = CoarseProbeHip()
+
+    def _prepare(self, x):
+        """a [d_vector, n] input as the kernels take it: on the index's device, normalised for "cosine", contiguous"""
+        assert len(x.shape) == 2
+        assert x.shape[0] == self.d_vector
+        x = x.to(self.device)
+        if self.distance == "cosine":
+            x = util.normalize(x)
+        return x.contiguous()
+
+    def _scan_preamble(self, x, cells, n_probe_list, extents):
+        """what every search_cells hands its list scan: (n_probe_list, cell_start, cell_size, slots_hint, is_empty);
+        `extents`: the cells' (start, size) when the coarse step already gathered them"""
+        if n_probe_list is None:
+            n_probe_list = torch.full((x.shape[1],), cells.shape[1], device=self.device, dtype=torch.long)
+        cell_start, cell_size = (self._cell_start[cells], self._cell_size[cells]) if extents is None else extents
+        # expected slots per query (host-side estimate, no sync): bounds the per-query split
+        slots_hint = cells.shape[1] * self.capacity // max(self.n_cells, 1)
+        return n_probe_list, cell_start, cell_size, slots_hint, self._is_empty if self._has_holes else None
+
+    def _search_batches(self, x, per_batch):
+        """search() over batches of `max_query_batch` prepared queries: per_batch(xb, sims, cells, n_probe_list,
+        extents) returns a tuple of [n_batch, k] tensors; the concatenations (a single batch's own tensors)"""
+        out = []
+        for q0 in range(0, max(x.shape[1], 1), self.max_query_batch):
+            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
+            out.append(per_batch(xb, *self._probe_with_extents(xb)))
+        return out[0] if len(out) == 1 else tuple(torch.cat(t, 0) for t in zip(*out))
+
     @property
     def use_smart_probing(self):
         return self._use_smart_probing

@@ -1,0 +1,475 @@
+"""The list scans and what feeds them: IVFPQ top-k (plain, fused LUT, residual), the LUT and residual tables, the
+IVFPQR re-rank, the IVFFlat scan."""
+import torch
+
+from .._lib import check, load, ptr, require_gpu, stream_ptr
+from ._common import alloc_pair, alloc_topk, call, metric_code, topk_result, workgroups_per_query
+
+# n_subvectors with an instantiated scan-layout kernel (= TPQ_PACKED_M_LIST in csrc/scan_device.h)
+PACKED_M = (4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 56, 64, 96, 120, 128)
+
+
+def packed_chunk_width(m):
+    return 16 if m % 16 == 0 else (8 if m % 8 == 0 else 4)
+
+
+class IVFPQTopkHip:
+    """IVF list scan + top-k.  Mirrors IVFPQTopkCuda (kernels/IVFPQTopkCuda.py:9-142);
+    ``tpb``/``stack_capacity``/``sm_size`` are accepted for signature compatibility and
+    ignored (the workgroup shape is fixed by the gfx950 kernel)."""
+
+    def __init__(self, m=8, k=256, tpb=256, n_cs=4, stack_capacity=2, sm_size=None):
+        assert k == 256  # 8-bit PQ only (IVFPQTopkCuda.py:21)
+        assert n_cs == 4
+        assert m % n_cs == 0
+        self.m = m
+        self.k = k
+        self.tpb = tpb
+        self.n_cs = n_cs
+        self.n_cus = None
+        # measurement hook (bench.py): when a list, every call appends a (start, stop) pair of
+        # timing events recorded on the launch stream around the scan kernel(s)
+        self.record_events = None
+        self.last_n_split = None
+        # tickets of the one-launch finish of split queries (tpq_ivfpq_*_tickets): caller-owned int32 [n_query],
+        # zero between calls.  One buffer per (device, stream) -- calls that share a buffer must be ordered;
+        # `ticket_buffer` overrides it (GraphedSearch hands in the buffer its graph owns).
+        self.ticket_buffer = None
+        self._ticket_cache = {}
+        self.keep_workspace = False   # diagnostics: keep the last call's workspace in `last_workspace`
+        self.last_workspace = None
+        self.last_call = None         # diagnostics: the arguments of the last topk / topk_fused call (`last_route()`)
+
+    def _tickets(self, n_query, n_split, device):
+        """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
+        inside a stream capture only a buffer handed in through `ticket_buffer` may be used: a fresh one
+        would be zeroed by a captured memset on every replay)"""
+        if n_split <= 1:
+            return None
+        if self.ticket_buffer is not None:
+            t = self.ticket_buffer
+            assert t.dtype == torch.int32 and t.numel() >= n_query and t.device == torch.device(device)
+            return t
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        dev = torch.device(device)
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        t = self._ticket_cache.get(key)
+        if t is None or t.numel() < n_query:
+            if len(self._ticket_cache) >= 64:
+                self._ticket_cache.clear()
+            t = torch.zeros(max(n_query, 1024), device=dev, dtype=torch.int32)
+            self._ticket_cache[key] = t
+        return t
+
+    def _drop_tickets(self, device):
+        """after a failed call the tickets may be left non-zero: never reuse them"""
+        dev = torch.device(device)
+        self._ticket_cache.pop((dev.index, torch.cuda.current_stream(dev).cuda_stream), None)
+
+    def last_redone(self, n_query):
+        """diagnostics (synchronises; needs keep_workspace): queries of the last packed scan that were redone exactly --
+        by the one-launch finisher's own redo branch (ws_delta[q] == 1) or, on the routes that end with the flag-gated
+        exact kernel (the large-batch routes, the pools, the three-launch path: ws_delta holds a selection band there),
+        by that kernel, which leaves kRedoneMark = -1 (csrc/scan_args.h).  None on the reference-layout route, which
+        writes no ws_delta."""
+        ws = self.last_workspace
+        route = self.last_route()
+        if ws is None or route in (None, "reference_layout", "rejected"):
+            return None
+        off = (n_query * 4 + 255) // 256 * 256
+        d = ws[off:off + 4 * n_query].view(torch.float32)
+        return int((d == (1.0 if route == "one_launch_finish" else -1.0)).sum().item())
+
+    ROUTES = {0: "reference_layout", 1: "one_launch_finish", 2: "sorted_lists", 3: "pools", 8: "dump_f32",
+              16: "dump_sel16", 17: "dump_sel16_w8", -1: "rejected"}
+
+    def route(self, n_query, k, n_split=1, ds=0, n_probe=1, slots_hint=None, has_lut=True, packed=True,
+              tickets=None, residual=False):
+        """diagnostics: the kernels a call with these arguments runs (tpq_ivfpq_scan_route: the library's own rule,
+        nothing is launched) -- one of ROUTES' names.  `tickets` defaults to what topk / topk_fused pass: the cached
+        buffer of a split query outside a stream capture."""
+        if tickets is None:
+            tickets = n_split > 1
+        code = load().tpq_ivfpq_scan_route(int(n_query), int(k), int(n_split), self.m, int(ds), int(n_probe),
+                                            int(slots_hint or 0), int(bool(has_lut)),
+                                            int(bool(packed) and self.m in PACKED_M), int(bool(tickets)),
+                                            int(bool(residual)))
+        return self.ROUTES.get(code, str(code))
+
+    def last_route(self):
+        """diagnostics: route(...) of the last topk / topk_fused call"""
+        return None if self.last_call is None else self.route(**self.last_call)
+
+    def _n_split(self, n_query, device, slots_hint=None):
+        """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
+        if self.n_cus is None:
+            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+        # four 4-wave workgroups per CU for short codes (m <= 32), two 8-wave ones while the LUT is
+        # <= 64 KiB, one 16-wave workgroup above (csrc/scan_packed_kernel.h packed_waves)
+        per_cu, waves = (4, 4) if self.m <= 32 else (2, 8) if self.m <= 64 else (1, 16)
+        return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
+
+    def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed, **route):
+        """What topk / topk_fused / topk_residual_packed share once their arguments are checked: the outputs, the
+        split, the diagnostics, the workspace and the call of `name` -- its own `inputs`, then the arguments every
+        scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint)."""
+        n_data, device = data.shape[1], data.device
+        n_query, n_probe = cell_start.shape
+        values, address, ids = alloc_topk(n_query, k, device, address2id)
+        if n_query == 0:
+            return topk_result(values, address, ids)
+        lib = load()
+        if n_split is None:
+            n_split = self._n_split(n_query, device, slots_hint)
+        self.last_n_split = n_split  # diagnostics / tests: workgroups per query of the last call
+        self.last_call = dict(n_query=n_query, k=k, n_split=n_split, n_probe=n_probe, slots_hint=slots_hint,
+                              packed=packed is not None, **route)
+        ws_bytes = lib.tpq_ivfpq_scan_workspace_bytes(n_query, k, n_split, self.m)
+        ws = torch.empty(max(ws_bytes, 1), device=device, dtype=torch.uint8)
+        ev = None
+        if self.record_events is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record(torch.cuda.current_stream(device))
+        with torch.cuda.device(device):
+            tail = ()
+            if ticketed:
+                tickets = self._tickets(n_query, n_split, device) if packed is not None else None
+                tail = (ptr(tickets), int(slots_hint or 0))
+            rc = getattr(lib, name)(*inputs, ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data, n_query,
+                                    n_probe, self.m, k, n_split, ptr(ws), ws_bytes, *tail, stream_ptr(device))
+            if rc != 0 and ticketed:
+                self._drop_tickets(device)
+            check(rc, name)
+        if self.keep_workspace:
+            self.last_workspace = ws
+        if ev is not None:
+            ev[1].record(torch.cuda.current_stream(device))
+            self.record_events.append(ev)
+        return topk_result(values, address, ids)
+
+    def topk(self, data, precomputed, is_empty, cell_start, cell_size, n_probe_list,
+             n_candidates=None, packed=None, address2id=None, n_split=None, slots_hint=None):
+        """
+          data: [m // 4, n_data, 4] uint8           (CellContainer._storage)
+          precomputed: [m, n_query, 256] float32    (PQCodec.precompute_adc)
+          is_empty: [n_data] uint8, or None when no slot inside a cell is a tombstone
+          cell_start / cell_size: [n_query, max_n_probe] int64
+          n_probe_list: [n_query] int64
+          n_candidates: k of the top-k (<= 1024)
+          packed: optional scan-layout copy of `data` (enables the bank-conflict-free kernel)
+          address2id: optional [n_data] int64; when given a third tensor (ids) is returned
+        returns (values [n_query, k] descending, address [n_query, k][, ids])
+        """
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert precomputed.shape == (self.m, n_query, self.k)
+        assert data.shape[0] == self.m // self.n_cs
+        assert data.shape[2] == self.n_cs
+        assert cell_size.shape[1] == n_probe
+        assert data.dtype == torch.uint8
+        assert precomputed.dtype == torch.float32
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,)
+        assert n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape[0] == n_data
+            assert is_empty.dtype == torch.uint8
+        if n_candidates is None:
+            n_candidates = self.tpb
+        assert 0 < n_candidates <= 1024
+        require_gpu(data, precomputed, is_empty, cell_start, cell_size, n_probe_list, packed,
+                    address2id)
+        inputs = (ptr(data), ptr(precomputed), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+        if packed is not None and self.m in PACKED_M:
+            return self._scan("tpq_ivfpq_scan_topk_packed_tickets", (ptr(packed), *inputs), data, cell_start,
+                              address2id, n_candidates, n_split, slots_hint, packed, True, ds=0, has_lut=True)
+        return self._scan("tpq_ivfpq_scan_topk", inputs, data, cell_start, address2id, n_candidates, n_split,
+                          slots_hint, packed, False, ds=0, has_lut=True)
+
+    def topk_fused(self, data, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                   n_candidates, distance="euclidean", packed=None, address2id=None, n_split=None,
+                   slots_hint=None):
+        """precompute_adc + topk in one pass: the LUT is built inside the scan workgroups
+        (query [d, n_query] f32, codebook [m, ds, 256] f32); results identical to
+        topk(precomputed=AdcLutHip()(query, codebook))."""
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        m, ds, kk = codebook.shape
+        assert m == self.m and kk == self.k
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        assert data.shape == (self.m // self.n_cs, n_data, self.n_cs) and data.dtype == torch.uint8
+        assert cell_size.shape == (n_query, n_probe)
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        assert 0 < n_candidates <= 1024
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        require_gpu(data, query, codebook, is_empty, cell_start, cell_size, n_probe_list, packed,
+                    address2id)
+        inputs = (ptr(packed), ptr(data), ptr(query), ptr(codebook), ds, metric_code(distance), ptr(is_empty),
+                  ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+        return self._scan("tpq_ivfpq_search_fused_tickets", inputs, data, cell_start, address2id, n_candidates,
+                          n_split, slots_hint, packed, True, ds=ds, has_lut=False)
+
+    # ---- residual PQ (pq_use_residual=True) ------------------------------------------------------
+    def _residual(self, data, part1, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
+                  n_probe_list, n_candidates, address2id):
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert data.shape == (self.m // self.n_cs, n_data, self.n_cs)
+        assert cell_size.shape == (n_query, n_probe)
+        assert base_sims.shape == (n_query, n_probe)
+        assert data.dtype == torch.uint8
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert base_sims.dtype == torch.float32
+        assert n_probe_list.shape == (n_query,)
+        assert n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_data,) and is_empty.dtype == torch.uint8
+        if n_candidates is None:
+            n_candidates = self.tpb
+        assert 0 < n_candidates <= 1024
+        # logical [q][j][c] / [cell][j][c] / [q][p][j][c] order, whatever view the caller built
+        part1 = None if part1 is None else part1.contiguous()
+        part2 = None if part2 is None else part2.contiguous()
+        full = None if full is None else full.contiguous()
+        cells = None if cells is None else cells.contiguous()
+        base_sims = base_sims.contiguous()
+        require_gpu(data, part1, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
+                    n_probe_list, address2id)
+        k = n_candidates
+        values, address, ids = alloc_topk(n_query, k, data.device, address2id)
+        if n_query:
+            call("tpq_ivfpq_scan_topk_residual", data.device,
+                 ptr(data), ptr(part1), ptr(part2), ptr(full), ptr(cells), ptr(base_sims),
+                 ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(values),
+                 ptr(address), ptr(address2id), ptr(ids), n_data, n_query, n_probe, self.m, k)
+        return topk_result(values, address, ids)
+
+    def topk_residual_packed(self, data, packed, part2, slot_term, cell_bound, cells, base_sims,
+                             is_empty, cell_start, cell_size, n_probe_list, n_candidates,
+                             part1=None, query=None, codebook=None, address2id=None, n_split=None,
+                             slots_hint=None):
+        """Residual scan on the scan layout (tpq_ivfpq_scan_topk_residual_packed): results equal
+        topk_residual_precomputed bit for bit.  part1 [n_query, m, 256] or (query [d, n_query],
+        codebook [m, ds, 256]) from which the workgroup builds it; part2 [n_cells, m, 256]
+        contiguous; slot_term / cell_bound from ResidualSlotTermsHip."""
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert self.m in PACKED_M and packed is not None
+        assert data.shape == (self.m // self.n_cs, n_data, self.n_cs) and data.dtype == torch.uint8
+        assert part2.shape[1:] == (self.m, self.k) and part2.dtype == torch.float32
+        assert part2.is_contiguous()
+        assert slot_term.shape == (n_data,) and slot_term.dtype == torch.float32
+        assert cell_bound.shape == (part2.shape[0],) and cell_bound.dtype == torch.float32
+        assert cells.shape == cell_start.shape == cell_size.shape == base_sims.shape
+        assert cells.dtype == cell_start.dtype == cell_size.dtype == torch.int64
+        assert base_sims.dtype == torch.float32
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        assert 0 < n_candidates <= 1024
+        ds = 0
+        if part1 is not None:
+            assert part1.shape == (n_query, self.m, self.k) and part1.dtype == torch.float32
+            part1 = part1.contiguous()
+        else:
+            assert query is not None and codebook is not None
+            ds = codebook.shape[1]
+            assert codebook.shape == (self.m, ds, self.k) and query.shape == (self.m * ds, n_query)
+            assert query.dtype == codebook.dtype == torch.float32
+            query = query.contiguous()
+            codebook = codebook.contiguous()
+        cells = cells.contiguous()
+        base_sims = base_sims.contiguous()
+        require_gpu(data, packed, part1, query, codebook, part2, slot_term, cell_bound, cells,
+                    base_sims, is_empty, cell_start, cell_size, n_probe_list, address2id)
+        inputs = (ptr(packed), ptr(data), ptr(part1), ptr(query), ptr(codebook), ds, ptr(part2), ptr(slot_term),
+                  ptr(cell_bound), ptr(cells), ptr(base_sims), ptr(is_empty), ptr(cell_start), ptr(cell_size),
+                  ptr(n_probe_list))
+        return self._scan("tpq_ivfpq_scan_topk_residual_packed", inputs, data, cell_start, address2id,
+                          n_candidates, n_split, slots_hint, packed, False, ds=ds, has_lut=part1 is not None,
+                          residual=True)
+
+    def topk_residual(self, data, precomputed, base_sims, is_empty, cell_start, cell_size,
+                      n_probe_list, n_candidates=None, address2id=None):
+        """precomputed: [n_query, max_n_probe, m, 256] f32 -- one LUT per (query, probe)
+        (kernels/IVFPQTopkCuda.py:144-210)."""
+        n_query, n_probe = cell_start.shape
+        assert precomputed.shape == (n_query, n_probe, self.m, self.k)
+        assert precomputed.dtype == torch.float32
+        return self._residual(data, None, None, precomputed, None, base_sims, is_empty, cell_start,
+                              cell_size, n_probe_list, n_candidates, address2id)
+
+    def topk_residual_precomputed(self, data, part1, part2, cells, base_sims, is_empty, cell_start,
+                                  cell_size, n_probe_list, n_candidates=None, address2id=None):
+        """part1 [n_query, m, 256], part2 [n_cells, m, 256] f32, cells [n_query, max_n_probe] int64
+        (kernels/IVFPQTopkCuda.py:212-283)."""
+        n_query = cell_start.shape[0]
+        assert part1.shape == (n_query, self.m, self.k) and part2.shape[1:] == (self.m, self.k)
+        assert part1.dtype == part2.dtype == torch.float32
+        assert cells.shape == cell_start.shape and cells.dtype == torch.int64
+        return self._residual(data, part1, part2, None, cells, base_sims, is_empty, cell_start,
+                              cell_size, n_probe_list, n_candidates, address2id)
+
+
+class ResidualSlotTermsHip:
+    """Per-slot / per-cell constants of the packed residual scan (tpq_ivfpq_residual_slot_terms):
+    slot_term [n_data] f32 = sum_j part2[cell(s), j, code_j(s)], cell_bound [n_cells] f32."""
+
+    def __call__(self, data, part2, cell_start, cell_size):
+        n_cells, m, kk = part2.shape
+        n_data = data.shape[1]
+        assert kk == 256 and data.shape == (m // 4, n_data, 4) and data.dtype == torch.uint8
+        assert part2.dtype == torch.float32 and part2.is_contiguous()
+        assert cell_start.shape == cell_size.shape == (n_cells,)
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        require_gpu(data, part2, cell_start, cell_size)
+        slot_term = torch.empty(n_data, device=data.device, dtype=torch.float32)
+        cell_bound = torch.empty(n_cells, device=data.device, dtype=torch.float32)
+        call("tpq_ivfpq_residual_slot_terms", data.device, ptr(data), ptr(part2), ptr(cell_start), ptr(cell_size),
+             ptr(slot_term), ptr(cell_bound), n_data, n_cells, m)
+        return slot_term, cell_bound
+
+
+class ResidualPart1Hip:
+    """part1[q, j, c] = 2 * q_j . r_jc (index/IVFPQIndex.py:366-379), [n_query, m, 256] f32."""
+
+    def __call__(self, query, codebook):
+        m, ds, k = codebook.shape
+        assert k == 256 and query.shape[0] == m * ds
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        require_gpu(query, codebook)
+        nq = query.shape[1]
+        out = torch.empty(nq, m, 256, device=query.device, dtype=torch.float32)
+        call("tpq_residual_part1", query.device, ptr(query), ptr(codebook), ptr(out), m, ds, nq)
+        return out
+
+
+class IVFPQTop1Hip(IVFPQTopkHip):
+    """k = 1 variant (kernels/IVFPQTop1Cuda.py:86-140): same kernel family, list of one."""
+
+    def topk(self, *args, n_candidates=1, **kwargs):
+        return super().topk(*args, n_candidates=n_candidates, **kwargs)
+
+
+class AdcLutHip:
+    """PQCodec.precompute_adc on the fp32 matrix cores (codec/PQCodec.py:62-75)."""
+
+    def __call__(self, query, codebook, distance="euclidean"):
+        """query [d, n_query] f32, codebook [m, ds, 256] f32 -> [m, n_query, 256] f32"""
+        m, ds, k = codebook.shape
+        assert k == 256
+        assert query.shape[0] == m * ds
+        assert query.dtype == codebook.dtype == torch.float32
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        require_gpu(query, codebook)
+        nq = query.shape[1]
+        lut = torch.empty(m, nq, 256, device=query.device, dtype=torch.float32)
+        if nq == 0:   # (an empty tensor has no address to hand to the library)
+            return lut
+        call("tpq_adc_lut", query.device, ptr(query), ptr(codebook), ptr(lut), m, ds, nq, metric_code(distance))
+        return lut
+
+
+class IVFPQRerankHip:
+    """The re-rank step of IVFPQRIndex (tpq_ivfpqr_rerank; the second half of the legacy IVFPQR.topk,
+    legacy/IVFPQR.py:408-473): the candidates of the list scan re-valued from both codes of their slot,
+    the best k kept."""
+
+    def __call__(self, storage, n_subvectors, codebook, codebook_r, query, cand_address, k, use_residual=True,
+                 distance="euclidean", address2id=None):
+        """
+          storage: [(m + m_r) // 4, capacity, 4] uint8, first the m first-stage rows, then the m_r re-rank rows
+          codebook [m, ds, 256] / codebook_r [m_r, ds_r, 256] float32 (codebook may be None when not use_residual)
+          query: [d, n_query] float32 (normalised by the caller for "cosine")
+          cand_address: [n_query, k1] int64, -1 = no candidate
+          address2id: optional [capacity] int64; when given a third tensor (ids) is returned
+        returns (values [n_query, k] descending, address [n_query, k][, ids]); unfilled = (-inf, -1, -1)
+        """
+        m = n_subvectors
+        g, capacity, cs = storage.shape
+        m_r, ds_r, kk = codebook_r.shape
+        d, n_query = query.shape
+        k1 = cand_address.shape[1]
+        assert cs == 4 and storage.dtype == torch.uint8 and g * 4 == m + m_r
+        assert kk == 256 and d == m_r * ds_r and d % m == 0
+        assert cand_address.shape == (n_query, k1) and cand_address.dtype == torch.int64
+        assert query.dtype == codebook_r.dtype == torch.float32
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= k1 <= 1024
+        if use_residual:
+            assert codebook.shape == (m, d // m, 256) and codebook.dtype == torch.float32
+            codebook = codebook.contiguous()
+        else:
+            codebook = None
+        if address2id is not None:
+            assert address2id.shape == (capacity,) and address2id.dtype == torch.int64
+        query = query.contiguous()
+        codebook_r = codebook_r.contiguous()
+        cand_address = cand_address.contiguous()
+        require_gpu(storage, codebook, codebook_r, query, cand_address, address2id)
+        values, address, ids = alloc_topk(n_query, k, storage.device, address2id)
+        if n_query:
+            call("tpq_ivfpqr_rerank", storage.device,
+                 ptr(storage), capacity, m, m_r, ptr(codebook), ptr(codebook_r), ptr(query), d, n_query,
+                 ptr(cand_address), k1, k, int(bool(use_residual)), metric_code(distance), ptr(address2id),
+                 ptr(values), ptr(address), ptr(ids))
+        return topk_result(values, address, ids)
+
+
+class IVFFlatTopkHip:
+    """The list scan of IVFFlatIndex (tpq_ivfflat_scan_topk, csrc/scan_flat.hip): the probed cells hold the vectors
+    themselves; value and order are defined in include/torchpq_amd.h."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    def _n_split(self, n_query, device, slots_hint=None):
+        """Workgroups per query: two 8-wave workgroups per CU, see workgroups_per_query."""
+        if self.n_cus is None:
+            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+        return workgroups_per_query(n_query, self.n_cus, 2, 8, slots_hint)
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          vectors: [d, n_slots] float32 (or [d, n_slots, 1]: CellContainer._storage.view(torch.float32))
+          query: [d, n_query] float32 (normalised by the caller for "cosine")
+          cell_start / cell_size: [n_query, max_n_probe] int64; n_probe_list: [n_query] int64
+          is_empty: [n_slots] uint8, or None when no slot inside a cell is a tombstone
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        if vectors.dim() == 3:
+            assert vectors.shape[2] == 1
+            vectors = vectors[:, :, 0]
+        d, n_slots = vectors.shape
+        n_query, n_probe = cell_start.shape
+        assert query.shape == (d, n_query)
+        assert vectors.dtype == query.dtype == torch.float32
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        query = query.contiguous()
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list)
+        device = vectors.device
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        if n_split is None:
+            n_split = self._n_split(n_query, device, slots_hint)
+        self.last_n_split = n_split
+        ws_bytes = load().tpq_ivfflat_scan_workspace_bytes(n_query, k, n_split)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+        call("tpq_ivfflat_scan_topk", device,
+             ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+             ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
+             ws_bytes)
+        return values, address
