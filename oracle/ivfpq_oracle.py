@@ -464,6 +464,73 @@ def get_ioa(cells):
     return ioa
 
 
+def get_address_by_id(address2id, ids):
+    """id -> the SMALLEST address holding it, -1 when no address does (or the id is negative: a
+    negative entry of ``address2id`` marks a free address, never an id).  The contract of
+    BaseContainer.get_address_by_id (container/BaseContainer.py:67-98); an id stored more than once
+    resolves to its first copy in address order, as the reference's CPU form does (:67-77)."""
+    first = {}
+    for a, v in enumerate(np.asarray(address2id, dtype=np.int64).tolist()):
+        if v >= 0 and v not in first:
+            first[v] = a
+    ids = np.asarray(ids, dtype=np.int64)
+    out = [first.get(i, -1) if i >= 0 else -1 for i in ids.reshape(-1).tolist()]
+    return np.array(out, dtype=np.int64).reshape(ids.shape)
+
+
+def grow_cells(storage, address2id, is_empty, old_start, old_cap, new_start, new_cap, new_slots):
+    """Re-lay the inverted lists out for per-cell capacities ``new_cap`` (>= ``old_cap``): cell c's
+    slots move from [old_start[c], old_start[c] + old_cap[c]) to new_start[c] onwards, its new tail
+    is free (code 0, id -1, is_empty 1).  What a round of CellContainer.expand
+    (container/CellContainer.py:249-311) leaves behind, as one copy per cell.  Slots of the new
+    arrays that belong to no cell keep code 0, id -1, is_empty 1.
+    Returns (storage [m/4, new_slots, 4], address2id [new_slots], is_empty [new_slots])."""
+    g, _, cs = storage.shape
+    out_storage = np.zeros((g, new_slots, cs), np.uint8)
+    out_a2i = np.full(new_slots, -1, np.int64)
+    out_empty = np.ones(new_slots, np.uint8)
+    for c in range(len(old_start)):
+        os_, oc, ns, nc = int(old_start[c]), int(old_cap[c]), int(new_start[c]), int(new_cap[c])
+        assert 0 <= oc <= nc and ns + nc <= new_slots
+        out_storage[:, ns:ns + oc] = storage[:, os_:os_ + oc]
+        out_a2i[ns:ns + oc] = address2id[os_:os_ + oc]
+        out_empty[ns:ns + oc] = is_empty[os_:os_ + oc]
+    return out_storage, out_a2i, out_empty
+
+
+def scan_layout_blocks(m):
+    """The scan layout's blocks of sub-quantizers as (base, size): greedy powers of two
+    64, ..., 64, 32, 16, 8, 4 (csrc/scan_layout.h header comment)."""
+    assert m >= 4 and m % 4 == 0
+    blocks, b = [], 0
+    while m - b >= 64:
+        blocks.append((b, 64))
+        b += 64
+    for size in (32, 16, 8, 4):
+        if m - b >= size:
+            blocks.append((b, size))
+            b += size
+    assert b == m
+    return blocks
+
+
+def pack_codes(storage):
+    """``_storage`` [m/4, n_slots, 4] -> the scan layout [m/W][n_slots][W], W = 16 / 8 / 4 (the
+    widest that divides m), as the header comment of csrc/scan_layout.h states it: inside the block
+    (base b, size B) byte position p of the slot with address s holds the code of sub-quantizer
+    b + ((p - b) xor (s mod B))."""
+    g, n_slots, cs = storage.shape
+    m = g * cs
+    w = 16 if m % 16 == 0 else (8 if m % 8 == 0 else 4)
+    codes = storage.transpose(0, 2, 1).reshape(m, n_slots)  # [sub-quantizer, slot]
+    s = np.arange(n_slots)
+    at = np.empty((m, n_slots), np.uint8)                   # [position, slot]
+    for b, size in scan_layout_blocks(m):
+        for p in range(b, b + size):
+            at[p] = codes[b + ((p - b) ^ (s % size)), s]
+    return np.ascontiguousarray(at.reshape(m // w, w, n_slots).transpose(0, 2, 1))
+
+
 def get_write_address(is_empty, cell_start, cell_capacity, cells, ioa):
     """The ``ioa``-th empty slot inside the cell's capacity range, -1 if none.
     Restates get_write_address_v2.cu:9-41."""

@@ -62,22 +62,28 @@ class BaseContainer(CustomModule, ABC):
         """_id2address [max_id + 1]: address of every stored id, -1 elsewhere (:100-110).
         The reference's dense table needs max_id + 1 entries whatever the number of items (its own
         tests draw ids below 2**62, tests/CellContainerTestCase.py:60-66: 32 EiB); ids much sparser
-        than the capacity are served from a sorted (id, address) list by binary search instead."""
+        than the capacity are served from a sorted (id, address) list by binary search instead.
+        An id stored at several addresses maps to the SMALLEST of them in both forms, as in the
+        linear search: the list is sorted stably over ascending addresses (searchsorted then lands
+        on an id's first copy), the table is filled by a minimum, not by a plain scatter (whose
+        winner among repeated indices is unspecified)."""
         a2i = self._address2id
-        adr = torch.nonzero(a2i >= 0)[:, 0]
+        adr = torch.nonzero(a2i >= 0)[:, 0]  # ascending
         del self._id2address
         if self.max_id + 1 > 8 * self.capacity + (1 << 20):
-            ids, order = torch.sort(a2i[adr])
+            ids, order = torch.sort(a2i[adr], stable=True)
             self.register_buffer("_id2address", None)
             self._sparse_id_map = (ids, adr[order])
             return
         id2a = torch.full((self.max_id + 1,), -1, device=self.device, dtype=torch.long)
-        id2a[a2i[adr]] = adr
+        id2a.scatter_reduce_(0, a2i[adr], adr, "amin", include_self=False)
         self.register_buffer("_id2address", id2a)
 
     def get_address_by_id(self, ids):
-        """ids int64 [n] -> addresses, -1 for unknown ids (:79-98).  The inverse table is rebuilt
-        after every add/remove (the reference keeps serving a stale one)."""
+        """ids int64 (any shape) -> addresses, -1 for unknown ids (:79-98).  An id stored more than
+        once resolves to the smallest address holding it, whichever of the three paths serves the
+        call (linear search, dense table, sorted list).  The inverse table is rebuilt after every
+        add/remove (the reference keeps serving a stale one)."""
         assert util.check_dtype(ids, torch.int64)
         ids = ids.to(self.device)
         if not self.use_inverse_id_mapping:
