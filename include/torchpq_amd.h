@@ -543,6 +543,49 @@ int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_
                           float* out_vals, int64_t* out_addr, int64_t n_slots, int d, int nq, int max_nprobe, int k,
                           int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * IVFFlatIndex range search: every stored vector of the probed cells whose value reaches a threshold (no
+ * reference counterpart).  vectors, query, is_empty, cell_start, cell_size, n_probe_list, n_slots, d, nq,
+ * max_nprobe, metric and n_split are those of tpq_ivfflat_scan_topk.
+ *
+ * Value      of a slot: exactly the value tpq_ivfflat_scan_topk defines (acc = 0.f, i ascending,
+ *            acc = acc - t*t with t = q_i - x_i, or acc = acc + q_i*x_i; one fp32 operation per step, no fma).
+ * Candidates of a query: those of tpq_ivfflat_scan_topk -- its first n_probe_list[q] cells (clamped to
+ *            [0, max_nprobe]), a probe whose start equals the previous probe's start skipped, the slots inside
+ *            [start, start + size) and inside the storage that are not tombstoned.
+ * Hit        a candidate with value >= threshold[q] (threshold f32 [nq]).  A NaN value is never a hit, a NaN
+ *            threshold gives no hits, -inf gives every candidate whose value is not NaN.
+ * Order      scan order: probe rank ascending, then address ascending; a slot of two overlapping cells appears
+ *            twice, as it does in the top-k scan.  The order does not depend on n_split.
+ * Output     lims i64 [nq + 1], lims[0] = 0: the hits of query q are out_vals[lims[q] : lims[q+1]] (f32) and
+ *            out_addr[lims[q] : lims[q+1]] (i64).
+ * A query with a NaN or +-Inf component returns what this definition gives (usually nothing) and touches no
+ * other query's segment.
+ *
+ * Two passes, no global atomics, no sort, deterministic.  A query's tiles are cut into n_split parts as in the
+ * top-k scan, a part's tiles into eight contiguous chunks, one per wave: segment (q * n_split + part) * 8 + wave.
+ *   1. tpq_ivfflat_range_count writes the hits of every segment: wave_counts i32
+ *      [tpq_ivfflat_range_segments(nq, n_split)] (= nq * n_split * 8; 0 for nq <= 0 or n_split outside [1, 1024]).
+ *   2. THE CALLER turns the counts into exclusive prefix sums: wave_offsets i64 [segments + 1], wave_offsets[0] = 0,
+ *      the last entry the total number of hits, which sizes out_vals / out_addr; lims[q] = wave_offsets[q * n_split
+ *      * 8].  The library does not do this step and allocates nothing.
+ *   3. tpq_ivfflat_range_fill, with the inputs of the count pass, computes the values again (the same code, the
+ *      same bits) and stores segment s at wave_offsets[s] onwards.  A wave stores nothing at or beyond
+ *      wave_offsets[s + 1], whatever it finds: inputs that changed between the passes lose hits, they do not
+ *      become a store outside the segment.  A segment without hits is not scanned again.
+ * 1 <= n_split <= 1024; n_slots < 2^31 - 1, else TPQ_ERR_UNSUPPORTED; any d >= 1.  nq == 0 is TPQ_OK.
+ * ------------------------------------------------------------------------- */
+size_t tpq_ivfflat_range_segments(int nq, int n_split);
+int tpq_ivfflat_range_count(const float* vectors, const float* query, const uint8_t* is_empty,
+                            const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                            const float* threshold, int32_t* wave_counts, int64_t n_slots, int d, int nq,
+                            int max_nprobe, int metric, int n_split, tpq_stream_t stream);
+int tpq_ivfflat_range_fill(const float* vectors, const float* query, const uint8_t* is_empty,
+                           const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                           const float* threshold, const int64_t* wave_offsets, float* out_vals, int64_t* out_addr,
+                           int64_t n_slots, int d, int nq, int max_nprobe, int metric, int n_split,
+                           tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

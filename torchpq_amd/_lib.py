@@ -95,6 +95,10 @@ SIGNATURES = {
     "tpq_ivfflat_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_ivfflat_scan_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz,
                                    _vp]),
+    "tpq_ivfflat_range_segments": (_sz, [_i, _i]),
+    "tpq_ivfflat_range_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "tpq_ivfflat_range_fill": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i,
+                                    _vp]),
     "tpq_ubench_stream_read": (_i, [_vp, _sz, _vp, _i, _vp]),
     "tpq_ubench_stream_read_ex": (_i, [_vp, _sz, _vp, _i, _i, _i, _sz, _i, _vp]),
     "tpq_ubench_rows_read": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp]),

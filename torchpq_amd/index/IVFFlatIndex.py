@@ -11,7 +11,7 @@ The coarse step is IVFPQIndex's (index/_coarse.py).
 import torch
 
 from ..container import CellContainer
-from ..kernels import IVFFlatTopkHip
+from ..kernels import IVFFlatRangeHip, IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
 
 
@@ -32,6 +32,7 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         self.use_cublas = True
         self._init_coarse(n_cells, verbose)
         self._flat_topk = IVFFlatTopkHip()
+        self._flat_range = IVFFlatRangeHip()
         self.to(device)
 
     def _after_load_state_dict(self):
@@ -115,3 +116,60 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
             x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=True,
             _extents=extents))
         return (vals, ids, address) if return_address else (vals, ids)
+
+    # ---- range search ----------------------------------------------------------------------------------
+    def range_search_cells(self, x, cells, threshold, n_probe_list=None, return_address=False, _extents=None):
+        """Every live vector of the given cells [n_query, n_probe] whose value is >= `threshold` (a float, or f32
+        [n_query]); (lims, values, ids[, address]) in scan order, see range_search.  (`_extents` as in search_cells.)"""
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        lims, vals, address = self._flat_range(
+            self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, threshold,
+            is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
+        ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+
+    def range_search(self, x, threshold, return_address=False, sort=False):
+        """x [d_vector, n_query] f32, threshold a float or f32 [n_query] -> (lims int64 [n_query + 1], values f32
+        [total], ids int64 [total][, address]): the hits of query q are values[lims[q]:lims[q+1]] and
+        ids[lims[q]:lims[q+1]] -- every stored vector of the query's probed cells (`n_probe`, as in search) whose value
+        is >= threshold.  `threshold` is in the index's value space, the one search returns: -squared-L2 for
+        "euclidean" (all vectors within distance r: threshold = -r * r), the cosine similarity for "cosine".
+        Hits come in scan order (probe rank, then slot address); sort=True orders each query's hits by value
+        descending, equal values by address ascending.  Synchronises once per batch of `max_query_batch` queries:
+        the number of hits sizes the outputs."""
+        x = self._prepare(x)
+        assert self.vq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        n_query = x.shape[1]
+        if torch.is_tensor(threshold):
+            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+            threshold = threshold.to(self.device)
+        lims = [torch.zeros(1, device=self.device, dtype=torch.int64)]
+        vals, ids, address, total = [], [], [], 0
+        for q0 in range(0, n_query, self.max_query_batch):
+            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
+            thr = threshold[q0:q0 + self.max_query_batch] if torch.is_tensor(threshold) else threshold
+            _, cells, n_probe_list, extents = self._probe_with_extents(xb)
+            lb, vb, ib, ab = self.range_search_cells(xb, cells, thr, n_probe_list, return_address=True,
+                                                     _extents=extents)
+            lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
+            vals.append(vb)
+            ids.append(ib)
+            address.append(ab)
+            total += vb.numel()
+        lims = torch.cat(lims)
+        if vals:
+            vals, ids, address = torch.cat(vals), torch.cat(ids), torch.cat(address)
+        else:
+            vals = torch.empty(0, device=self.device, dtype=torch.float32)
+            ids = address = torch.empty(0, device=self.device, dtype=torch.int64)
+        if sort and total:
+            # three stable sorts, least significant key first: address, value (descending), query
+            order = torch.argsort(address, stable=True)
+            order = order[torch.argsort(vals[order], descending=True, stable=True)]
+            query_of = torch.repeat_interleave(torch.arange(n_query, device=self.device), lims.diff(),
+                                               output_size=total)
+            order = order[torch.argsort(query_of[order], stable=True)]
+            vals, ids, address = vals[order], ids[order], address[order]
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)

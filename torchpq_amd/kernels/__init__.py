@@ -12,12 +12,12 @@ from .coarse import (CoarseProbeHip, CoarseSelectHip, SmartProbingHip, Top1Selec
 from .container import (GetAddressByIdHip, GetCellByAddressHip, GetIdByAddressHip, GetIOAHip,
                         GetWriteAddressHip, GrowCellsHip, PackCodesHip, PQDecodeHip, ScatterCodesHip)
 from .kmeans import ComputeCentroidsHip, CoarseAssignHip, LloydStepHip, MaxSimHip, MaxSimSelectHip
-from .scan import (PACKED_M, AdcLutHip, IVFFlatTopkHip, IVFPQRerankHip, IVFPQTop1Hip, IVFPQTopkHip,
+from .scan import (PACKED_M, AdcLutHip, IVFFlatRangeHip, IVFFlatTopkHip, IVFPQRerankHip, IVFPQTop1Hip, IVFPQTopkHip,
                    ResidualPart1Hip, ResidualSlotTermsHip, packed_chunk_width)
 
 __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "CoarseAssignHip", "MaxSimSelectHip", "LloydStepHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "packed_chunk_width", "PACKED_M",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "packed_chunk_width", "PACKED_M",
 ]

@@ -1,5 +1,5 @@
 """The list scans and what feeds them: IVFPQ top-k (plain, fused LUT, residual), the LUT and residual tables, the
-IVFPQR re-rank, the IVFFlat scan."""
+IVFPQR re-rank, the IVFFlat scan and range search."""
 import torch
 
 from .._lib import check, load, ptr, require_gpu, stream_ptr
@@ -473,3 +473,69 @@ class IVFFlatTopkHip:
              ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
              ws_bytes)
         return values, address
+
+
+class IVFFlatRangeHip:
+    """Range search over the lists of IVFFlatIndex (tpq_ivfflat_range_count / tpq_ivfflat_range_fill,
+    csrc/scan_flat.hip): every candidate of IVFFlatTopkHip whose value is >= the query's threshold, in scan order;
+    the semantics are defined in include/torchpq_amd.h."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    _n_split = IVFFlatTopkHip._n_split
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, threshold, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          vectors, query, cell_start, cell_size, n_probe_list, is_empty: as IVFFlatTopkHip
+          threshold: a Python float, or [n_query] float32 -- one per query
+        returns (lims [n_query + 1] int64, values [total] float32, address [total] int64): the hits of query q are
+        values[lims[q]:lims[q+1]] / address[lims[q]:lims[q+1]], probe rank ascending, then address ascending.
+        Synchronises once: the number of hits sizes the outputs.
+        """
+        if vectors.dim() == 3:
+            assert vectors.shape[2] == 1
+            vectors = vectors[:, :, 0]
+        d, n_slots = vectors.shape
+        n_query, n_probe = cell_start.shape
+        assert query.shape == (d, n_query)
+        assert vectors.dtype == query.dtype == torch.float32
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        assert distance in ("euclidean", "cosine", "inner")
+        per_query = torch.is_tensor(threshold)
+        if per_query:
+            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+            threshold = threshold.contiguous()
+        query = query.contiguous()
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list, threshold if per_query else None)
+        device = vectors.device
+        if not per_query:
+            threshold = torch.full((n_query,), float(threshold), device=device, dtype=torch.float32)
+        if n_query == 0:
+            return (torch.zeros(1, device=device, dtype=torch.int64),
+                    torch.empty(0, device=device, dtype=torch.float32),
+                    torch.empty(0, device=device, dtype=torch.int64))
+        if n_split is None:
+            n_split = self._n_split(n_query, device, slots_hint)
+        self.last_n_split = n_split
+        n_seg = load().tpq_ivfflat_range_segments(n_query, n_split)
+        assert n_seg == n_query * n_split * 8, (n_query, n_split)
+        inputs = (ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+                  ptr(threshold))
+        shape = (n_slots, d, n_query, n_probe, metric_code(distance), n_split)
+        counts = torch.empty(n_seg, device=device, dtype=torch.int32)
+        call("tpq_ivfflat_range_count", device, *inputs, ptr(counts), *shape)
+        offsets = torch.zeros(n_seg + 1, device=device, dtype=torch.int64)
+        offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(offsets[-1].item())     # the host sync a variable-size output needs
+        values = torch.empty(total, device=device, dtype=torch.float32)
+        address = torch.empty(total, device=device, dtype=torch.int64)
+        if total:
+            call("tpq_ivfflat_range_fill", device, *inputs, ptr(offsets), ptr(values), ptr(address), *shape)
+        return offsets[::n_split * 8].contiguous(), values, address
