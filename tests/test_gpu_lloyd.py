@@ -290,3 +290,28 @@ def test_coarse_assign_cascade_ties_and_flags(monkeypatch):
     lab = op(T(x3), T(c3))
     _, l32 = K.MaxSimHip(distance="euclidean")(T(x3), T(c3), dim=1)
     assert torch.equal(lab, l32) and op.last_rechecked() == m
+
+
+def test_coarse_assign_cascade_candidate_list_flush_and_overflow(monkeypatch):
+    """the narrow candidate route's staged pair list (cand_stream_kernel; the wide route's has its own test): 8 chunks
+    = 16 half-chunks cross its every-eighth-stage flush while every point has at least 8 tied candidates; then all
+    2 048 centroids identical: every centroid is a candidate of every point, the pair list overflows and the exact
+    fallback takes over.  Whichever branch runs, the labels are the oracle's (ties to the smaller index) and every
+    point -- each has an exact tie for its best -- is listed"""
+    import torchpq_amd.kernels as K
+    monkeypatch.setattr(K.CoarseAssignHip, "default_route", "cascade")  # (small problems take other paths by default)
+    rng = np.random.default_rng(5)
+    d, m, n = 48, 3000, 2048
+    x = rng.integers(-9, 9, (d, m)).astype(np.float32)
+    op = K.CoarseAssignHip(distance="euclidean")
+    cent = np.tile(x[:, :256], (1, 8))                 # chunks 1..7 repeat chunk 0
+    assert cent.shape == (d, n)
+    lab = op(T(x), T(cent))
+    _, el = c_oracle.max_sim(x[None], cent[None], "euclidean", "expanded")
+    assert np.array_equal(N(lab), el[0]) and N(lab).max() < 256
+    assert op.last_rechecked() == m
+    same = np.tile(x[:, :1], (1, n))                   # one centroid, 2 048 times
+    lab = op(T(x), T(same))
+    _, el = c_oracle.max_sim(x[None], same[None], "euclidean", "expanded")
+    assert np.array_equal(N(lab), el[0]) and not N(lab).any()
+    assert op.last_rechecked() == m

@@ -8,8 +8,9 @@ appearance.  Prints the kernel count per unit and every kernel that differs, is 
 
     python tools/isa_diff.py [--parent HEAD] [--jobs 8] [--cache DIR] [unit ...]
 
-A unit is a file of torchpq_amd/csrc, `scan_packed.hip:64` for one per-M unit; default: scan.hip and scan_packed.hip
-at every M of build.sh.  --cache keeps the parent's assembly, per revision, between runs (one check per step of a refactor).
+A unit is a file of torchpq_amd/csrc, `scan_packed.hip:64` for one per-M unit, or `old.hip=new1.hip+new2.hip` for a
+unit the working tree has split: the parent's kernels of old.hip against the union of the new units'.  Default: scan.hip
+and scan_packed.hip at every M of build.sh.  --cache keeps the parent's assembly, per revision, between runs (one check per step of a refactor).
 """
 import argparse
 import os
@@ -71,16 +72,21 @@ def main():
         old = os.path.join(a.cache or td, rev)  # (the parent's assembly, kept per revision)
         os.makedirs(old, exist_ok=True)
         subprocess.run(f"git -C '{ROOT}' archive {rev} | tar -x -C '{td}'", shell=True, check=True)
-        asm = {u: u.replace(":", "_") + ".s" for u in units}
-        jobs = [(os.path.join(td, CSRC), u, flags, os.path.join(old, f)) for u, f in asm.items()
-                if not os.path.exists(os.path.join(old, f))]
-        jobs += [(os.path.join(ROOT, CSRC), u, flags, os.path.join(td, f)) for u, f in asm.items()]
+        asm = lambda u: u.replace(":", "_") + ".s"
+        sides = {u: (u.split("=")[0], u.split("=")[-1].split("+")) for u in units}  # spec -> (parent's unit, ours)
+        jobs = [(os.path.join(td, CSRC), o, flags, os.path.join(old, asm(o))) for o, _ in sides.values()
+                if not os.path.exists(os.path.join(old, asm(o)))]
+        jobs += [(os.path.join(ROOT, CSRC), n, flags, os.path.join(td, asm(n))) for _, ns in sides.values() for n in ns]
         with ThreadPoolExecutor(a.jobs) as ex:
             list(ex.map(lambda j: compile_asm(*j), jobs))
         bad = 0
-        for u, f in asm.items():
-            ko, kn = kernels(os.path.join(old, f)), kernels(os.path.join(td, f))
-            diff = [f"missing {k}" for k in ko if k not in kn] + [f"new {k}" for k in kn if k not in ko] + \
+        for u, (o, ns) in sides.items():
+            ko, kn, twice = kernels(os.path.join(old, asm(o))), {}, []
+            for n in ns:
+                kk = kernels(os.path.join(td, asm(n)))
+                twice += [f"twice {k}" for k in kk if k in kn]
+                kn.update(kk)
+            diff = twice + [f"missing {k}" for k in ko if k not in kn] + [f"new {k}" for k in kn if k not in ko] + \
                    [f"differs {k}" for k in ko if k in kn and ko[k] != kn[k]]
             print("\n  ".join([f"{u}: {len(ko)} kernels before, {len(kn)} after, {len(diff)} not identical"] + diff))
             bad += len(diff)

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "fp16_cascade.h"
+#include "wave_topk.h"
 
 namespace tpq {
 namespace lloyd {
@@ -31,7 +32,7 @@ namespace lloyd {
 //   2. gemm_kernel<true> over the listed points (hi pieces gathered into a compact fragment array): every
 //      (point, centroid) at or above the point's threshold goes to a pair list -- 2-3 per listed point;
 //   3. pair_exact_kernel: the exact kernel's value of each pair -- the SAME instruction sequence as
-//      max_sim_kernel (kmeans.hip): ascending-k fma chains for |x|^2 and |c|^2, v_mfma_f32_32x32x2f32 over
+//      max_sim_kernel (max_sim.hip): ascending-k fma chains for |x|^2 and |c|^2, v_mfma_f32_32x32x2f32 over
 //      ascending k pairs, 2 acc - |x|^2 - |c|^2 -- 32 pairs per wave on the diagonal of a 32 x 32 tile,
 //      folded per point with the 64-bit atomicMax key of the exact kernel's split mode (value, then the
 //      smaller index).
@@ -157,13 +158,8 @@ __global__ __launch_bounds__(CT == 2 ? 512 : 256) void gemm_kernel(GemmArgs a) {
       if (row < rows) thr[ct] = a.thr[row];
     }
   }
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
+  const f32x16 zero = zero_f32x16();
   int cb = cb0, kst = 0;
 #pragma unroll 1
   for (int g = 0; g < n_stage; ++g, ++kst) {
@@ -475,22 +471,14 @@ __global__ __launch_bounds__(256) void gdecide_kernel(GDecideArgs a) {
     if (a.vals) a.vals[p] = (a.euclid ? B1 - n2.x : B1) * ((1.f / s) * (1.f / s));
   }
   const bool listed = valid && !(B1 - B2 > 2.f * delta);
-  const unsigned long long mk = __ballot(listed);
-  if (mk) {
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mk) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(a.count, __popcll(mk));
-    base = __shfl(base, leader, 64);
-    if (listed) {
-      const int slot = base + __popcll(mk & ((1ull << lane) - 1ull));
-      a.list[slot] = p;
-      // (a flagged problem -- delta = inf, keys possibly inf / NaN -- emits no candidates: gdecode_kernel sends
-      // its whole list to the exact kernel)
-      if (slot < a.cap)
-        a.thr[slot] = (a.flag[0] | a.cflag[0]) != 0 ? __builtin_nanf("")  // (no value compares >= NaN, not even inf)
-                                                    : B1 - 2.f * delta - (fabsf(B1) * (1.0f / 65536.0f) + 1.0e-30f);
-    }
+  int slot;
+  if (wave_append(listed, a.count, slot)) {
+    a.list[slot] = p;
+    // (a flagged problem -- delta = inf, keys possibly inf / NaN -- emits no candidates: gdecode_kernel sends
+    // its whole list to the exact kernel)
+    if (slot < a.cap)
+      a.thr[slot] = (a.flag[0] | a.cflag[0]) != 0 ? __builtin_nanf("")  // (no value compares >= NaN, not even inf)
+                                                  : B1 - 2.f * delta - (fabsf(B1) * (1.0f / 65536.0f) + 1.0e-30f);
   }
 }
 
@@ -547,7 +535,7 @@ __global__ __launch_bounds__(256) void pair_exact_kernel(const float* __restrict
     const int p = valid ? list[pr.x] : 0;
     const int c = (int)pr.y;
     const float4* src = reinterpret_cast<const float4*>(half ? Bt + (int64_t)c * dp : Xt + (int64_t)pr.x * dp);
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 acc = zero_f32x16();
     float chain = 0.f;  // half 0: |x|^2, half 1: |c|^2
     for (int k0 = 0; k0 < dp; k0 += 16) {
       float v[16];
@@ -585,9 +573,8 @@ __global__ __launch_bounds__(256) void pair_exact_kernel(const float* __restrict
     }
     v = v + 0.f;  // (-0 -> +0: the key orders by bits)
     if (valid && half == ((l31 >> 2) & 1)) {
-      const unsigned fb = __float_as_uint(v);
-      const unsigned ordered = (fb & 0x80000000u) ? ~fb : (fb | 0x80000000u);
-      atomicMax(keys + p, ((unsigned long long)ordered << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c));
+      const unsigned long long key = key_u64(make_key(v, c));
+      atomicMax(keys + p, key);
     }
   }
 }
@@ -606,10 +593,7 @@ __global__ __launch_bounds__(256) void gdecode_kernel(const int* __restrict__ li
   const int i = list[p];
   const unsigned long long key = keys[i];
   if (key == 0ull) return;  // (beyond the compact array: the fallback's)
-  const unsigned ordered = (unsigned)(key >> 32);
-  const unsigned fb = (ordered & 0x80000000u) ? (ordered & 0x7FFFFFFFu) : ~ordered;
-  inds[i] = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-  if (vals) vals[i] = __uint_as_float(fb);
+  store_keyed_best(key, i, vals, inds);
 }
 
 // the end of both candidate routes -- the centroids and the listed points as rows, the exact value of every pair,
@@ -743,12 +727,6 @@ static int run_wide(const float* A, const float* B, float* vals, int64_t* inds, 
   const auto k_top2 = tile_ct == 4 ? gemm_kernel<false, 4> : gemm_kernel<false, 2>;
   const auto k_cand = tile_ct == 4 ? gemm_kernel<true, 4> : gemm_kernel<true, 2>;
   const int gemm_threads = tile_ct == 4 ? 256 : 512;
-  rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k_top2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds), "lloyd gemm_kernel attr");
-  if (rc) return rc;
-  rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cand), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds), "lloyd gemm_kernel attr");
-  if (rc) return rc;
   const int64_t rows1 = L.T * 32;
   // (gdecide_kernel's comment) accumulation, N, shift rounding, 6-bit keys
   const float eps = 1.001f * (float)(17 * (L.KS + 1) + 8) / 16777216.0f + 1.0f / 8388608.0f + 1.0f / 4194304.0f +
@@ -757,8 +735,8 @@ static int run_wide(const float* A, const float* B, float* vals, int64_t* inds, 
     const int pblocks = (int)(L.T / 8);
     GemmArgs ga{c1, phi, cnorm, part_b, part_i, L.KAp, L.ncb, L.ysplit, pblocks, rows1, nullptr, nullptr, nullptr, nullptr,
                 0, nullptr, n};
-    hipLaunchKernelGGL(k_top2, dim3(gemm_grid(pblocks, L.ysplit)), dim3(gemm_threads), lds, st, ga);
-    TPQ_LAUNCH_CHECK("lloyd gemm_kernel");
+    rc = launch_with_lds(k_top2, "lloyd gemm_kernel", dim3(gemm_grid(pblocks, L.ysplit)), dim3(gemm_threads), lds, st, ga);
+    if (rc) return rc;
     // (ranges of ceil(ncb / ysplit) centroid blocks: the last ones may be empty and write nothing)
     const int cb_per = (L.ncb + L.ysplit - 1) / L.ysplit, yused = (L.ncb + cb_per - 1) / cb_per;
     GDecideArgs da{part_b, part_i, 2 * yused, rows1, norms, cmax, scale, flag, cflag, inds, vals, list1, count1,
@@ -772,8 +750,9 @@ static int run_wide(const float* A, const float* B, float* vals, int64_t* inds, 
     TPQ_LAUNCH_CHECK("lloyd ggather_kernel");
     GemmArgs ga{c1, p2, cnorm, nullptr, nullptr, L.KAp, L.ncb, L.ysplit, L.cap2 / 256, (int64_t)L.cap2, count1, thr, pairs,
                 n_pairs, L.pair_cap, oflag, n};
-    hipLaunchKernelGGL(k_cand, dim3(gemm_grid(L.cap2 / 256, L.ysplit)), dim3(gemm_threads), lds, st, ga);
-    TPQ_LAUNCH_CHECK("lloyd gemm_kernel (candidates)");
+    rc = launch_with_lds(k_cand, "lloyd gemm_kernel (candidates)", dim3(gemm_grid(L.cap2 / 256, L.ysplit)),
+                         dim3(gemm_threads), lds, st, ga);
+    if (rc) return rc;
   }
   // pass 3: exact values of the pairs
   return run_pair_tail(A, B, vals, inds, d, m, n, euclid, ws, L, flag, cflag, L.cap3, st);
@@ -892,13 +871,8 @@ __global__ __launch_bounds__(kWaves * 64) void cand_stream_kernel(CandStreamArgs
           f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_hi, voff, (st >> 1) * 2048 + (st & 1) * 32, 0));
     });
   }
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
+  const f32x16 zero = zero_f32x16();
 #pragma unroll 1
   for (int h = 0; h < c.n_half; ++h) {
     __syncthreads();  // half chunk h has landed (vmcnt(0) + barrier); everyone is done with the other buffer
@@ -963,7 +937,7 @@ static int run_cand_tail(const float* A, const float* B, float* vals, int64_t* i
   int rc = dispatch_ks<8>(L.KS, [&](auto ks) -> int {
     constexpr int K = decltype(ks)::value;
     return launch_with_lds(cand_stream_kernel<K>, "lloyd cand_stream_kernel", dim3((unsigned)(L.cap2 / kCandPoints)),
-                           (size_t)2 * 4 * (K + 1) * 1024 + sizeof(PairList), st, ca, ga);
+                           dim3(kWaves * 64), (size_t)2 * 4 * (K + 1) * 1024 + sizeof(PairList), st, ca, ga);
   });
   if (rc) return rc;
   return run_pair_tail(A, B, vals, inds, d, m, n, 1, ws, L, reinterpret_cast<const int*>(ws + L.prep_off + L.P.flag_off),

@@ -29,34 +29,13 @@
 //      shift by mu and -- on the raw norms -- the rounding of the exact chain itself.  A point whose two
 //      best fast values are further apart than 2 delta has its label decided: any other centroid is
 //      worse in the exact arithmetic too.  The rest (1-3 % at d = 128) are appended to a list;
-//   3. the bit-exact fp32-MFMA kernel (max_sim_kernel, kmeans.hip) over the listed points only: it
+//   3. the bit-exact fp32-MFMA kernel (max_sim_kernel, max_sim.hip) over the listed points only: it
 //      reads the list and its length from device memory (no host round trip; the grid covers the
 //      worst case and surplus blocks leave at once).
-#include <type_traits>
-
-#include "fp16_cascade.h"  // lloyd_assign*, lloyd_wide_supported (assign_cascade.hip), launch_max_sim_list (kmeans.hip)
+#include "fp16_cascade.h"  // lloyd_assign*, lloyd_wide_supported (assign_cascade.hip), launch_max_sim_list (max_sim.hip)
 
 namespace tpq {
 namespace afast {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int I0, int I1, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    static_for<I0 + 1, I1>(f);
-  }
-}
-
-__device__ __forceinline__ void split3(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - (float)p1;
-  p2 = (__bf16)r1;
-  const float r2 = r1 - (float)p2;
-  p3 = (__bf16)r2;
-}
 
 // top-2 of fast values: (b1, b2, bi) <- v with in-unit index CL (inline constant).  A tie with b1
 // keeps the earlier index and makes b2 == b1: the point is then ambiguous by construction.
@@ -154,7 +133,7 @@ __global__ __launch_bounds__(64) void assign_prep_kernel(const float* __restrict
     bf16x8 f = {0, 0, 0, 0, 0, 0, 0, 0};
     if (half == 0) {
       __bf16 h, mm, lo;
-      split3(c < n ? (euclid ? -s : 0.f) : -3.0e38f, h, mm, lo);
+      split3_bf16(c < n ? (euclid ? -s : 0.f) : -3.0e38f, h, mm, lo);
       f[0] = h;
       f[1] = mm;
       f[2] = lo;
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(64) void assign_prep_kernel(const float* __restrict
       float x = (k < d && c < n) ? B[(int64_t)k * n + c] - mu[k] : 0.f;
       if (euclid) x *= 2.f;
       __bf16 h, mm, lo;
-      split3(x, h, mm, lo);
+      split3_bf16(x, h, mm, lo);
       p[0][j] = h;
       p[1][j] = mm;
       p[2][j] = lo;
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void assign_fast_kernel(FastArgs a)
         // lanes without a point and dimensions beyond d read 0 and stay 0 (mu is 0 beyond d)
         const float xc = pv[ct] ? x[j] - mk[j] : 0.f;
         __bf16 p[3];
-        split3(xc, p[0], p[1], p[2]);
+        split3_bf16(xc, p[0], p[1], p[2]);
 #pragma unroll
         for (int q = 0; q < NP; ++q) xs[ct][st][q][j] = p[q];
         s2 = fmaf(xc, xc, s2);
@@ -259,12 +238,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void assign_fast_kernel(FastArgs a)
     an2[ct] = s2 + __shfl_xor(s2, 32, 64);  // (any order: the norms only scale the bound)
     an2raw[ct] = s2raw + __shfl_xor(s2raw, 32, 64);
   }
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
   float b1[CT], b2[CT];
   int bi[CT], bu[CT];
 #pragma unroll
@@ -296,7 +270,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void assign_fast_kernel(FastArgs a)
 #pragma unroll
       for (int q = 0; q < NP; ++q) ar[0][q] = up[(1 + q) * 64];
     }
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = zero_f32x16();
     // epilogue slice after MFMA number mi (of NM): CT * 16 values spread over gaps [CT, NM)
     auto slice = [&](auto mi_c) {
       constexpr int mi = decltype(mi_c)::value;
@@ -497,11 +471,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void select_resident_kernel(SelArgs
   bool iv, ivn = false;
   int i, in_ = 0;
   __syncthreads();  // fragments (vmcnt(0) of the DMA) and mu_s are in LDS
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   // this lane's 8 centring values of k-step st (two ds_read_b128)
   auto load_mu = [&](int st, float (&mk)[8]) {
-    const f32x4v lo = *reinterpret_cast<const f32x4v*>(mu_s + 16 * st + 8 * half);
-    const f32x4v hi = *reinterpret_cast<const f32x4v*>(mu_s + 16 * st + 8 * half + 4);
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(mu_s + 16 * st + 8 * half);
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(mu_s + 16 * st + 8 * half + 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       mk[j] = lo[j];
@@ -516,7 +489,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void select_resident_kernel(SelArgs
     const float x = xr[st * 8 + j];
     const float xc = x - muv;
     __bf16 h, mm, lo;
-    split3(xc, h, mm, lo);
+    split3_bf16(xc, h, mm, lo);
     dst[st][0][j] = h;
     dst[st][1][j] = mm;
     // (asm: left to the compiler the two norm chains are packed into v_pk_fma_f32 with a v_mov per
@@ -555,12 +528,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void select_resident_kernel(SelArgs
     c1k[1] = fp[3 * 64];
     c2r[1] = fp[4 * 64];
   }
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
   const float cn = sqrtf(__uint_as_float(a.cmax2_bits[b * 2])), cnr = sqrtf(__uint_as_float(a.cmax2_bits[b * 2 + 1]));
 
   auto finish_tile = [&](bool fiv, int fi, float c2own, float r2own) {
@@ -594,7 +562,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void select_resident_kernel(SelArgs
     const bf16x8* up = fp + U * FPU * 64;
     const bf16x8* upn = fp + ((U + 1) & 7) * FPU * 64;  // the next unit (unit 0 of the next tile after 7)
     const float before0 = b1[0], before1 = b1[1];
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = zero_f32x16();
     const bf16x8 cfrag = up[0];
     float mk[8];
     if constexpr (U >= 4 && U - 4 < KS) load_mu(U - 4, mk);
@@ -713,7 +681,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void select_resident_kernel(SelArgs
   }
 }
 
-// ---- 3. exact re-check: max_sim_kernel (kmeans.hip, the bit-exact fp32-MFMA kernel) over the list ----
+// ---- 3. exact re-check: max_sim_kernel (max_sim.hip, the bit-exact fp32-MFMA kernel) over the list ----
 struct Layout {
   size_t frags_off, frags_bytes, cmax_off, count_off, mu_off, list_off, keys_off, ac_off, total;
   int cap;
@@ -757,11 +725,6 @@ static int run(const float* A, const float* B, float* vals, int64_t* inds, int d
                      euclid);
   TPQ_LAUNCH_CHECK("assign_prep_kernel");
   const size_t lds = 2 * chunk_bytes(KS, NP);
-  auto kernel = assign_fast_kernel<KS, NP, CT>;
-  rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                 "assign_fast_kernel attr");
-  if (rc) return rc;
   // roundings of the full-size partial sum (see the accumulation order in the kernel)
   const int terms = NP == 2 ? KS * 16 + 2 + 3 : KS * 16 * n_products(NP) + 3;
   // dropped products: NP = 2: c2 a2 + r_c a + c r_a <= 3 x 2^-16 |a_k c_k| (1 % slack for the second-order
@@ -771,8 +734,9 @@ static int run(const float* A, const float* B, float* vals, int64_t* inds, int d
   FastArgs fa{A, frags, cmax, mu, inds, vals, list, count, d, m, units_padded, euclid,
               eps_prod + (float)(terms + 8) / 8388608.0f, (float)(d + 4) / 16777216.0f};
   const int per_block = kWaves * 32 * CT;
-  hipLaunchKernelGGL(kernel, dim3((m + per_block - 1) / per_block), dim3(kWaves * 64), lds, st, fa);
-  TPQ_LAUNCH_CHECK("assign_fast_kernel");
+  rc = launch_with_lds(assign_fast_kernel<KS, NP, CT>, "assign_fast_kernel", dim3((m + per_block - 1) / per_block),
+                       dim3(kWaves * 64), lds, st, fa);
+  if (rc) return rc;
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + L.keys_off);
   rc = check_hip(hipMemsetAsync(keys, 0, (size_t)m * 8, st), "coarse_assign keys memset");
   if (rc) return rc;
@@ -810,17 +774,13 @@ static int run_select(const float* A, const float* B, float* vals, int64_t* inds
   hipLaunchKernelGGL((assign_prep_kernel<KS, 2>), dim3(8, l), dim3(64), 0, st, B, frags, cmax, mu, d, n, euclid);
   TPQ_LAUNCH_CHECK("assign_prep_kernel");
   const size_t lds = (size_t)8 * (2 * KS + 1) * 1024 + 16 * KS * 4;
-  auto kernel = select_resident_kernel<KS>;
-  rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                 "select_resident_kernel attr");
-  if (rc) return rc;
   const int terms = KS * 16 + 2 + 3;
   SelArgs sa{A, frags, cmax, mu, inds, vals, list, count, d, m, euclid,
              3.03f / 65536.0f + (float)(terms + 8) / 8388608.0f, (float)(d + 4) / 16777216.0f};
   const int per_block = kWaves * 32 * kSelTiles;
-  hipLaunchKernelGGL(kernel, dim3((m + per_block - 1) / per_block, l), dim3(kWaves * 64), lds, st, sa);
-  TPQ_LAUNCH_CHECK("select_resident_kernel");
+  rc = launch_with_lds(select_resident_kernel<KS>, "select_resident_kernel", dim3((m + per_block - 1) / per_block, l),
+                       dim3(kWaves * 64), lds, st, sa);
+  if (rc) return rc;
   return launch_max_sim_list(A, B, vals, inds, l, d, m, n, euclid, list, count, nullptr, nullptr, 0, st);
 }
 

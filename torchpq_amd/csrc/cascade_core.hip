@@ -370,12 +370,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void coarse_kernel(StepArgs a) {
   // MFMAs have taken them --, k-steps >= 2 through a three-slot ring two k-steps ahead
   f16x8 a0 = ldsf(fp + 1 * 64), a1 = a0, aring[3];
   if constexpr (KS > 1) a1 = ldsf(fp + 2 * 64);
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
   const float s = a.scale[b];
   const float cn = sqrtf(__uint_as_float(a.cmax2_bits[b * kCm])), cnr = sqrtf(__uint_as_float(a.cmax2_bits[b * kCm + 1]));
   const float c2n = a.level == 1 ? sqrtf(__uint_as_float(a.cmax2_bits[b * kCm + 2])) : -1.f;
@@ -403,7 +398,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void coarse_kernel(StepArgs a) {
     constexpr int U = decltype(u_c)::value;
     const u32x4* up = fp + U * FL * 64;
     const u32x4* upn = fp + ((U + 1) & 7) * FL * 64;  // the next unit (unit 0 of the next tile after 7)
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = zero_f32x16();
     const bf16x8 cfrag = __builtin_bit_cast(bf16x8, up[0]);
     if constexpr (U < 4) {  // the next wide tile's hi pieces: 2 KS 16-byte loads over units 0..3
       constexpr int l0 = (U * 2 * KS) / 4, l1 = ((U + 1) * 2 * KS) / 4;
@@ -560,12 +555,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void refine_kernel(StepArgs a) {
     c1k[1] = ldsf(fp + 3 * 64);
     c2r[1] = ldsf(fp + 4 * 64);
   }
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
   const float s = a.scale[b];
   const float cn = sqrtf(__uint_as_float(a.cmax2_bits[b * kCm])), cnr = sqrtf(__uint_as_float(a.cmax2_bits[b * kCm + 1]));
   const float c2n = a.level == 1 ? sqrtf(__uint_as_float(a.cmax2_bits[b * kCm + 2])) : -1.f;
@@ -595,7 +585,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void refine_kernel(StepArgs a) {
     const u32x4* up = fp + U * FPU * 64;
     const u32x4* upn = fp + ((U + 1) & 7) * FPU * 64;  // the next unit (unit 0 of the next tile after 7)
     const float before0 = b1[0], before1 = b1[1];
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = zero_f32x16();
     const bf16x8 cfrag = __builtin_bit_cast(bf16x8, up[0]);
     auto fill = [&](auto mi_c) {
       constexpr int mi = decltype(mi_c)::value;
@@ -759,13 +749,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void refine_stream_kernel(StepArgs 
   float b1[2] = {-INFINITY, -INFINITY}, b2[2] = {-INFINITY, -INFINITY};
   int bu[2] = {0, 0};
   f16x8 c1k[KS], c2r[3];
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
+  const f32x16 zero = zero_f32x16();
 
   // unit U of the half chunk in `base`; the values of the unit before it (`fin`, global unit number gprev)
   // go through the top-2 update between the MFMAs
@@ -925,24 +910,16 @@ __global__ __launch_bounds__(256) void decide_kernel(StepArgs a, int n_chunks) {
     if (a.vals) a.vals[p] = (B1 - n2.x) * ((1.f / s) * (1.f / s));
   }
   const bool listed = valid && !(B1 - B2 > 2.f * delta);
-  const unsigned long long mk = __ballot(listed);
-  if (mk) {
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mk) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(a.count, __popcll(mk));
-    base = __shfl(base, leader, 64);
-    if (listed) {
-      const int slot = base + __popcll(mk & ((1ull << lane) - 1ull));
-      a.list[slot] = p;
-      // candidate route (cand_stream_kernel): every centroid at or above this may be the exact winner
-      // (a flagged problem -- non-finite data, centroids beyond fp16's range: delta = inf, the keys may be inf or
-      // NaN -- emits no candidates at all: gdecode_kernel sends its whole list to the exact kernel)
-      if (LEVEL == 1 && a.thr && slot < a.thr_cap)
-        a.thr[slot] = (a.flag[0] | a.cflag[0]) != 0
-                          ? __builtin_nanf("")  // (no value compares >= NaN, not even inf)
-                          : B1 - 2.f * delta - (fabsf(B1) * (1.0f / 65536.0f) + 1.0e-30f);
-    }
+  int slot;
+  if (wave_append(listed, a.count, slot)) {
+    a.list[slot] = p;
+    // candidate route (cand_stream_kernel): every centroid at or above this may be the exact winner
+    // (a flagged problem -- non-finite data, centroids beyond fp16's range: delta = inf, the keys may be inf or
+    // NaN -- emits no candidates at all: gdecode_kernel sends its whole list to the exact kernel)
+    if (LEVEL == 1 && a.thr && slot < a.thr_cap)
+      a.thr[slot] = (a.flag[0] | a.cflag[0]) != 0
+                        ? __builtin_nanf("")  // (no value compares >= NaN, not even inf)
+                        : B1 - 2.f * delta - (fabsf(B1) * (1.0f / 65536.0f) + 1.0e-30f);
   }
 }
 
@@ -985,7 +962,7 @@ int launch_coarse(int KS, const StepArgs& sa, int grid_y, hipStream_t st) {
   const dim3 grid((unsigned)((wide + per_block - 1) / per_block), grid_y);
   return dispatch_ks<8>(KS, [&](auto ks) -> int {
     constexpr int K = decltype(ks)::value;
-    return launch_with_lds(coarse_kernel<K>, "lloyd coarse_kernel", grid,
+    return launch_with_lds(coarse_kernel<K>, "lloyd coarse_kernel", grid, dim3(kWaves * 64),
                            (size_t)8 * (K + 1) * 1024 + sizeof(BlockListT<kCoarseList>), st, sa);
   });
 }
@@ -995,7 +972,7 @@ int launch_refine(int KS, const StepArgs& sa, int grid_y, hipStream_t st) {
   const dim3 grid((unsigned)((sa.T + per_block - 1) / per_block), grid_y);
   return dispatch_ks<8>(KS, [&](auto ks) -> int {
     constexpr int K = decltype(ks)::value;
-    return launch_with_lds(refine_kernel<K>, "lloyd refine_kernel", grid,
+    return launch_with_lds(refine_kernel<K>, "lloyd refine_kernel", grid, dim3(kWaves * 64),
                            (size_t)8 * (2 * K + 1) * 1024 + sizeof(BlockListT<kRefineList>), st, sa);
   });
 }
@@ -1004,7 +981,7 @@ int launch_refine_stream(int KS, const StepArgs& sa, int n_half, hipStream_t st)
   const dim3 grid((unsigned)(((int64_t)sa.m + kWaves * 32 - 1) / (kWaves * 32)));
   return dispatch_ks<8>(KS, [&](auto ks) -> int {
     constexpr int K = decltype(ks)::value;
-    return launch_with_lds(refine_stream_kernel<K>, "lloyd refine_stream_kernel", grid,
+    return launch_with_lds(refine_stream_kernel<K>, "lloyd refine_stream_kernel", grid, dim3(kWaves * 64),
                            (size_t)2 * 4 * (2 * K + 1) * 1024 + sizeof(BlockListT<kStreamList>), st, sa, n_half);
   });
 }

@@ -33,6 +33,18 @@ inline int check_hip(hipError_t e, const char* what) {
     if (_e != hipSuccess) return ::tpq::check_hip(_e, name);     \
   } while (0)
 
+// raises the kernel's dynamic-LDS limit to `lds` bytes, launches it, checks the launch
+template <class Kernel, class... Args>
+int launch_with_lds(Kernel kernel, const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                    const Args&... args) {
+  int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  TPQ_LAUNCH_CHECK(name);
+  return TPQ_OK;
+}
+
 // A/B switches read from the environment exist only in experiment builds (tools/build_variant.sh passes
 // -DTPQ_AB_SWITCHES); the product library reads no environment variable and carries none of their names.
 #ifdef TPQ_AB_SWITCHES

@@ -15,18 +15,16 @@
 //            + s^2 (d + 4) 2^-24 (|x| + |c|max)^2                the exact fp32 chain's own rounding
 // delta = 1.25 x that.  A point whose two best fast values differ by more than 2 delta has its
 // label decided -- the arg-max of tpq_max_sim, bit for bit; the others are listed and re-evaluated
-// by the exact fp32-MFMA kernel (launch_max_sim_list, kmeans.hip) on the raw data.
+// by the exact fp32-MFMA kernel (launch_max_sim_list, max_sim.hip) on the raw data.
 #pragma once
-#include <type_traits>
-
-#include "common.h"
+#include "mfma_util.h"
 
 #define TPQ_LOCAL __attribute__((visibility("hidden")))  // crosses units, but is no part of the library's surface
 
 namespace tpq {
 int launch_max_sim_list(const float* A, const float* B, float* vals, int64_t* inds, int l, int d, int m, int n,
                         int euclid, const int* list, const int* count, unsigned long long* keys, float* Ac, int cap,
-                        hipStream_t st);  // kmeans.hip
+                        hipStream_t st);  // max_sim.hip
 // tpq_coarse_assign (assign_fast.hip) -> assign_cascade.hip: one problem with many centroids through the cascade
 // (euclidean, d <= 128), and the GEMM-shaped cascade of wide vectors (128 < d <= 1024)
 int lloyd_assign_supported(int d, int64_t m, int n, int route);
@@ -36,20 +34,6 @@ int lloyd_wide_supported(int d, int64_t m, int n);
 int lloyd_assign(const float* A, const float* B, float* vals, int64_t* inds, int d, int64_t m, int n, int euclid, char* ws,
                  hipStream_t st);
 namespace lloyd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int I0, int I1, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    static_for<I0 + 1, I1>(f);
-  }
-}
 
 constexpr int kWaves = 8;
 constexpr int kMu = 128;  // floats per sub-problem in the centring table (d <= 128)
@@ -100,14 +84,6 @@ static PrepLayout prep_layout(int l, int d, int64_t m) {
 
 constexpr int kCm = 4;  // words per sub-problem in cmax2_bits: max N, max |c|^2, max |C - Ch|^2, -
 
-__device__ __forceinline__ void split3_bf16(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - (float)p1;
-  p2 = (__bf16)r1;
-  const float r2 = r1 - (float)p2;
-  p3 = (__bf16)r2;
-}
-
 // Level 1's keys carry 6 bits -- register number + 16 x (unit mod 4) -- so that the unit of the best value
 // needs no bookkeeping of its own (which half of the tile's units it came from is one compare per tile).
 // 2^-17 |v| off: in level 1's bound.
@@ -136,7 +112,7 @@ __device__ __forceinline__ void top2_keys_pair(float& p1, float& p2, float k0, f
 // in place of 3.03 2^-22 (.)^2: the bound is ~36x wider and 5-13 % of the points stay undecided.
 // Level 2 (refine_kernel): those points, gathered through the level-1 list, with all three products
 // (the bound of the header comment): 0.2-0.7 % stay undecided.
-// Level 3: the exact fp32 kernel over the level-2 list (launch_max_sim_list, kmeans.hip).
+// Level 3: the exact fp32 kernel over the level-2 list (launch_max_sim_list, max_sim.hip).
 // Every level decides a point only when its two best fast values are further apart than twice its
 // own rigorous bound, so the labels are tpq_max_sim's whatever the split between the levels.
 struct StepArgs {
@@ -175,17 +151,6 @@ static float level_eps(int KS, int d, int level) {
                        1.0f / 524288.0f;  // accumulation, norm chain, shift rounding, key bits
   return level == 1 ? common + 1.0f / 131072.0f  // (the dropped pieces: per point, emit()); 6-bit keys: 2^-17
                     : 3.03f / 4194304.0f + common;
-}
-
-// launches a kernel of kWaves waves that needs `lds` bytes of dynamic LDS
-template <class Kernel, class... Args>
-static int launch_with_lds(Kernel kernel, const char* name, dim3 grid, size_t lds, hipStream_t st, const Args&... args) {
-  int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kernel, grid, dim3(kWaves * 64), lds, st, args...);
-  TPQ_LAUNCH_CHECK(name);
-  return TPQ_OK;
 }
 
 // ---- host launchers of the kernels of cascade_core.hip (KS at run time) -----------------------------------

@@ -1,5 +1,5 @@
 // K-means assign on the bf16 matrix cores with fp32-level accuracy (training path of
-// MultiKMeans.fit; the bit-exact fp32-MFMA kernels of kmeans.hip stay the encode / predict path).
+// MultiKMeans.fit; the bit-exact fp32-MFMA kernels of max_sim.hip stay the encode / predict path).
 //
 // tpq_max_sim_split computes the same (max, arg-max) of 2 a.b - |a|^2 - |b|^2 (or a.b) as
 // tpq_max_sim (replaces max_sim_tn, torchpq/kernels/cuda/max_sim.cu:182-309, as called from the
@@ -21,34 +21,20 @@
 // never stored codes.
 //
 // Structure: centroids are the MFMA rows, points the columns (each lane owns ONE point: the
-// arg-max over centroids is an in-lane reduction over accumulator registers, as in kmeans.hip).
+// arg-max over centroids is an in-lane reduction over accumulator registers, as in max_sim.hip).
 // A block of 8 waves stages the <= 256 centroids of sub-problem b ONCE -- scaled by 2 (exact),
 // split, laid out in LDS in MFMA-fragment order [unit][k-step][piece][lane] x 16 B, so that every A
 // operand is one conflict-free ds_read_b128 at lane*16 + constant -- plus -|c|^2 per centroid,
 // which seeds the accumulator: after the chain acc = 2 a.c - |c|^2 and the epilogue is a bare
 // compare + two selects per value.  Each wave then walks kSpTiles tiles of 32 points; the raw fp32
 // fragment of tile t+1 is loaded under units 0-3 of tile t and split under units 4-7.
-#include <type_traits>
-
-#include "common.h"
+#include "mfma_util.h"
 
 namespace tpq {
 namespace split {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int I0, int I1, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    static_for<I0 + 1, I1>(f);
-  }
-}
-
 // (best, besti) <- (val, CL) if val > best.  CL is an inline constant (0..64): see ms_take in
-// kmeans.hip.  Inputs are accumulator registers of the PREVIOUS unit, whose last MFMA retired at
+// max_sim.hip.  Inputs are accumulator registers of the PREVIOUS unit, whose last MFMA retired at
 // least one full MFMA issue slot earlier (the callers place no slice before the second MFMA of
 // the running unit), so no MFMA->VALU wait states are owed inside the asm.
 template <int CL>
@@ -70,15 +56,6 @@ __device__ __forceinline__ void take2(float& best, int& besti, float v0, float v
       : "+v"(best), "+v"(besti)
       : "v"(v0), "v"(v1), "n"(CL0), "n"(CL1)
       : "vcc");
-}
-
-// x -> (x1, x2, x3), exact: x == x1 + x2 + x3
-__device__ __forceinline__ void split3(float x, __bf16& p1, __bf16& p2, __bf16& p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - (float)p1;
-  p2 = (__bf16)r1;
-  const float r2 = r1 - (float)p2;
-  p3 = (__bf16)r2;
 }
 
 #ifndef TPQ_SP_TILES
@@ -121,7 +98,7 @@ __global__ __launch_bounds__(kSpWaves * 64, 2) void max_sim_split_kernel(
       float x = (k < d && c < n) ? Bb[(int64_t)k * n_total + c] : 0.f;
       if (euclidean) x *= 2.f;  // exact; the chain then yields 2 a.c
       __bf16 h, mm, lo;
-      split3(x, h, mm, lo);
+      split3_bf16(x, h, mm, lo);
       p1[j] = h;
       p2[j] = mm;
       p3[j] = lo;
@@ -158,7 +135,7 @@ __global__ __launch_bounds__(kSpWaves * 64, 2) void max_sim_split_kernel(
     bf16x8 f = {0, 0, 0, 0, 0, 0, 0, 0};
     if (threadIdx.x < 256) {
       __bf16 h, mm, lo;
-      split3(nrm, h, mm, lo);
+      split3_bf16(nrm, h, mm, lo);
       f[0] = h;
       f[1] = mm;
       f[2] = lo;
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(kSpWaves * 64, 2) void max_sim_split_kernel(
     constexpr int s = decltype(s_c)::value, j = decltype(j_c)::value;
     const float x = xr[s * 8 + j];
     __bf16 h, mm, lo;
-    split3(x, h, mm, lo);
+    split3_bf16(x, h, mm, lo);
     dst[s][0][j] = h;
     dst[s][1][j] = mm;
     dst[s][2][j] = lo;
@@ -219,12 +196,7 @@ __global__ __launch_bounds__(kSpWaves * 64, 2) void max_sim_split_kernel(
 #pragma unroll
   for (int p = 0; p < 3; ++p) ar[0][p] = cp[p * 64];
   bf16x8 cfrag = cnf[lane];  // -|c|^2 fragment of the coming unit
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};  // B fragment of ones at k = 0, 1, 2
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
 
   auto finish_tile = [&](bool fiv, int fi, float a2own) {
     besti += 32 * bestu + 4 * half;
@@ -259,8 +231,7 @@ __global__ __launch_bounds__(kSpWaves * 64, 2) void max_sim_split_kernel(
     const float best_before = best;
     {
       // (inner product: the fragment is 0 for real centroids and -3e38 for padding columns)
-      const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cfrag, bones, zero, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cfrag, bones, zero_f32x16(), 0, 0, 0);
       cfrag = cnf[((U + 1) & 7) * 64 + lane];  // the next unit's, a whole unit ahead
     }
     static_for<0, KS>([&](auto s_c) {
@@ -378,14 +349,10 @@ static int launch_split(const float* A, const float* B, float* vals, int64_t* in
   const int per_block = kSpWaves * 32 * kSpTiles;
   const dim3 grid((m + per_block - 1) / per_block, l);
   auto go = [&](auto kernel) -> int {
-    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                       "max_sim_split_kernel attr");
-    if (rc) return rc;
     for (int c0 = 0; c0 < n; c0 += 256) {
-      hipLaunchKernelGGL(kernel, grid, dim3(kSpWaves * 64), lds, st, A, B, vals, inds, d, m, n, c0,
-                         c0 == 0 ? 1 : 0);
-      TPQ_LAUNCH_CHECK("max_sim_split_kernel");
+      int rc = launch_with_lds(kernel, "max_sim_split_kernel", grid, dim3(kSpWaves * 64), lds, st, A, B, vals, inds, d, m, n,
+                               c0, c0 == 0 ? 1 : 0);
+      if (rc) return rc;
     }
     return TPQ_OK;
   };

@@ -38,7 +38,7 @@ namespace lloyd {
 // sums[cluster][dim] = sum_i onehot(label_i)[cluster] * (h_i + m_i)[dim] on v_mfma_f32_32x32x16_f16 (exact
 // products 1.0 * piece, fp32 sums: x is represented to 2^-22 relative, two ulps of fp32; the sums are
 // of the centred, scaled values s (x - mu), undone by finalize).  Against centroid_accum_mfma_kernel
-// (kmeans.hip) on the fp32 data: no splitting (it spends ~6.5 VALU instructions per element on three
+// (max_sim.hip) on the fp32 data: no splitting (it spends ~6.5 VALU instructions per element on three
 // bf16 pieces), no LDS staging of the data, 64 + 8 MFMAs per 32 points x 64 dimensions instead of 96.
 // The pieces are stored point-major (a lane of the assign kernels = one point, 8 dimensions); the
 // update contracts over POINTS, so its B operand wants lane = dimension, 8 points.  The transposition
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64 * NH * ((KS + 1) / 2), (NH == 1 ? 2 : 3)) void u
       x[1][ks2] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_mid, voff, ks2 * 32, 0));
     }
   };
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const f32x16 zero = zero_f32x16();
   // tiles dealt round-robin to the blocks of a sub-problem (adjacent rows are read side by side).  A
   // tile's fragments are consumed by its four transposing MFMAs right at the start; the loads of the
   // next tile go into the same registers immediately afterwards.
@@ -405,7 +405,7 @@ extern "C" int tpq_lloyd_step(const float* data, const void* prepared, const flo
   char* ws = reinterpret_cast<char*>(workspace);
   const float* mu = reinterpret_cast<const float*>(p + P.mu_off);
   const float* scale = reinterpret_cast<const float*>(p + P.scale_off);
-  lloyd::u32x4* frags = reinterpret_cast<lloyd::u32x4*>(ws + L.frags_off);
+  u32x4* frags = reinterpret_cast<u32x4*>(ws + L.frags_off);
   unsigned* cmax = reinterpret_cast<unsigned*>(ws + L.cmax_off);
   int* count = reinterpret_cast<int*>(ws + L.count_off);
   int* cflag = reinterpret_cast<int*>(ws + L.cflag_off);
@@ -416,8 +416,8 @@ extern "C" int tpq_lloyd_step(const float* data, const void* prepared, const flo
   if (rc) return rc;
   rc = lloyd::launch_cprep(centroids, mu, scale, frags, cmax, cflag, l, d, n, 1, P.KS, st);
   if (rc) return rc;
-  lloyd::StepArgs sa{reinterpret_cast<const lloyd::u32x4*>(p + P.hi_off),
-                     reinterpret_cast<const lloyd::u32x4*>(p + P.mid_off),
+  lloyd::StepArgs sa{reinterpret_cast<const u32x4*>(p + P.hi_off),
+                     reinterpret_cast<const u32x4*>(p + P.mid_off),
                      reinterpret_cast<const float2*>(p + P.norms_off),
                      frags, cmax, scale, reinterpret_cast<const int*>(p + P.flag_off), cflag, inds, vals,
                      nullptr, nullptr, list, count, (int)m, P.T,
@@ -428,15 +428,15 @@ extern "C" int tpq_lloyd_step(const float* data, const void* prepared, const flo
   rc = launch_max_sim_list(data, centroids, vals, inds, l, d, (int)m, n, 1, list2, count2, nullptr, nullptr, 0, st);
   if (rc) return rc;
   if (new_centroids) {
-    if (TPQ_AB_ENV("TPQ_LL_OLD_UPDATE"))  // (A/B: the fp32-data update of kmeans.hip)
+    if (TPQ_AB_ENV("TPQ_LL_OLD_UPDATE"))  // (A/B: the fp32-data update of max_sim.hip)
       return tpq_compute_centroids(data, inds, new_centroids, l, d, m, n, ws + L.upd_off,
                                    tpq_compute_centroids_workspace_bytes(l, d, n), stream);
     float* sums = reinterpret_cast<float*>(ws + L.upd_off);
     float* counts = sums + (size_t)l * d * n;
     rc = check_hip(hipMemsetAsync(sums, 0, tpq_compute_centroids_workspace_bytes(l, d, n), st), "lloyd_step memset");
     if (rc) return rc;
-    lloyd::UpdArgs ua{reinterpret_cast<const lloyd::u32x4*>(p + P.hi_off),
-                      reinterpret_cast<const lloyd::u32x4*>(p + P.mid_off), inds,
+    lloyd::UpdArgs ua{reinterpret_cast<const u32x4*>(p + P.hi_off),
+                      reinterpret_cast<const u32x4*>(p + P.mid_off), inds,
                       reinterpret_cast<const int*>(p + P.flag_off), sums, counts, d, n, (int)m, P.T};
     return lloyd::dispatch_ks<4>(P.KS, [&](auto ks) -> int {
       return lloyd::run_update<decltype(ks)::value>(ua, data, mu, scale, new_centroids, l, st);

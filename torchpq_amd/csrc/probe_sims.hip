@@ -72,12 +72,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void probe_sims_kernel(ProbeSimsArg
   f32x16 acc[2];
   f16x8 a0 = ldsf(fp + 1 * 64), a1 = a0, aring[3];
   if constexpr (KS > 1) a1 = ldsf(fp + 2 * 64);
-  bf16x8 bones = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (half == 0) {
-    bones[0] = (__bf16)1.0f;
-    bones[1] = (__bf16)1.0f;
-    bones[2] = (__bf16)1.0f;
-  }
+  const bf16x8 bones = ones3_bf16x8(half);  // B fragment of ones at k = 0, 1, 2
   float gm[2][NG];  // [column tile][group of the chunk]
   // the sims rows of this block's queries as ONE buffer resource (base: the block's first query, the chunk's first
   // cell): a lane's stores are buffer_store_dwordx4 at a 32-bit offset -- its row, its half -- plus a compile-time
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void probe_sims_kernel(ProbeSimsArg
     constexpr int U = decltype(u_c)::value;
     const u32x4* up = fp + U * FL * 64;
     const u32x4* upn = fp + ((U + 1) & 7) * FL * 64;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = zero_f32x16();
     const bf16x8 cfrag = __builtin_bit_cast(bf16x8, up[0]);
     if constexpr (U < 4) {
       constexpr int l0 = (U * 2 * KS) / 4, l1 = ((U + 1) * 2 * KS) / 4;
@@ -478,8 +473,8 @@ static int run_probe_sims(const float* query, const char* prepared, int d, int n
   const int64_t per_block = (int64_t)kWaves * n_wide;
   ProbeSimsArgs pa{reinterpret_cast<const u32x4*>(p + P.hi_off), frags, sims, qscale, gmax, nq, n_cells, L.n_groups, n_wide,
                    P.T, 8 * (2 * KS + 1) * 64};
-  int rc = launch_with_lds(kernel, "probe_sims_kernel", dim3((unsigned)((wide + per_block - 1) / per_block), C.chunks), lds,
-                           st, pa);
+  int rc = launch_with_lds(kernel, "probe_sims_kernel", dim3((unsigned)((wide + per_block - 1) / per_block), C.chunks),
+                           dim3(kWaves * 64), lds, st, pa);
   if (rc) return rc;
   *out = ProbeFastBuffers{sims, gmax, band, qscale, xt, q2, L.xt_stride, reinterpret_cast<const float*>(prepared + C.ct_off),
                           reinterpret_cast<const float*>(prepared + C.c2_off), L.n_groups, L.gshift};

@@ -3,7 +3,7 @@
 // tpq_topk_select replaces Top1Select / Top32Select / TopkSelect
 // (torchpq/kernels/cuda/top1_select.cu:542, top32_select.cu:484-636, topk_select.cu:662-805,
 // dispatch torchpq/fn/Topk.py:43-67): one 64-lane wave per row, register top-k (wave_topk.h).
-#include "common.h"
+#include "mfma_util.h"
 #include "probe_fast.h"
 #include "wave_topk.h"
 
@@ -36,9 +36,60 @@ struct ProbeEpilogue {
   float inv_t;                    // 1 / temperature; <= 0: n_probe_list = k
 };
 
+// the selected row: values, columns and -- coarse probe -- the cells' extents and the probe count
 template <int R>
 __device__ __forceinline__ void write_row(const WaveTopK<R>& top, float* __restrict__ vals, int64_t* __restrict__ idx,
-                                          int row, int k, const ProbeEpilogue& pe);
+                                          int row, int k, const ProbeEpilogue& pe) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int e = r * 64 + lane;
+    if (e < k) {
+      const int ci = key_index(top.k[r]);
+      const bool pad = ci == kPadIdx;
+      vals[(int64_t)row * k + e] = pad ? -INFINITY : key_value(top.k[r]);
+      idx[(int64_t)row * k + e] = pad ? -1 : (int64_t)ci;
+      if (pe.cell_start_tbl) {
+        pe.out_cell_start[(int64_t)row * k + e] = pad ? 0 : pe.cell_start_tbl[ci];
+        pe.out_cell_size[(int64_t)row * k + e] = pad ? 0 : pe.cell_size_tbl[ci];
+      }
+    }
+  }
+  if (!pe.cell_start_tbl) return;
+  if (!(pe.inv_t > 0.f) || k < 2) {
+    if (lane == 0) pe.n_probe_list[row] = k;
+    return;
+  }
+  // smart probing on the register-resident sims: element e = r*64 + lane, the assignment (and so
+  // the summation order) of smart_probing_kernel below
+  float zmax = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r * 64 + lane < k) zmax = fmaxf(zmax, -sqrtf(fabsf(key_value(top.k[r]))) * pe.inv_t);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) zmax = fmaxf(zmax, __shfl_xor(zmax, d, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r * 64 + lane < k) sum += expf(-sqrtf(fabsf(key_value(top.k[r]))) * pe.inv_t - zmax);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  const float inv_log = 1.0f / log2f((float)k);
+  float h = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r * 64 + lane < k) {
+      const float p = expf(-sqrtf(fabsf(key_value(top.k[r]))) * pe.inv_t - zmax) / sum;
+      if (p > 0.f) h -= p * log2f(p) * inv_log;
+    }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) h += __shfl_xor(h, d, 64);
+  if (lane == 0) {
+    long long n = (long long)ceilf(h * (float)k);
+    n = n < 1 ? 1 : (n > k ? k : n);
+    pe.n_probe_list[row] = n;
+  }
+}
 
 // one wave selects row `row` (its values at xr[0 .. cols), global memory or LDS) -- the body of
 // topk_select_kernel and of probe_small_kernel
@@ -127,64 +178,6 @@ __device__ __forceinline__ void select_row(float* qvw, int* qiw, const float* xr
   }
   sel.flush();
   write_row<R>(sel.top, vals, idx, row, k, pe);
-}
-
-// the selected row: values, columns and -- coarse probe -- the cells' extents and the probe count
-template <int R>
-__device__ __forceinline__ void write_row(const WaveTopK<R>& top, float* __restrict__ vals, int64_t* __restrict__ idx,
-                                          int row, int k, const ProbeEpilogue& pe) {
-  const int lane = lane_id();
-  struct {
-    const WaveTopK<R>& top;
-  } sel{top};
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int e = r * 64 + lane;
-    if (e < k) {
-      const int ci = key_index(sel.top.k[r]);
-      const bool pad = ci == kPadIdx;
-      vals[(int64_t)row * k + e] = pad ? -INFINITY : key_value(sel.top.k[r]);
-      idx[(int64_t)row * k + e] = pad ? -1 : (int64_t)ci;
-      if (pe.cell_start_tbl) {
-        pe.out_cell_start[(int64_t)row * k + e] = pad ? 0 : pe.cell_start_tbl[ci];
-        pe.out_cell_size[(int64_t)row * k + e] = pad ? 0 : pe.cell_size_tbl[ci];
-      }
-    }
-  }
-  if (!pe.cell_start_tbl) return;
-  if (!(pe.inv_t > 0.f) || k < 2) {
-    if (lane == 0) pe.n_probe_list[row] = k;
-    return;
-  }
-  // smart probing on the register-resident sims: element e = r*64 + lane, the assignment (and so
-  // the summation order) of smart_probing_kernel below
-  float zmax = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    if (r * 64 + lane < k) zmax = fmaxf(zmax, -sqrtf(fabsf(key_value(sel.top.k[r]))) * pe.inv_t);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) zmax = fmaxf(zmax, __shfl_xor(zmax, d, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    if (r * 64 + lane < k) sum += expf(-sqrtf(fabsf(key_value(sel.top.k[r]))) * pe.inv_t - zmax);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
-  const float inv_log = 1.0f / log2f((float)k);
-  float h = 0.f;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    if (r * 64 + lane < k) {
-      const float p = expf(-sqrtf(fabsf(key_value(sel.top.k[r]))) * pe.inv_t - zmax) / sum;
-      if (p > 0.f) h -= p * log2f(p) * inv_log;
-    }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) h += __shfl_xor(h, d, 64);
-  if (lane == 0) {
-    long long n = (long long)ceilf(h * (float)k);
-    n = n < 1 ? 1 : (n > k ? k : n);
-    pe.n_probe_list[row] = n;
-  }
 }
 
 template <int R>
@@ -536,11 +529,10 @@ __global__ __launch_bounds__(256) void id_by_address_kernel(const int64_t* __res
   ids[i] = (a >= 0 && a < cap) ? a2i[a] : -1;
 }
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Coarse similarities sims[q][c] = 2 x_q.C_c - |x_q|^2 - |C_c|^2 (metric.negative_squared_l2_distance,
 // torchpq/metric.py:31-98: library GEMM + three element-wise passes) as one fp32-MFMA kernel, built
-// like max_sim_kernel (kmeans.hip): a block owns 128 QUERIES (4 waves x 32 MFMA columns, operand
+// like max_sim_kernel (max_sim.hip): a block owns 128 QUERIES (4 waves x 32 MFMA columns, operand
 // in registers, prefetched one k-slab ahead) and walks centroid chunks of 256 MFMA rows whose
 // 16-row k-slabs are double-buffered in LDS (global -> registers while the previous slab's 8 x 8
 // MFMAs run -> the other buffer, one barrier per slab).  |C|^2 is accumulated from the values each

@@ -45,6 +45,13 @@ __device__ __forceinline__ int key_index(Key k) { return (int)~k.lo; }
 __device__ __forceinline__ unsigned long long key_u64(Key k) {
   return ((unsigned long long)k.hi << 32) | k.lo;
 }
+__device__ __forceinline__ Key key_of_u64(unsigned long long u) { return Key{(unsigned)(u >> 32), (unsigned)u}; }
+// what a 64-bit atomicMax over key_u64(make_key(value, label)) left for point i -> its label and value
+__device__ __forceinline__ void store_keyed_best(unsigned long long key, int i, float* vals, int64_t* inds) {
+  const Key k = key_of_u64(key);
+  inds[i] = (int64_t)(unsigned)key_index(k);
+  if (vals) vals[i] = key_value(k);
+}
 __device__ __forceinline__ bool key_better(Key a, Key b) { return key_u64(a) > key_u64(b); }
 
 __device__ __forceinline__ bool kv_better(float av, int ai, float bv, int bi) {
