@@ -70,6 +70,9 @@ def _probe_data(kind, d, nq, n_cells, rng):
     (64, 500, 12320, 24, True),      # fp16 route: group maxima of 64 cells, the last group half full
     (32, 400, 17440, 40, False),     # ... of 128 cells, the last group a quarter full
     (48, 300, 4128, 64, True),       # ... of 32 cells, 2 n_probe = the number of groups - 1: the direct list's edge
+    (16, 3, 1024, 600, True),        # one-block kernel at R = 16; smart probing on 10 registers per lane
+    (8, 2, 512, 300, False),         # ... at R = 8
+    (8, 1100, 16500, 100, True),     # group filter (9 query groups x 65 chunks) with an R = 2 selector
 ])
 @pytest.mark.parametrize("route", ["auto", "fp32", "fp16"])
 def test_coarse_probe_is_bit_exact(K, kind, d, nq, n_cells, n_probe, smart, route):

@@ -3,7 +3,7 @@
 # flags (and -DTPQ_AB_SWITCHES: the environment A/B switches exist only in variants, never in the product
 # library), everything else taken from csrc/build/.  The variant is loaded with TPQ_AMD_LIB=<path>.
 #   tools/build_variant.sh <name> "<extra flags>" <unit>...
-#     unit = object basename: scan, cascade_core, assign_cascade, probe_sims, lloyd, select, max_sim, centroid_update, assign_fast, ..., or scan_packed_<M>
+#     unit = object basename: scan, cascade_core, assign_cascade, probe_sims, lloyd, select, coarse_probe, max_sim, centroid_update, assign_fast, ..., or scan_packed_<M>
 #   e.g. tools/build_variant.sh prof "-DTPQ_SCAN_PROFILE" scan scan_packed_64 scan_packed_32
 # -> torchpq_amd/variants/libtorchpq_amd_<name>.so
 set -euo pipefail

@@ -9,7 +9,8 @@ appearance.  Prints the kernel count per unit and every kernel that differs, is 
     python tools/isa_diff.py [--parent HEAD] [--jobs 8] [--cache DIR] [unit ...]
 
 A unit is a file of torchpq_amd/csrc, `scan_packed.hip:64` for one per-M unit, or `old.hip=new1.hip+new2.hip` for a
-unit the working tree has split: the parent's kernels of old.hip against the union of the new units'.  Default: scan.hip
+unit the working tree has split: the parent's kernels of old.hip against the union of the new units'.  The left side
+takes several units too (`old1.hip+old2.hip=new1.hip+new2.hip`) when kernels moved into a unit that already existed.  Default: scan.hip
 and scan_packed.hip at every M of build.sh.  --cache keeps the parent's assembly, per revision, between runs (one check per step of a refactor).
 """
 import argparse
@@ -73,19 +74,20 @@ def main():
         os.makedirs(old, exist_ok=True)
         subprocess.run(f"git -C '{ROOT}' archive {rev} | tar -x -C '{td}'", shell=True, check=True)
         asm = lambda u: u.replace(":", "_") + ".s"
-        sides = {u: (u.split("=")[0], u.split("=")[-1].split("+")) for u in units}  # spec -> (parent's unit, ours)
-        jobs = [(os.path.join(td, CSRC), o, flags, os.path.join(old, asm(o))) for o, _ in sides.values()
+        sides = {u: (u.split("=")[0].split("+"), u.split("=")[-1].split("+")) for u in units}  # spec -> (parent's units, ours)
+        jobs = [(os.path.join(td, CSRC), o, flags, os.path.join(old, asm(o))) for olds, _ in sides.values() for o in olds
                 if not os.path.exists(os.path.join(old, asm(o)))]
         jobs += [(os.path.join(ROOT, CSRC), n, flags, os.path.join(td, asm(n))) for _, ns in sides.values() for n in ns]
         with ThreadPoolExecutor(a.jobs) as ex:
             list(ex.map(lambda j: compile_asm(*j), jobs))
         bad = 0
-        for u, (o, ns) in sides.items():
-            ko, kn, twice = kernels(os.path.join(old, asm(o))), {}, []
-            for n in ns:
-                kk = kernels(os.path.join(td, asm(n)))
-                twice += [f"twice {k}" for k in kk if k in kn]
-                kn.update(kk)
+        for u, (olds, ns) in sides.items():
+            ko, kn, twice = {}, {}, []
+            for side, d, us in ((ko, old, olds), (kn, td, ns)):
+                for n in us:
+                    kk = kernels(os.path.join(d, asm(n)))
+                    twice += [f"twice {k}" for k in kk if k in side]
+                    side.update(kk)
             diff = twice + [f"missing {k}" for k in ko if k not in kn] + [f"new {k}" for k in kn if k not in ko] + \
                    [f"differs {k}" for k in ko if k in kn and ko[k] != kn[k]]
             print("\n  ".join([f"{u}: {len(ko)} kernels before, {len(kn)} after, {len(diff)} not identical"] + diff))

@@ -1,5 +1,5 @@
-// Device-side pieces the MFMA units share (the assign / k-means family, the fp16 cascade, select.hip, lut.hip):
-// operand vector types, the compile-time loop, the exact bf16 split and its constant fragments, the wave-aggregated
+// Device-side pieces the MFMA units share (the assign / k-means family, the fp16 cascade, coarse_probe.hip, lut.hip):
+// operand vector types, the compile-time loop, the loads-ahead block of a sequential chain, the exact bf16 split and its constant fragments, the wave-aggregated
 // list append.  All force-inlined: a unit's kernels own every instruction they run.
 #pragma once
 #include <type_traits>
@@ -22,6 +22,17 @@ __device__ __forceinline__ void static_for(F&& f) {
     f(std::integral_constant<int, I0>{});
     static_for<I0 + 1, I1>(f);
   }
+}
+
+// A block of a chain that is sequential in k while its loads are not: N loads issued together, then use(u, y_u) in
+// ascending u.
+template <int N, class L, class U>
+__device__ __forceinline__ void load_then_use(L&& load, U&& use) {
+  decltype(load(0)) y[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) y[u] = load(u);
+#pragma unroll
+  for (int u = 0; u < N; ++u) use(u, y[u]);
 }
 
 // x -> (p1, p2, p3), exact: x == p1 + p2 + p3 (3 x 8 significant bits, round to nearest even)

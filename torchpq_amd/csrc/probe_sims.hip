@@ -1,10 +1,30 @@
-// The coarse step of search() on the fp16 matrix cores (probe_fast.h; called from select.hip): fast similarities of
-// every (query, cell) pair on data prepared as the fp16 cascade prepares it (fp16_cascade.h; the centroids'
-// preparation runs the shared kernels of cascade_core.hip).
+// The coarse step of search() on the fp16 matrix cores (probe_fast.h; called from coarse_probe.hip), at many cells
+// (IVF4096 / IVF16384 of the reference's benchmark grid), where the fp32-MFMA similarity GEMM (75 TF/s) was 40-85 % of a
+// search: fast similarities of every (query, cell) pair on data prepared as the fp16 cascade prepares it
+// (fp16_cascade.h; the centroids' preparation runs the shared kernels of cascade_core.hip), then a row select on them
+// that re-evaluates its candidates in fp32.
 #include "fp16_cascade.h"
 #include "probe_fast.h"
 
 namespace tpq {
+
+// What the fast pass leaves in the workspace (and the prepared block) for the select kernel.
+struct ProbeFastBuffers {
+  const _Float16* sims;  // [nq][n_cells] fast values f' = 2 a'.c' - |c'|^2 (centred, scaled: per query a monotone image of
+                         // the similarity), stored as fp16 of f' x qscale[q]
+  const float* gmax;     // [nq][n_groups] maxima of the unrounded f' over groups of 2^gshift cells (fp32, not scaled)
+  const float* band;     // [nq] 2 delta' x qscale: the candidate band in STORED units before the rounding of the stored
+                         // values (which the select kernel adds); +inf: the query is evaluated exactly
+  const float* qscale;   // [nq] power of two
+  const float* xt;       // [nq][xt_stride] the queries as rows (fp32, as given)
+  const float* q2;       // [nq] |x|^2 as the exact kernels sum it (fma chain over ascending k)
+  int xt_stride;         // multiple of 4
+  const float* ct;    // [n_cells][d] the centroids as rows
+  const float* c2;    // [n_cells] |C|^2, ascending-k fma chain
+  int n_groups;
+  int gshift;            // log2 of the cells per group (5 or 7)
+};
+
 namespace lloyd {
 
 // ---- the coarse step of search(): fast similarities of every (query, cell) pair (probe_fast.h) ---------------
@@ -483,7 +503,223 @@ static int run_probe_sims(const float* query, const char* prepared, int d, int n
 
 }  // namespace lloyd
 
-// hooks for tpq_ivfpq_coarse_probe (select.hip, probe_fast.h): euclidean, d <= 128, whole 16-byte pieces per row
+// ---- the coarse step's row select on FAST similarities: one wave per query ---------------------------------------
+// The reference offers a reduced-precision coarse GEMM behind use_tensor_core / fp16_scale_mode (torchpq/metric.py:47-73,
+// index/IVFPQIndex.py:98-125) and accepts its errors; here the fp16 pass only SELECTS: every cell that can still be among
+// the query's n_probe best -- fast value within twice a rigorous error bound of the n_probe-th best fast value -- gets the
+// fp32 kernel's own value (the same ascending-k fma chain), and the result (cells, order, similarities) is
+// coarse_sims_kernel's (coarse_probe.hip), bit for bit.
+//   1. the k best fast values of the row, kept with a margin: everything within `band` = 2 delta' of the running
+//      k-th best is admitted and the list holds 64 R > k entries (the group filter works on fast values too: a group
+//      is read when its maximum reaches the k-th largest group maximum minus the band);
+//   2. every list entry within the band of the k-th best fast value is a CANDIDATE: the exact top-k is among them
+//      (|f' - e'| <= delta' for every cell).  A lane evaluates its candidate with the fp32 kernels' own arithmetic --
+//      acc = fma chain over ascending k of C[k][c] x[k], v = ((2 acc) - |x|^2) - |C|^2 -- from the centroid's row copy;
+//   3. the candidates are re-ranked by (exact value desc, cell asc) and the best k written: coarse_sims_kernel +
+//      topk_select_kernel's output, bit for bit.
+// A list full of candidates (an entry may have been evicted), or band = +inf (queries / centroids beyond the fp16 scale):
+// the wave evaluates ALL cells of its query exactly -- slow, and normally never taken.
+constexpr int kCandCap = 256;  // candidate cells a wave keeps without selecting (direct path)
+constexpr int kHotCap = 512;   // hot groups a wave lists
+
+// Every lane of the wave calls it; the lanes with `take` set append x to the wave's own LDS list, in lane order, while
+// it has room.  n -- wave-uniform, kept in a register -- counts every taker, so n > cap says that the list overflowed.
+__device__ __forceinline__ void list_append(bool take, int x, int* list, int cap, int& n) {
+  const unsigned long long b = __ballot(take);
+  const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+  if (take && pos < cap) list[pos] = x;
+  n += __popcll(b);
+}
+
+template <int R>
+__global__ __launch_bounds__(kSelWaves * 64) void probe_select_fast_kernel(ProbeFastBuffers fb, const float* __restrict__ x,
+                                                                          float* __restrict__ vals,
+                                                                          int64_t* __restrict__ idx, int d, int nq,
+                                                                          int n_cells, int k, ProbeEpilogue pe) {
+  __shared__ float qv[kSelWaves * 64];
+  __shared__ int qi[kSelWaves * 64];
+  __shared__ float xq_all[kSelWaves * 128];
+  __shared__ int cand[kSelWaves * kCandCap];
+  __shared__ int hot[kSelWaves * kHotCap];
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int row = blockIdx.x * kSelWaves + wave;
+  if (row >= nq) return;
+  float* xq = xq_all + wave * 128;
+  // everything the wave needs first, issued together: its query's row (d <= 128 floats), |x|^2, band, scale and the
+  // first group maxima
+  const float4 xrow = lane * 4 < d ? reinterpret_cast<const float4*>(fb.xt + (int64_t)row * fb.xt_stride)[lane]
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float q2 = fb.q2[row];
+  const float band0 = fb.band[row];
+  const float qs = fb.qscale[row];
+  const float* __restrict__ gm = fb.gmax + (int64_t)row * fb.n_groups;   // f' (fp32): scaled on the fly
+  float gm0[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) gm0[u] = 64 * u + lane < fb.n_groups ? gm[64 * u + lane] : -INFINITY;
+  if (lane * 4 < d) reinterpret_cast<float4*>(xq)[lane] = xrow;  // (d % 4 != 0: the row copy is zero-padded to xt_stride)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  auto exact = [&](int c) -> float {  // the fp32 kernels' value of (query, cell c)
+    const float4* __restrict__ cr = reinterpret_cast<const float4*>(fb.ct + (int64_t)c * d);
+    float acc = 0.f;
+    int t = 0;
+    auto block = [&](auto n_c) {
+      load_then_use<decltype(n_c)::value>([&](int u) { return cr[(t >> 2) + u]; },
+                                          [&](int u, const float4& y) {
+                                            acc = fmaf(y.x, xq[t + 4 * u], acc);
+                                            acc = fmaf(y.y, xq[t + 4 * u + 1], acc);
+                                            acc = fmaf(y.z, xq[t + 4 * u + 2], acc);
+                                            acc = fmaf(y.w, xq[t + 4 * u + 3], acc);
+                                          });
+    };
+    // (each candidate's row is a lane's own: eight loads in flight, four round trips at d = 128)
+    for (; t + 32 <= d; t += 32) block(std::integral_constant<int, 8>{});
+    for (; t + 16 <= d; t += 16) block(std::integral_constant<int, 4>{});
+    for (; t < d; ++t) acc = fmaf(fb.ct[(int64_t)c * d + t], xq[t], acc);
+    const float v = neg_sq_l2(acc, q2, fb.c2[c]);
+    return v + 0.0f;  // (a statement of its own: folded into the line above, the kernel's registers are allocated differently)
+  };
+#ifdef TPQ_SELECT_STOP
+#define TPQ_STOP_AT(n, val) if (TPQ_SELECT_STOP == n) { if (lane == 0) vals[(int64_t)row * k] = (val); return; }
+#else
+#define TPQ_STOP_AT(n, val)
+#endif
+  TPQ_STOP_AT(1, q2)
+  WaveTopK<R> ex;
+  bool slow = !(band0 < INFINITY);
+  if (!slow) {
+    WaveSelector<R> sel;
+    sel.init(qv + wave * 64, qi + wave * 64, k);
+    sel.margin = band0;
+    const _Float16* __restrict__ xr = fb.sims + (int64_t)row * n_cells;  // stored units: f' x qs, fp16
+    const uint32_t* __restrict__ xr2 = reinterpret_cast<const uint32_t*>(xr);  // (rows are 64-byte aligned: n_cells % 32 == 0)
+    // phase 1: the k-th largest group maximum (a lower bound of the k-th largest fast value)
+    for (int base = 0; base < fb.n_groups; base += 64) {
+      const int g = base + lane;
+      const float gv = base < 256 ? gm0[(base >> 6) & 3] : (g < fb.n_groups ? gm[g] : -INFINITY);
+      const float v = g < fb.n_groups ? gv * qs + 0.0f : -INFINITY;
+      sel.push(g < fb.n_groups && (v >= sel.tau - band0), v, g);
+    }
+    sel.flush();
+    // The stored values are fp16: u = f' x qs rounded to nearest, |stored - u| <= 2^-11 |u| (+ 2^-25 where the result is
+    // subnormal).  A cell that belongs to the exact top k has u in [G_k - band0, M_1] (G_k the k-th largest group
+    // maximum -- a lower bound of the k-th largest u --, M_1 the largest; both unrounded), so its stored value is within
+    // eps = 2^-11 (max(|M_1|, |G_k|) + band0) of u; and the k-th largest stored value is within eps of the k-th largest u
+    // (rounding is monotone, the k-th largest u lies in [G_k, M_1]).  Band in stored values: band0 + 2 eps.  |u| < 2^15
+    // by the choice of qs: eps <= 16 whatever the row holds (fewer than k groups: G_k = -inf).
+    const float gk = sel.top.kth_value(k);
+    const float mag = fmaxf(fabsf(sel.top.kth_value(1)), fabsf(gk)) + band0;
+    const float eps = fminf(16.f, mag * 4.8828125e-4f) * 1.001f + 5.9604645e-8f;
+    const float band = band0 + 2.f * eps;
+    const float tau0 = gk - band;  // -inf while there are fewer than k groups
+    TPQ_STOP_AT(2, tau0)
+    // the hot groups -- those whose maximum reaches tau0 -- as a list in LDS, then their cells two per lane (a dword of
+    // the fp16 row; a 32-cell group is 16 lanes of a load, a 128-cell group all 64), eight loads a round: the walk is a
+    // chain of memory round trips and there are as many of them as rounds
+    int* hl = hot + wave * kHotCap;
+    int n_hot = 0;  // wave-uniform
+    for (int base = 0; base < fb.n_groups; base += 64) {
+      const int g = base + lane;
+      const float gv = base < 256 ? gm0[(base >> 6) & 3] : (g < fb.n_groups ? gm[g] : -INFINITY);
+      const bool is_hot = g < fb.n_groups && (gv * qs >= tau0);
+      list_append(is_hot, g, hl, kHotCap, n_hot);
+    }
+    const bool hot_listed = n_hot <= kHotCap;  // (more groups than the list holds: only beyond 65 536 cells; exact then)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the wave's own LDS appends)
+    const int lpg_shift = fb.gshift - 1;                    // lanes per group: a lane holds two cells
+    const int sub = lane >> lpg_shift, lig = lane & ((1 << lpg_shift) - 1);
+    const int gpl = 64 >> lpg_shift;                        // groups per load
+    auto walk = [&](auto&& consume, auto&& go_on) {
+      for (int h0 = 0; h0 < n_hot && go_on(); h0 += 8 * gpl) {
+        uint32_t vw[8];
+        int cb[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int hi = h0 + u * gpl + sub;
+          const int g = hi < n_hot ? hl[hi] : -1;
+          const int c = (g << fb.gshift) + 2 * lig;   // (n_cells is even: a pair is inside the row or beyond it)
+          const bool ok = g >= 0 && c < n_cells;
+          vw[u] = ok ? xr2[c >> 1] : 0xfc00fc00u;      // (-inf, -inf)
+          cb[u] = ok ? c : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          if (h0 + u * gpl < n_hot) {  // wave-uniform
+            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+            const f16x2 hv = __builtin_bit_cast(f16x2, vw[u]);
+            consume(cb[u] >= 0, cb[u], (float)hv[0]);
+            consume(cb[u] >= 0, cb[u] + 1, (float)hv[1]);
+          }
+        }
+      }
+    };
+    // phase 2, direct: EVERY cell of a hot group whose stored value reaches tau0 is kept -- a superset of the candidates
+    // (cut >= tau0: the k-th largest stored value is not below G_k - eps) that costs a ballot and an LDS append per 64
+    // cells instead of the selector's queue, sorts and merges; the exact top k is among them whatever else is, so the
+    // exact values of all of them, sorted once, are the answer.  More than kCandCap of them (k close to or beyond the
+    // number of groups: G_k is a poor bound or none) and the selector path below finds the cut itself.
+    int* cl = cand + wave * kCandCap;
+    int n_cand = 0;  // wave-uniform
+    bool direct = hot_listed && gk > -INFINITY && 2 * k <= fb.n_groups;  // (k-th of fewer than 2 k maxima: too low a bound to try)
+    if (direct) {
+      walk(
+          [&](bool valid, int c, float v) { list_append(valid && v >= tau0, c, cl, kCandCap, n_cand); },
+          [&]() { return n_cand <= kCandCap; });
+      direct = n_cand <= kCandCap;
+    }
+    TPQ_STOP_AT(3, (float)n_cand)
+    if (direct) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the wave's own LDS appends)
+      ex.init();
+      for (int base = 0; base < n_cand; base += 64) {
+        const bool want = base + lane < n_cand;
+        const int c = want ? cl[base + lane] : 0;
+        const float e = want ? exact(c) : -INFINITY;
+        ex.insert_unsorted(want ? make_key(e, c) : pad_key());
+      }
+      TPQ_STOP_AT(4, ex.kth_value(1))
+    } else if (!hot_listed) {
+      slow = true;
+    } else {
+    sel.init(qv + wave * 64, qi + wave * 64, k);
+    sel.margin = band;
+    // phase 2 through the selector: the k best stored values with their band
+    walk([&](bool valid, int c, float v0) {
+           const float v = v0 + 0.0f;
+           sel.push(valid && (v >= sel.tau - band), v, c);
+         },
+         [&]() { return true; });
+    sel.flush();
+    const float cut = sel.top.kth_value(k) - band;
+    const Key last = readlane_key(sel.top.k[R - 1], 63);
+    if (key_index(last) != kPadIdx && key_value(last) >= cut) slow = true;  // a full list of candidates: wave-uniform
+    if (!slow) {
+      ex.init();
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int c = key_index(sel.top.k[r]);
+        const bool want = c != kPadIdx && key_value(sel.top.k[r]) >= cut;
+        if (__ballot(want) == 0ull) break;  // sorted by fast value: nothing further down qualifies
+        const float e = want ? exact(c) : -INFINITY;
+        ex.insert_unsorted(want ? make_key(e, c) : pad_key());
+      }
+    }
+    }
+  }
+  if (slow) {  // every cell, exactly
+    WaveSelector<R> sel;
+    sel.init(qv + wave * 64, qi + wave * 64, k);
+    for (int base = 0; base < n_cells; base += 64) {
+      const int c = base + lane;
+      const float v = c < n_cells ? exact(c) : -INFINITY;
+      sel.push(c < n_cells && (v >= sel.tau), v, c);
+    }
+    sel.flush();
+    ex = sel.top;
+  }
+  write_row<R>(ex, vals, idx, row, k, pe);
+}
+
+// hooks for tpq_ivfpq_coarse_probe (coarse_probe.hip, probe_fast.h): euclidean, d <= 128, whole 16-byte pieces per row
 int lloyd_probe_supported(int d, int nq, int n_cells) {
   // d % 4: probe_select_fast_kernel reads the centroid rows (stride d floats) as float4.
   // n_cells <= 2^20: the 512 rows of one wide tile per wave (kWaves x 64) x n_cells x 2 bytes must fit the 32-bit
@@ -507,8 +743,8 @@ int lloyd_probe_prepare(const float* centroids, int d, int n_cells, char* prepar
   const lloyd::ProbePrepared C = lloyd::probe_prepared_layout(d, n_cells);
   return lloyd::run_probe_prepare(centroids, d, n_cells, prepared, C, st);
 }
-int lloyd_probe_sims(const float* query, const float* centroids, const void* prepared, int d, int nq, int n_cells,
-                     char* ws, ProbeFastBuffers* out, hipStream_t st) {
+int lloyd_probe_select(const float* query, const float* centroids, const void* prepared, int d, int nq, int n_cells,
+                       int n_probe, float* topk_sims, int64_t* cells, const ProbeEpilogue& pe, char* ws, hipStream_t st) {
   const lloyd::ProbeLayout L = lloyd::probe_layout(d, nq, n_cells);
   const char* prep = reinterpret_cast<const char*>(prepared);
   if (!prep) {  // no prepared block: prepare into the workspace, for this call
@@ -516,10 +752,20 @@ int lloyd_probe_sims(const float* query, const float* centroids, const void* pre
     if (rc) return rc;
     prep = ws + L.prepared_off;
   }
+  ProbeFastBuffers fb;
+  int rc;
   switch (L.KS) {
-    case 2: return lloyd::run_probe_sims<2>(query, prep, d, nq, n_cells, ws, L, out, st);
-    case 4: return lloyd::run_probe_sims<4>(query, prep, d, nq, n_cells, ws, L, out, st);
-    default: return lloyd::run_probe_sims<8>(query, prep, d, nq, n_cells, ws, L, out, st);
+    case 2: rc = lloyd::run_probe_sims<2>(query, prep, d, nq, n_cells, ws, L, &fb, st); break;
+    case 4: rc = lloyd::run_probe_sims<4>(query, prep, d, nq, n_cells, ws, L, &fb, st); break;
+    default: rc = lloyd::run_probe_sims<8>(query, prep, d, nq, n_cells, ws, L, &fb, st);
   }
+  if (rc) return rc;
+  // (the candidate list: 64 R >= n_probe + 16 entries)
+  return with_list_regs(list_regs(n_probe + 16), [&](auto r_c) -> int {
+    hipLaunchKernelGGL(probe_select_fast_kernel<decltype(r_c)::value>, dim3((nq + kSelWaves - 1) / kSelWaves),
+                       dim3(kSelWaves * 64), 0, st, fb, query, topk_sims, cells, d, nq, n_cells, n_probe, pe);
+    TPQ_LAUNCH_CHECK("probe_select_fast_kernel");
+    return TPQ_OK;
+  });
 }
 }  // namespace tpq

@@ -65,13 +65,7 @@ static int launch_ref(ScanArgs a, hipStream_t st) {
 }
 
 static int dispatch_ref(const ScanArgs& a, int R, hipStream_t st) {
-  switch (R) {
-    case 1: return launch_ref<1>(a, st);
-    case 2: return launch_ref<2>(a, st);
-    case 4: return launch_ref<4>(a, st);
-    case 8: return launch_ref<8>(a, st);
-    default: return launch_ref<16>(a, st);
-  }
+  return with_list_regs(R, [&](auto r_c) { return launch_ref<decltype(r_c)::value>(a, st); });
 }
 
 static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st) {
@@ -85,13 +79,7 @@ static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st) {
     TPQ_LAUNCH_CHECK("scan_residual_kernel");
     return TPQ_OK;
   };
-  switch (R) {
-    case 1: return go(scan_residual_kernel<1>);
-    case 2: return go(scan_residual_kernel<2>);
-    case 4: return go(scan_residual_kernel<4>);
-    case 8: return go(scan_residual_kernel<8>);
-    default: return go(scan_residual_kernel<16>);
-  }
+  return with_list_regs(R, [&](auto r_c) { return go(scan_residual_kernel<decltype(r_c)::value>); });
 }
 
 static int run_ref(ScanArgs a, void* workspace, size_t workspace_bytes, hipStream_t st) {

@@ -137,13 +137,7 @@ static int launch(const ScanArgs& a, const FlatArgs& f, hipStream_t st) {
 
 template <int METRIC>
 static int dispatch(const ScanArgs& a, const FlatArgs& f, int R, hipStream_t st) {
-  switch (R) {
-    case 1: return launch<1, METRIC>(a, f, st);
-    case 2: return launch<2, METRIC>(a, f, st);
-    case 4: return launch<4, METRIC>(a, f, st);
-    case 8: return launch<8, METRIC>(a, f, st);
-    default: return launch<16, METRIC>(a, f, st);
-  }
+  return with_list_regs(R, [&](auto r_c) { return launch<decltype(r_c)::value, METRIC>(a, f, st); });
 }
 
 // ---- range search (tpq_ivfflat_range_count / tpq_ivfflat_range_fill) -------------------------------------------

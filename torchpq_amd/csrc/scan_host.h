@@ -14,12 +14,6 @@ static int pool_max_split(int m, int k) {
   return s < 1 ? 1 : s;
 }
 
-static int pow2_ceil(int r) {
-  int p = 1;
-  while (p < r) p <<= 1;
-  return p;
-}
-static int list_regs(int k) { return pow2_ceil((k + 63) / 64); }  // 1, 2, 4, 8, 16
 constexpr int kBandSlack = 8;  // spare list entries the packed path wants beyond k
 static int list_regs_packed(int k) { return pow2_ceil((k + kBandSlack + 63) / 64); }
 // ... and of the finish kernel's exact list on the dump routes: the band of the 16-bit table is ~70 table units wide
@@ -66,7 +60,6 @@ static int pool_list_regs(int k, int m) {
 static int pool_capacity(int k, int m) {  // (16 / 32 registers per lane at read-back; four waves share a query's admissions)
   return (k <= 512 && m > 32) ? 1024 : 2048;
 }  // (16 / 32 registers per lane at read-back)
-static size_t pool_ws_bytes(int nq, int k, int m, int n_lists);
 
 static size_t scan_lds_bytes_ref(int m, int R, int max_nprobe, int fused_floats) {
   const int lut_bytes = m * 1024;

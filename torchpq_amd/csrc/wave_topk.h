@@ -16,6 +16,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace tpq {
 
 constexpr int kPadIdx = 0x7fffffff;
@@ -195,6 +197,25 @@ struct WaveTopK {
     return t;
   }
 };
+
+// Host side: the registers R of a list that holds k entries -- 1, 2, 4, 8 or 16: the instantiations of the kernels
+// built on WaveTopK<R> -- and the step from that run-time R to the instantiation: f(integral_constant<int, R>).
+static int pow2_ceil(int r) {
+  int p = 1;
+  while (p < r) p <<= 1;
+  return p;
+}
+static int list_regs(int k) { return pow2_ceil((k + 63) / 64); }
+template <class F>
+static auto with_list_regs(int R, F&& f) {
+  switch (R) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
 
 // Threshold filter + per-wave LDS queue in front of a WaveTopK.
 template <int R>
