@@ -586,6 +586,43 @@ int tpq_ivfflat_range_fill(const float* vectors, const float* query, const uint8
                            int64_t n_slots, int d, int nq, int max_nprobe, int metric, int n_split,
                            tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * FlatIndex fused exact search: the k best stored vectors of every query without a [nq][n_slots] similarity
+ * matrix -- a similarity GEMM on the fp32 matrix cores with a top-k epilogue (the semantics of the reference's
+ * TopkBMMCuda, torchpq/kernels/TopkBMMCuda.py, which FlatIndex itself does not use).
+ *
+ * vectors      f32 [d][n_slots]     FlatIndex._storage [d, capacity, 1] as it is; also IVFFlatIndex's vectors
+ * query        f32 [d][nq]          (pre-normalised by the host for "cosine")
+ * address2id   i64 [n_slots] or NULL   a slot is live iff its entry is >= 0; NULL: every slot is live
+ * out_vals     f32 [nq][k]          descending
+ * out_addr     i64 [nq][k]
+ * out_ids      i64 [nq][k] or NULL  address2id[out_addr] (-1 at the pads); only together with address2id
+ *
+ * Value of (query q, slot s): dot = sum_i x_q[i] y_s[i], |x_q|^2 and |y_s|^2 are ascending-dimension fp32 fmaf chains
+ * from 0.f (what v_mfma_f32_32x32x2_f32 computes; the arithmetic of tpq_ivfpq_coarse_probe's similarities):
+ *       TPQ_METRIC_NEG_SQ_L2:  v = 2.f*dot;  v = v - |x|^2;  v = v - |y|^2
+ *       TPQ_METRIC_INNER:      v = dot
+ * Output per query: the k best live slots by (value descending, address ascending) -- a strict total order, so the
+ * result does not depend on the order the slots are met in; a slot whose value is NaN never enters; a live slot
+ * whose value is -inf keeps its address and stands ahead of the pads; positions beyond the candidates are
+ * (-inf, -1, -1).  A query with a NaN or +-Inf component still returns: its own row is not pinned, every other row
+ * is what it is without it.
+ * 1 <= k <= 1024, any d >= 1, 1 <= n_parts <= 1024, else TPQ_ERR_INVALID_ARGUMENT; n_slots < 2^31 - 1, else
+ * TPQ_ERR_UNSUPPORTED.  nq == 0 or n_slots == 0 is TPQ_OK (no slots: all pads).
+ * n_parts: the contiguous slot ranges (of whole 256-slot chunks) a query's walk over the database is cut into, one
+ * workgroup per (128 queries, range), so that a small batch still fills the chip; the caller picks it from nq,
+ * n_slots and the CU count.  The result is the same bits for every n_parts, empty ranges included.
+ * workspace: tpq_flat_topk_workspace_bytes(nq, k, n_parts) bytes -- one sorted list of 64 R keys of 8 bytes per
+ * (query, range), R = 1, 2, 4, 8, 16 covering k; a function of (nq, k, n_parts) only: nothing of size nq x n_slots
+ * exists anywhere (0 for nq <= 0 or arguments out of range); too small: TPQ_ERR_WORKSPACE.  Two launches (tiles,
+ * then a merge that also gathers the ids), no global atomics, deterministic.  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+size_t tpq_flat_topk_workspace_bytes(int nq, int k, int n_parts);
+int tpq_flat_topk(const float* vectors, const float* query, const int64_t* address2id,
+                  float* out_vals, int64_t* out_addr, int64_t* out_ids,
+                  int64_t n_slots, int d, int nq, int k, int metric, int n_parts,
+                  void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("TPQ_AMD_LIB") or os.path.join(_HERE, "libtorchpq_amd.
 METRIC_NEG_SQ_L2 = 0
 METRIC_INNER = 1
 ERR_UNSUPPORTED = -4  # TPQ_ERR_UNSUPPORTED
+ERR_WORKSPACE = -3    # TPQ_ERR_WORKSPACE
 ASSIGN_ROUTE_AUTO = 0     # TPQ_ASSIGN_ROUTE_AUTO
 ASSIGN_ROUTE_CASCADE = 1  # TPQ_ASSIGN_ROUTE_CASCADE
 PROBE_ROUTE_AUTO, PROBE_ROUTE_FP32, PROBE_ROUTE_FP16 = 0, 1, 2  # TPQ_PROBE_ROUTE_*
@@ -99,6 +100,8 @@ SIGNATURES = {
     "tpq_ivfflat_range_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "tpq_ivfflat_range_fill": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i,
                                     _vp]),
+    "tpq_flat_topk_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tpq_flat_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ubench_stream_read": (_i, [_vp, _sz, _vp, _i, _vp]),
     "tpq_ubench_stream_read_ex": (_i, [_vp, _sz, _vp, _i, _i, _i, _sz, _i, _vp]),
     "tpq_ubench_rows_read": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp]),

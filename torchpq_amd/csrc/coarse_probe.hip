@@ -5,6 +5,7 @@
 #include "mfma_util.h"
 #include "probe_fast.h"
 #include "row_select.h"
+#include "sims_chunk.h"
 
 namespace tpq {
 
@@ -89,10 +90,6 @@ __global__ __launch_bounds__(kProbeSmallThreads) void probe_small_kernel(const f
 // of a search, not the scan.
 // x [d][nq], C [d][n_cells] -> sims [nq][n_cells], gmax [nq][ceil(n_cells/128)]
 // grid (ceil(nq/128), centroid-chunk groups)
-constexpr int kCsRows = 256;  // centroids per chunk (8 MFMA row tiles = 2 groups of 128)
-constexpr int kCsKC = 16;     // k rows per LDS slab
-constexpr int kCsSlab = kCsKC * kCsRows;
-
 __global__ __launch_bounds__(256, 2) void coarse_sims_kernel(const float* __restrict__ x,
                                                             const float* __restrict__ C,
                                                             float* __restrict__ sims, int d, int nq,
@@ -109,91 +106,14 @@ __global__ __launch_bounds__(256, 2) void coarse_sims_kernel(const float* __rest
   const float* __restrict__ xq = x + (qvalid ? q : 0);
   float* trw = tr + wave * 32 * 33;
 
-  float q2 = 0.f;  // |x_q|^2, one ascending-k chain, 16 loads in flight per step
-  {
-    const float* __restrict__ p = xq;
-    int k = 0;
-    for (; k + 16 <= d; k += 16) {
-      load_then_use<16>([&](int u) { return p[(int64_t)u * nq]; }, [&](int, float y) { q2 = fmaf(y, y, q2); });
-      p += 16 * (int64_t)nq;
-    }
-    for (; k < d; ++k) {
-      q2 = fmaf(*p, *p, q2);
-      p += nq;
-    }
-  }
+  const float q2 = sims_query_sq_norm(xq, d, nq);
 
-  const int n_slabs = (d + kCsKC - 1) / kCsKC;
   const int chunk0 = blockIdx.y * chunks_per_block;
   for (int ch = chunk0; ch < chunk0 + chunks_per_block; ++ch) {
     const int c0 = ch * kCsRows;
     if (c0 >= n_cells) break;
-    const int nc = (n_cells - c0) < kCsRows ? (n_cells - c0) : kCsRows;
-    const bool cv = (int)threadIdx.x < nc;  // this thread's centroid row of the chunk exists
-    const float* __restrict__ Cc = C + c0 + (cv ? (int)threadIdx.x : 0);
-    float rs[kCsKC], yc[kCsKC / 2], yn[kCsKC / 2];
-    float csq = 0.f;
-    auto load_slab = [&](int kb) {
-      const float* __restrict__ p = Cc + (int64_t)kb * n_cells;
-#pragma unroll
-      for (int u = 0; u < kCsKC; ++u) {
-        rs[u] = (cv && kb + u < d) ? *p : 0.f;
-        p += n_cells;
-      }
-    };
-    auto square_slab = [&]() {
-#pragma unroll
-      for (int u = 0; u < kCsKC; ++u) csq = fmaf(rs[u], rs[u], csq);
-    };
-    auto store_slab = [&](float* dst) {
-#pragma unroll
-      for (int u = 0; u < kCsKC; ++u) dst[u * kCsRows + threadIdx.x] = rs[u];
-    };
-    auto load_y = [&](int kb, float (&y)[kCsKC / 2]) {
-      const float* __restrict__ p = xq + (int64_t)(kb + half) * nq;
-#pragma unroll
-      for (int j = 0; j < kCsKC / 2; ++j) {
-        y[j] = (qvalid && kb + 2 * j + half < d) ? *p : 0.f;
-        p += 2 * (int64_t)nq;
-      }
-    };
-    load_slab(0);
-    load_y(0, yc);
-    __syncthreads();  // every wave finished the previous chunk (reads of cs and c2s)
-    square_slab();
-    // (rows past the last centroid get |C|^2 = +inf: their sims come out as -inf and drop out of
-    // the group maxima without a per-element predicate)
-    if (n_slabs == 1) c2s[threadIdx.x] = cv ? csq : INFINITY;
-    store_slab(cs);
     f32x16 acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    __syncthreads();
-    for (int sb = 0; sb < n_slabs; ++sb) {
-      const float* cur = cs + (sb & 1) * kCsSlab;
-      const bool more = sb + 1 < n_slabs;
-      if (more) {
-        load_slab((sb + 1) * kCsKC);
-        load_y((sb + 1) * kCsKC, yn);
-      }
-#pragma unroll
-      for (int j = 0; j < kCsKC / 2; ++j) {
-        const float* crow = cur + (2 * j + half) * kCsRows + l31;  // A operand [row=centroid][k]
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(crow[t * 32], yc[j], acc[t], 0, 0, 0);
-      }
-      if (more) {
-        square_slab();
-        if (sb + 2 == n_slabs) c2s[threadIdx.x] = cv ? csq : INFINITY;
-        store_slab(cs + ((sb + 1) & 1) * kCsSlab);
-#pragma unroll
-        for (int j = 0; j < kCsKC / 2; ++j) yc[j] = yn[j];
-      }
-      __syncthreads();
-    }
+    sims_chunk_mfma(xq, qvalid, C, c0, d, nq, n_cells, cs, c2s, acc, [](bool) {});
     // epilogue: acc[t][r] = (centroid row cl(t, r, half), query column l31)
     float gm[2] = {-INFINITY, -INFINITY};
     const int nq_w = nq - qw;  // queries of this wave that exist (may be <= 0)
@@ -201,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void coarse_sims_kernel(const float* __rest
     for (int t = 0; t < 8; ++t) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int cl = (r & 3) + 8 * (r >> 2) + 4 * half;   // row inside the tile
+        const int cl = sims_tile_row(r, half);
         const float v = neg_sq_l2(acc[t][r], q2, c2s[t * 32 + cl]);
         gm[t >> 2] = fmaxf(gm[t >> 2], v);
         trw[l31 * 33 + cl] = v;                              // [query][centroid]

@@ -2,7 +2,8 @@
 over container/FlatContainer.py).  SURVEY 8(f) rank 4: the ground-truth generator for recall.
 
 search = one library GEMM (rocBLAS, as the reference uses cuBLAS) + the HIP row top-k select
-(tpq_topk_select) + address->id.  Storage is the reference's dense `_storage [d, capacity, 1]`
+(tpq_topk_select) + address->id; with `use_fused_search = True` one fused HIP similarity + top-k
+(tpq_flat_topk) that never forms the [n_query, capacity] matrix.  Storage is the reference's dense `_storage [d, capacity, 1]`
 with `_address2id`; vectors are appended, removed slots are tombstoned (id -1) and reused.
 """
 import torch
@@ -10,9 +11,20 @@ import torch
 from .. import metric, util
 from ..container.BaseContainer import BaseContainer
 from ..fn import Topk
+from ..kernels import FlatTopkHip
 
 
 class FlatIndex(BaseContainer):
+    # Opt-in route of search(): tpq_flat_topk on _storage and _address2id, O(n_query k) temporary memory at any
+    # capacity, queries in batches of max_query_batch.  It ranks by the same similarity as the default route for every
+    # distance ("cosine": queries AND stored vectors divided by their norms, the latter in a [d, capacity] temporary per
+    # call); the values are the fp32-MFMA chains of include/torchpq_amd.h where the default route's are the library
+    # GEMM's, so low bits differ.  The kernel's limit is min(k, capacity) <= 1024: beyond it search() raises ValueError
+    # (the default route has no such limit).  Plain attributes, not constructor arguments (the signature is the
+    # reference's) and not part of the state_dict.
+    use_fused_search = False
+    max_query_batch = 32768
+
     def __init__(self, d_vector, initial_size=None, expand_step_size=1024, expand_mode="double",
                  device="cuda:0", distance="euclidean", verbose=0):
         super().__init__(device=device, initial_size=initial_size, expand_step_size=expand_step_size,
@@ -36,6 +48,7 @@ class FlatIndex(BaseContainer):
         self.register_buffer("_storage", torch.zeros(d_vector, self.initial_size, 1, device=device,
                                                      dtype=torch.float32))
         self._topk = Topk()
+        self._flat_topk = FlatTopkHip()
 
     @property
     def n_items(self):
@@ -105,6 +118,8 @@ class FlatIndex(BaseContainer):
         assert util.check_dtype(x, "float32")
         assert k >= 1
         x = x.to(self.device)
+        if self.use_fused_search:
+            return self._search_fused(x, k, return_address)
         storage = self._storage.view(self.d_vector, -1)
         if self.distance == "euclidean":
             sims = metric.negative_squared_l2_distance(x, storage)
@@ -116,6 +131,34 @@ class FlatIndex(BaseContainer):
         topk_val, topk_address = self._topk(sims, k=min(k, sims.shape[1]), dim=1)
         topk_address = torch.where(torch.isneginf(topk_val), torch.full_like(topk_address, -1), topk_address)
         topk_ids = self.get_id_by_address(topk_address)
+        if return_address:
+            return topk_val, topk_ids, topk_address
+        return topk_val, topk_ids
+
+    def _fused_vectors(self):
+        """what the fused kernel reads: _storage as it is, or for "cosine" a copy with every stored vector divided by
+        (its norm + 1e-8) -- metric.cosine_similarity's normalisation; [d, capacity], never n_query x capacity"""
+        if self.distance != "cosine":
+            return self._storage
+        storage = self._storage.view(self.d_vector, -1)
+        return (storage / (storage.norm(dim=-2, keepdim=True) + 1e-8)).contiguous()
+
+    def _search_fused(self, x, k, return_address):
+        """search() through tpq_flat_topk: the same conventions -- "cosine" divides queries and stored vectors by
+        (norm + 1e-8) as metric.cosine_similarity does, width min(k, capacity), pads (-inf, -1), ids gathered by the
+        same call"""
+        k = min(k, self.capacity)
+        if k > 1024:
+            raise ValueError(f"FlatIndex.use_fused_search: min(k, capacity) = {k} is beyond the fused kernel's limit "
+                             "of 1024; set use_fused_search = False for this call")
+        storage = self._fused_vectors()
+        if self.distance == "cosine":
+            x = x / (x.norm(dim=-2, keepdim=True) + 1e-8)
+        x = x.contiguous()
+        parts = [self._flat_topk(storage, x[:, b:b + self.max_query_batch].contiguous(), k,
+                                 address2id=self._address2id, distance=self.distance)
+                 for b in range(0, max(x.shape[1], 1), self.max_query_batch)]
+        topk_val, topk_address, topk_ids = parts[0] if len(parts) == 1 else (torch.cat(t, dim=0) for t in zip(*parts))
         if return_address:
             return topk_val, topk_ids, topk_address
         return topk_val, topk_ids

@@ -5,12 +5,13 @@ same call signature and argument meaning, same asserts, outputs allocated with t
 owned by the caller, launches asynchronous on the CURRENT torch stream, never synchronising.
 There is no CPU path: tensors must live on the GPU.
 
-One module per subsystem -- scan.py, coarse.py, kmeans.py, container.py; what they share is in _common.py.
+One module per subsystem -- scan.py, coarse.py, kmeans.py, container.py, flat.py; what they share is in _common.py.
 """
 from .coarse import (CoarseProbeHip, CoarseSelectHip, SmartProbingHip, Top1SelectHip, Top32SelectHip,
                      TopkSelectHip)
 from .container import (GetAddressByIdHip, GetCellByAddressHip, GetIdByAddressHip, GetIOAHip,
                         GetWriteAddressHip, GrowCellsHip, PackCodesHip, PQDecodeHip, ScatterCodesHip)
+from .flat import FlatTopkHip
 from .kmeans import ComputeCentroidsHip, CoarseAssignHip, LloydStepHip, MaxSimHip, MaxSimSelectHip
 from .scan import (PACKED_M, AdcLutHip, IVFFlatRangeHip, IVFFlatTopkHip, IVFPQRerankHip, IVFPQTop1Hip, IVFPQTopkHip,
                    ResidualPart1Hip, ResidualSlotTermsHip, packed_chunk_width)
@@ -19,5 +20,5 @@ __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "CoarseAssignHip", "MaxSimSelectHip", "LloydStepHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "packed_chunk_width", "PACKED_M",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "FlatTopkHip", "packed_chunk_width", "PACKED_M",
 ]
