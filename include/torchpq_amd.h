@@ -623,6 +623,45 @@ int tpq_flat_topk(const float* vectors, const float* query, const int64_t* addre
                   int64_t n_slots, int d, int nq, int k, int metric, int n_parts,
                   void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * FlatIndex range search: every live stored vector whose value reaches a threshold, over the whole database (no
+ * reference counterpart) -- the similarity tiles of tpq_flat_topk with a count and a fill epilogue.  vectors, query,
+ * address2id, n_slots, d, nq, metric and n_parts are those of tpq_flat_topk.
+ *
+ * Value      of (query q, slot s): exactly the value tpq_flat_topk defines (the same code, the same bits), -0.0
+ *            returned as +0.0.
+ * Hit        a slot below n_slots that is live (address2id NULL, or address2id[s] >= 0) with value >= threshold[q]
+ *            (threshold f32 [nq]).  A NaN value is never a hit, a NaN threshold gives no hits, -inf gives every live
+ *            slot whose value is not NaN -- a live slot whose value is -inf included.
+ * Order      address ascending, for every n_parts.
+ * Output     lims i64 [nq + 1], lims[0] = 0: the hits of query q are out_vals[lims[q] : lims[q+1]] (f32),
+ *            out_addr[lims[q] : lims[q+1]] (i64) and, where out_ids is given (only together with address2id),
+ *            out_ids[lims[q] : lims[q+1]] = address2id[out_addr] (i64).
+ * A query with a NaN or +-Inf component returns what this definition gives (usually nothing) and touches no
+ * other query's segment.
+ *
+ * Two passes, no global atomics, no sort, deterministic.  A query's walk is cut into n_parts ranges of whole
+ * 256-slot chunks as in tpq_flat_topk, one workgroup per (128 queries, range): segment q * n_parts + part.
+ *   1. tpq_flat_range_count writes the hits of every segment: counts i32 [tpq_flat_range_segments(nq, n_parts)]
+ *      (= nq * n_parts; 0 for nq <= 0 or n_parts outside [1, 1024]), empty ranges and n_slots == 0 included (0).
+ *   2. THE CALLER turns the counts into exclusive prefix sums: offsets i64 [segments + 1], offsets[0] = 0, the last
+ *      entry the total number of hits, which sizes out_vals / out_addr / out_ids; lims[q] = offsets[q * n_parts].
+ *      The library does not do this step and allocates nothing.
+ *   3. tpq_flat_range_fill, with the inputs of the count pass, computes the values again and stores segment s at
+ *      offsets[s] onwards.  Nothing is stored at or beyond offsets[s + 1], whatever is found: inputs that changed
+ *      between the passes lose hits, they do not become a store outside the segment.  A workgroup whose 128
+ *      segments are all empty does not walk its range again.
+ * Temporary memory is the counts and offsets: nothing of size nq x n_slots exists anywhere.
+ * any d >= 1, 1 <= n_parts <= 1024, else TPQ_ERR_INVALID_ARGUMENT; n_slots < 2^31 - 1, else TPQ_ERR_UNSUPPORTED.
+ * nq == 0 is TPQ_OK.
+ * ------------------------------------------------------------------------- */
+size_t tpq_flat_range_segments(int nq, int n_parts);
+int tpq_flat_range_count(const float* vectors, const float* query, const int64_t* address2id, const float* threshold,
+                         int32_t* counts, int64_t n_slots, int d, int nq, int metric, int n_parts, tpq_stream_t stream);
+int tpq_flat_range_fill(const float* vectors, const float* query, const int64_t* address2id, const float* threshold,
+                        const int64_t* offsets, float* out_vals, int64_t* out_addr, int64_t* out_ids,
+                        int64_t n_slots, int d, int nq, int metric, int n_parts, tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

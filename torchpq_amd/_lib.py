@@ -102,6 +102,9 @@ SIGNATURES = {
                                     _vp]),
     "tpq_flat_topk_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_flat_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tpq_flat_range_segments": (_sz, [_i, _i]),
+    "tpq_flat_range_count": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "tpq_flat_range_fill": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "tpq_ubench_stream_read": (_i, [_vp, _sz, _vp, _i, _vp]),
     "tpq_ubench_stream_read_ex": (_i, [_vp, _sz, _vp, _i, _i, _i, _sz, _i, _vp]),
     "tpq_ubench_rows_read": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp]),

@@ -6,8 +6,8 @@
 # rebuilds the four cascade units (cascade_core, assign_cascade, probe_sims, lloyd) and assign_fast; row_select.h (the
 # row select's device code) rebuilds select, coarse_probe and probe_sims; probe_fast.h rebuilds coarse_probe and
 # probe_sims; mfma_util.h (the MFMA units' shared device helpers) rebuilds the cascade units, assign_fast, coarse_probe,
-# max_sim, centroid_update, kmeans_split, lut and flat_topk; sims_chunk.h (the fp32 similarity tile) rebuilds coarse_probe
-# and flat_topk.  The exact assign (max_sim.hip) and the centroid update
+# max_sim, centroid_update, kmeans_split, lut, flat_topk and flat_range; sims_chunk.h (the fp32 similarity tile) rebuilds
+# coarse_probe, flat_topk and flat_range.  The exact assign (max_sim.hip) and the centroid update
 # (centroid_update.hip) are units of their own: a change to one does not recompile the other.
 # The library is linked from the objects of the unit list below, not from whatever build/ holds: an object left
 # behind by a unit that has since been renamed or split would define its symbols a second time.
@@ -43,7 +43,7 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_flat.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_flat.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   if stale "$obj" "${HERE}/${src}"; then

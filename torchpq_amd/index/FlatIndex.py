@@ -3,7 +3,8 @@ over container/FlatContainer.py).  SURVEY 8(f) rank 4: the ground-truth generato
 
 search = one library GEMM (rocBLAS, as the reference uses cuBLAS) + the HIP row top-k select
 (tpq_topk_select) + address->id; with `use_fused_search = True` one fused HIP similarity + top-k
-(tpq_flat_topk) that never forms the [n_query, capacity] matrix.  Storage is the reference's dense `_storage [d, capacity, 1]`
+(tpq_flat_topk) that never forms the [n_query, capacity] matrix.  range_search = the same HIP similarity tiles with a
+count and a fill pass (tpq_flat_range_count / tpq_flat_range_fill).  Storage is the reference's dense `_storage [d, capacity, 1]`
 with `_address2id`; vectors are appended, removed slots are tombstoned (id -1) and reused.
 """
 import torch
@@ -11,7 +12,8 @@ import torch
 from .. import metric, util
 from ..container.BaseContainer import BaseContainer
 from ..fn import Topk
-from ..kernels import FlatTopkHip
+from ..kernels import FlatRangeHip, FlatTopkHip
+from ._range import sort_range_hits
 
 
 class FlatIndex(BaseContainer):
@@ -49,6 +51,7 @@ class FlatIndex(BaseContainer):
                                                      dtype=torch.float32))
         self._topk = Topk()
         self._flat_topk = FlatTopkHip()
+        self._flat_range = FlatRangeHip()
 
     @property
     def n_items(self):
@@ -162,3 +165,44 @@ class FlatIndex(BaseContainer):
         if return_address:
             return topk_val, topk_ids, topk_address
         return topk_val, topk_ids
+
+    def range_search(self, x, threshold, return_address=False, sort=False):
+        """x [d_vector, n_query] f32, threshold a float or f32 [n_query] -> (lims int64 [n_query + 1], values f32
+        [total], ids int64 [total][, address]): the hits of query q are values[lims[q]:lims[q+1]] and
+        ids[lims[q]:lims[q+1]] -- every stored vector whose value is >= threshold, exactly: the whole database is
+        walked.  `threshold` is in the index's value space, the one search returns: -squared-L2 for "euclidean" (all
+        vectors within distance r: threshold = -r * r), the cosine similarity for "cosine".  Hits come in address
+        order; sort=True orders each query's hits by value descending, equal values by address ascending.  Always the
+        HIP route (tpq_flat_range_count / tpq_flat_range_fill; values as use_fused_search's), O(n_query) temporary
+        memory beside the hits.  Synchronises once per batch of `max_query_batch` queries: the number of hits sizes
+        the outputs."""
+        d_vector, n_query = x.shape
+        assert d_vector == self.d_vector
+        assert util.check_dtype(x, "float32")
+        x = x.to(self.device)
+        if torch.is_tensor(threshold):
+            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+            threshold = threshold.to(self.device)
+        storage = self._fused_vectors()
+        if self.distance == "cosine":
+            x = x / (x.norm(dim=-2, keepdim=True) + 1e-8)
+        lims = [torch.zeros(1, device=self.device, dtype=torch.int64)]
+        vals, ids, address, total = [], [], [], 0
+        for q0 in range(0, n_query, self.max_query_batch):
+            thr = threshold[q0:q0 + self.max_query_batch] if torch.is_tensor(threshold) else threshold
+            lb, vb, ab, ib = self._flat_range(storage, x[:, q0:q0 + self.max_query_batch].contiguous(), thr,
+                                              address2id=self._address2id, distance=self.distance)
+            lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
+            vals.append(vb)
+            ids.append(ib)
+            address.append(ab)
+            total += vb.numel()
+        lims = torch.cat(lims)
+        if vals:
+            vals, ids, address = torch.cat(vals), torch.cat(ids), torch.cat(address)
+        else:
+            vals = torch.empty(0, device=self.device, dtype=torch.float32)
+            ids, address = (torch.empty(0, device=self.device, dtype=torch.int64) for _ in range(2))
+        if sort:
+            vals, ids, address = sort_range_hits(lims, vals, ids, address)
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)

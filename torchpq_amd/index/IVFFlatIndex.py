@@ -13,6 +13,7 @@ import torch
 from ..container import CellContainer
 from ..kernels import IVFFlatRangeHip, IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
+from ._range import sort_range_hits
 
 
 class IVFFlatIndex(CoarseProbeMixin, CellContainer):
@@ -164,12 +165,6 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         else:
             vals = torch.empty(0, device=self.device, dtype=torch.float32)
             ids = address = torch.empty(0, device=self.device, dtype=torch.int64)
-        if sort and total:
-            # three stable sorts, least significant key first: address, value (descending), query
-            order = torch.argsort(address, stable=True)
-            order = order[torch.argsort(vals[order], descending=True, stable=True)]
-            query_of = torch.repeat_interleave(torch.arange(n_query, device=self.device), lims.diff(),
-                                               output_size=total)
-            order = order[torch.argsort(query_of[order], stable=True)]
-            vals, ids, address = vals[order], ids[order], address[order]
+        if sort:
+            vals, ids, address = sort_range_hits(lims, vals, ids, address)
         return (lims, vals, ids, address) if return_address else (lims, vals, ids)

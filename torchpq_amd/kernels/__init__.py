@@ -11,7 +11,7 @@ from .coarse import (CoarseProbeHip, CoarseSelectHip, SmartProbingHip, Top1Selec
                      TopkSelectHip)
 from .container import (GetAddressByIdHip, GetCellByAddressHip, GetIdByAddressHip, GetIOAHip,
                         GetWriteAddressHip, GrowCellsHip, PackCodesHip, PQDecodeHip, ScatterCodesHip)
-from .flat import FlatTopkHip
+from .flat import FlatRangeHip, FlatTopkHip
 from .kmeans import ComputeCentroidsHip, CoarseAssignHip, LloydStepHip, MaxSimHip, MaxSimSelectHip
 from .scan import (PACKED_M, AdcLutHip, IVFFlatRangeHip, IVFFlatTopkHip, IVFPQRerankHip, IVFPQTop1Hip, IVFPQTopkHip,
                    ResidualPart1Hip, ResidualSlotTermsHip, packed_chunk_width)
@@ -20,5 +20,5 @@ __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "CoarseAssignHip", "MaxSimSelectHip", "LloydStepHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "FlatTopkHip", "packed_chunk_width", "PACKED_M",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "FlatTopkHip", "FlatRangeHip", "packed_chunk_width", "PACKED_M",
 ]
