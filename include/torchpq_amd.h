@@ -587,6 +587,78 @@ int tpq_ivfflat_range_fill(const float* vectors, const float* query, const uint8
                            tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQIndex range search: every stored code of the probed cells whose ADC value reaches a threshold (no
+ * reference counterpart).  codes, is_empty, cell_start, cell_size, n_probe_list, n_slots, nq, max_nprobe, m and
+ * n_split are those of tpq_ivfpq_scan_topk; the scan reads the reference layout, codes u8 [m/4][n_slots][4].
+ *
+ * Candidates of a query: those of tpq_ivfpq_scan_topk -- its first n_probe_list[q] probes (clamped to
+ *            [0, max_nprobe]), a probe whose start equals the previous probe's start skipped, the slots inside
+ *            [start, start + size) and inside [0, n_slots) (a cell that leaves the storage is cut) that are not
+ *            tombstoned (is_empty).
+ * Value      plain PQ: v = 0.f; for j = 0..m-1 ascending: v += lut[j][q][code_j], one fp32 add per step -- the value
+ *            of tpq_ivfpq_scan_topk.  The table is either `lut` f32 [m][nq][256] (tpq_adc_lut's output) or, when
+ *            lut == NULL, built in the workgroup from query f32 [m*ds][nq], codebook f32 [m][ds][256], ds and
+ *            metric, as tpq_ivfpq_search_fused does: bit-identical entries.
+ *            residual PQ: the value of tpq_ivfpq_scan_topk_residual -- v = base_sims[q][p], then v += LUT_p[j][code_j]
+ *            for j ascending, with LUT_p[j][c] = part1[q][j][c] + part2[cells[q][p]][j][c] (one fp32 add per entry),
+ *            or LUT_p = full_lut[q][p] when full_lut is given; when part1 == NULL (and full_lut == NULL) part1 is
+ *            built in the workgroup from query and codebook (2 q_j . r_jc, the entries of tpq_residual_part1).  The
+ *            value stored is v + 0.0f, as in the top-k scan: a range hit and a top-k result of one slot carry the
+ *            same bits.
+ * Hit        a candidate with value >= threshold[q] (threshold f32 [nq]).  A NaN value is never a hit, a NaN
+ *            threshold gives no hits, -inf gives every candidate whose value is not NaN.
+ * Order      scan order: probe rank ascending, then address ascending; a slot of two overlapping cells appears
+ *            twice.  Neither the order nor the bits depend on how the work is cut (n_split).
+ * Output     lims i64 [nq + 1], lims[0] = 0: the hits of query q are out_vals[lims[q] : lims[q+1]] (f32) and
+ *            out_addr[lims[q] : lims[q+1]] (i64).
+ * A query with a NaN or +-Inf component returns what this definition gives and touches no other query's segment.
+ *
+ * Two passes, no global atomics, no sort, deterministic -- the protocol of tpq_ivfflat_range_count / _fill.
+ *   plain     a query's tiles are cut into n_split parts as in the top-k scan, a part's tiles into eight contiguous
+ *             chunks, one per wave: segment (q * n_split + part) * 8 + wave; tpq_ivfpq_range_segments(nq, n_split)
+ *             = nq * n_split * 8 segments (0 for nq <= 0 or n_split outside [1, 1024]).
+ *   residual  the table depends on the probed cell: one workgroup per (query, probe rank), the cell's tiles in eight
+ *             contiguous chunks: segment (q * max_nprobe + p) * 8 + wave; tpq_ivfpq_range_residual_segments(nq,
+ *             max_nprobe) = nq * max_nprobe * 8 segments (0 for nq <= 0 or max_nprobe < 1).  A probe that is not
+ *             scanned has eight zero counts.
+ *   1. the count pass writes the hits of every segment: wave_counts i32 [segments].
+ *   2. THE CALLER turns the counts into exclusive prefix sums: wave_offsets i64 [segments + 1], wave_offsets[0] = 0,
+ *      the last entry the total number of hits, which sizes out_vals / out_addr; lims[q] = wave_offsets[q * (segments
+ *      / nq)].  The library does not do this step and allocates nothing.
+ *   3. the fill pass, with the inputs of the count pass, computes the values again (the same code, the same bits)
+ *      and stores segment s at wave_offsets[s] onwards.  A wave stores nothing at or beyond wave_offsets[s + 1],
+ *      whatever it finds: inputs that changed between the passes lose hits, they do not become a store outside the
+ *      segment.  A segment without hits is not scanned again, a workgroup without hits stages no table.
+ * m % 4 == 0 and 1 <= n_split <= 1024, else TPQ_ERR_INVALID_ARGUMENT; n_slots < 2^31 - 1 and the workgroup's LDS
+ * (m KiB of table, the staged query when the table is built there, the probe table) <= 160 KiB -- m <= 156 -- else
+ * TPQ_ERR_UNSUPPORTED.  nq == 0 is TPQ_OK.  Every check comes before the first HIP call.  There is no scan-layout
+ * ("packed") route: the range scan reads `codes` whatever the index keeps for its top-k search.
+ * ------------------------------------------------------------------------- */
+size_t tpq_ivfpq_range_segments(int nq, int n_split);
+int tpq_ivfpq_range_count(const uint8_t* codes, const float* lut, const float* query, const float* codebook, int ds,
+                          int metric, const uint8_t* is_empty, const int64_t* cell_start, const int64_t* cell_size,
+                          const int64_t* n_probe_list, const float* threshold, int32_t* wave_counts, int64_t n_slots,
+                          int nq, int max_nprobe, int m, int n_split, tpq_stream_t stream);
+int tpq_ivfpq_range_fill(const uint8_t* codes, const float* lut, const float* query, const float* codebook, int ds,
+                         int metric, const uint8_t* is_empty, const int64_t* cell_start, const int64_t* cell_size,
+                         const int64_t* n_probe_list, const float* threshold, const int64_t* wave_offsets,
+                         float* out_vals, int64_t* out_addr, int64_t n_slots, int nq, int max_nprobe, int m,
+                         int n_split, tpq_stream_t stream);
+size_t tpq_ivfpq_range_residual_segments(int nq, int max_nprobe);
+int tpq_ivfpq_range_residual_count(const uint8_t* codes, const float* part1, const float* query,
+                                   const float* codebook, int ds, const float* part2, const float* full_lut,
+                                   const int64_t* cells, const float* base_sims, const uint8_t* is_empty,
+                                   const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                   const float* threshold, int32_t* wave_counts, int64_t n_slots, int nq,
+                                   int max_nprobe, int m, tpq_stream_t stream);
+int tpq_ivfpq_range_residual_fill(const uint8_t* codes, const float* part1, const float* query, const float* codebook,
+                                  int ds, const float* part2, const float* full_lut, const int64_t* cells,
+                                  const float* base_sims, const uint8_t* is_empty, const int64_t* cell_start,
+                                  const int64_t* cell_size, const int64_t* n_probe_list, const float* threshold,
+                                  const int64_t* wave_offsets, float* out_vals, int64_t* out_addr, int64_t n_slots,
+                                  int nq, int max_nprobe, int m, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FlatIndex fused exact search: the k best stored vectors of every query without a [nq][n_slots] similarity
  * matrix -- a similarity GEMM on the fp32 matrix cores with a top-k epilogue (the semantics of the reference's
  * TopkBMMCuda, torchpq/kernels/TopkBMMCuda.py, which FlatIndex itself does not use).

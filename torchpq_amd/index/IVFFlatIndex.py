@@ -13,7 +13,7 @@ import torch
 from ..container import CellContainer
 from ..kernels import IVFFlatRangeHip, IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
-from ._range import sort_range_hits
+from ._range import range_search_batches
 
 
 class IVFFlatIndex(CoarseProbeMixin, CellContainer):
@@ -142,29 +142,6 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         x = self._prepare(x)
         assert self.vq_codec.is_trained, "index is not trained"
         assert 1 <= self.n_probe <= self.n_cells
-        n_query = x.shape[1]
-        if torch.is_tensor(threshold):
-            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
-            threshold = threshold.to(self.device)
-        lims = [torch.zeros(1, device=self.device, dtype=torch.int64)]
-        vals, ids, address, total = [], [], [], 0
-        for q0 in range(0, n_query, self.max_query_batch):
-            xb = x[:, q0:q0 + self.max_query_batch].contiguous()
-            thr = threshold[q0:q0 + self.max_query_batch] if torch.is_tensor(threshold) else threshold
-            _, cells, n_probe_list, extents = self._probe_with_extents(xb)
-            lb, vb, ib, ab = self.range_search_cells(xb, cells, thr, n_probe_list, return_address=True,
-                                                     _extents=extents)
-            lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
-            vals.append(vb)
-            ids.append(ib)
-            address.append(ab)
-            total += vb.numel()
-        lims = torch.cat(lims)
-        if vals:
-            vals, ids, address = torch.cat(vals), torch.cat(ids), torch.cat(address)
-        else:
-            vals = torch.empty(0, device=self.device, dtype=torch.float32)
-            ids = address = torch.empty(0, device=self.device, dtype=torch.int64)
-        if sort:
-            vals, ids, address = sort_range_hits(lims, vals, ids, address)
-        return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+        return range_search_batches(
+            self, x, threshold, lambda xb, thr, sims, cells, n_probe_list, extents: self.range_search_cells(
+                xb, cells, thr, n_probe_list, return_address=True, _extents=extents), return_address, sort)

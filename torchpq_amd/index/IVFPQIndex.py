@@ -12,8 +12,9 @@ from .. import util
 from ..codec import PQCodec
 from ..container import CellContainer
 from ..fn import IVFPQTopk
-from ..kernels import PACKED_M, ResidualPart1Hip, ResidualSlotTermsHip
+from ..kernels import PACKED_M, IVFPQRangeHip, ResidualPart1Hip, ResidualSlotTermsHip
 from ._coarse import CoarseProbeMixin
+from ._range import range_search_batches
 
 
 class IVFPQIndex(CoarseProbeMixin, CellContainer):
@@ -64,6 +65,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         self.pq_codec = PQCodec(d_vector=d_vector, n_subvectors=n_subvectors, n_clusters=256,
                                 distance=distance, verbose=verbose)
         self._ivfpq_topk = IVFPQTopk(n_subvectors=n_subvectors, contiguous_size=self.contiguous_size)
+        self._ivfpq_range = IVFPQRangeHip(m=n_subvectors)
         self.to(device)
 
     # ---- knobs (reference :89-232) ---------------------------------------------------------------
@@ -310,3 +312,55 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         return self._search_batches(x, lambda xb, sims, cells, n_probe_list, extents: self.search_cells(
             x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=False,
             _extents=extents))
+
+    # ---- range search ------------------------------------------------------------------------------
+    def range_search_cells(self, x, cells, threshold, base_sims=None, n_probe_list=None, return_address=False,
+                           _extents=None):
+        """Every live code of the given cells [n_query, n_probe] whose value is >= `threshold` (a float, or f32
+        [n_query]); (lims, values, ids[, address]) in scan order, see range_search.  The tables are those search_cells
+        would use; the codes are read in the container's own layout (`_scan_codes()`), never the scan-layout copy.
+        (`_extents` as in search_cells.)"""
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        lists = dict(data=self._scan_codes(), cell_start=cell_start.contiguous(), cell_size=cell_size.contiguous(),
+                     n_probe_list=n_probe_list, threshold=threshold, is_empty=is_empty)
+        fused = self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector
+        if self.pq_use_residual:
+            assert base_sims is not None, "base_sims is required when pq_use_residual is True"
+            if self.use_precomputed:
+                if self._precomputed_part2 is None:
+                    self.precompute_part2()
+                tables = dict(part2=self._part2_by_cell, cells=cells)
+                if fused:
+                    tables.update(query=x, codebook=self.pq_codec.codebook)
+                else:
+                    tables.update(part1=ResidualPart1Hip()(x, self.pq_codec.codebook))
+            else:
+                tables = dict(full=self.precomputed_adc_residual(x, cells))
+            lims, vals, address = self._ivfpq_range.residual(base_sims=base_sims, **tables, **lists)
+        elif fused:
+            lims, vals, address = self._ivfpq_range(query=x, codebook=self.pq_codec.codebook, distance=self.distance,
+                                                    slots_hint=slots_hint, **lists)
+        else:
+            lims, vals, address = self._ivfpq_range(precomputed=self.pq_codec.precompute_adc(x),
+                                                    slots_hint=slots_hint, **lists)
+        ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+
+    def range_search(self, x, threshold, return_address=False, sort=False):
+        """x [d_vector, n_query] f32, threshold a float or f32 [n_query] -> (lims int64 [n_query + 1], values f32
+        [total], ids int64 [total][, address]): the hits of query q are values[lims[q]:lims[q+1]] and
+        ids[lims[q]:lims[q+1]] -- every stored code of the query's probed cells (`n_probe`, as in search) whose value is
+        >= threshold.  `threshold` is in the index's value space, the one search returns: -squared-L2 to the PQ
+        reconstruction for "euclidean" (everything within distance r: threshold = -r * r), the cosine similarity of
+        the reconstruction for "cosine".  A hit carries the bits search returns for the same slot.
+        Hits come in scan order (probe rank, then slot address); sort=True orders each query's hits by value
+        descending, equal values by address ascending.  Synchronises once per batch of `max_query_batch` queries:
+        the number of hits sizes the outputs."""
+        x = self._prepare(x)
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        return range_search_batches(
+            self, x, threshold, lambda xb, thr, sims, cells, n_probe_list, extents: self.range_search_cells(
+                xb, cells, thr, base_sims=sims, n_probe_list=n_probe_list, return_address=True, _extents=extents),
+            return_address, sort)

@@ -161,3 +161,15 @@ class IVFPQRIndex(IVFPQIndex):
 
         vals, ids, address = self._search_batches(x, per_batch)
         return (vals, ids, address) if return_address else (vals, ids)
+
+    # ---- range search ----------------------------------------------------------------------------------
+    def range_search_cells(self, x, cells, threshold, base_sims=None, n_probe_list=None, return_address=False,
+                           _extents=None):
+        raise NotImplementedError(
+            "IVFPQRIndex has no range search: the list scan's values are those of the first code, not the re-ranked "
+            "values search returns, so a threshold in this index's value space cannot be applied to them")
+
+    def range_search(self, x, threshold, return_address=False, sort=False):
+        raise NotImplementedError(
+            "IVFPQRIndex has no range search: the list scan's values are those of the first code, not the re-ranked "
+            "values search returns, so a threshold in this index's value space cannot be applied to them")

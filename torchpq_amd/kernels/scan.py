@@ -1,5 +1,5 @@
 """The list scans and what feeds them: IVFPQ top-k (plain, fused LUT, residual), the LUT and residual tables, the
-IVFPQR re-rank, the IVFFlat scan and range search."""
+IVFPQR re-rank, the IVFFlat scan and range search, the IVFPQ range search."""
 import torch
 
 from .._lib import check, load, ptr, require_gpu, stream_ptr
@@ -508,34 +508,173 @@ class IVFFlatRangeHip:
         if is_empty is not None:
             assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
         assert distance in ("euclidean", "cosine", "inner")
-        per_query = torch.is_tensor(threshold)
-        if per_query:
-            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
-            threshold = threshold.contiguous()
+        threshold = _checked_threshold(threshold, n_query)
         query = query.contiguous()
-        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list, threshold if per_query else None)
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list, _tensor_or_none(threshold))
         device = vectors.device
-        if not per_query:
-            threshold = torch.full((n_query,), float(threshold), device=device, dtype=torch.float32)
-        if n_query == 0:
-            return (torch.zeros(1, device=device, dtype=torch.int64),
-                    torch.empty(0, device=device, dtype=torch.float32),
-                    torch.empty(0, device=device, dtype=torch.int64))
-        if n_split is None:
-            n_split = self._n_split(n_query, device, slots_hint)
-        self.last_n_split = n_split
-        n_seg = load().tpq_ivfflat_range_segments(n_query, n_split)
-        assert n_seg == n_query * n_split * 8, (n_query, n_split)
-        inputs = (ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
-                  ptr(threshold))
-        shape = (n_slots, d, n_query, n_probe, metric_code(distance), n_split)
-        counts = torch.empty(n_seg, device=device, dtype=torch.int32)
-        call("tpq_ivfflat_range_count", device, *inputs, ptr(counts), *shape)
-        offsets = torch.zeros(n_seg + 1, device=device, dtype=torch.int64)
-        offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
-        total = int(offsets[-1].item())     # the host sync a variable-size output needs
-        values = torch.empty(total, device=device, dtype=torch.float32)
-        address = torch.empty(total, device=device, dtype=torch.int64)
-        if total:
-            call("tpq_ivfflat_range_fill", device, *inputs, ptr(offsets), ptr(values), ptr(address), *shape)
-        return offsets[::n_split * 8].contiguous(), values, address
+        inputs = (ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+
+        def passes():
+            split = self._n_split(n_query, device, slots_hint) if n_split is None else n_split
+            self.last_n_split = split
+            n_seg = load().tpq_ivfflat_range_segments(n_query, split)
+            assert n_seg == n_query * split * 8, (n_query, split)
+            shape = (n_slots, d, n_query, n_probe, metric_code(distance), split)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivfflat_range_count", device, *inputs, thr, counts, *shape),
+                    lambda thr, *out: call("tpq_ivfflat_range_fill", device, *inputs, thr, *out, *shape))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+
+class IVFPQRangeHip:
+    """Range search over the lists of IVFPQIndex (tpq_ivfpq_range_count / _fill and their residual forms,
+    csrc/scan_range.hip): every candidate of IVFPQTopkHip whose value is >= the query's threshold, in scan order, the
+    value being that of the exact reference-layout scan; the semantics are defined in include/torchpq_amd.h.  The scan
+    reads CellContainer._storage itself: there is no scan-layout route."""
+
+    def __init__(self, m=8):
+        assert m % 4 == 0
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
+
+    _n_split = IVFPQTopkHip._n_split
+
+    def _check_lists(self, data, is_empty, cell_start, cell_size, n_probe_list):
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert data.shape == (self.m // 4, n_data, 4) and data.dtype == torch.uint8
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_data,) and is_empty.dtype == torch.uint8
+        return n_data, n_query, n_probe
+
+    def _check_fused(self, query, codebook, n_query):
+        """(query, codebook, ds) of a table built in the workgroup"""
+        m, ds, kk = codebook.shape
+        assert m == self.m and kk == 256 and query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        return query.contiguous(), codebook.contiguous(), ds
+
+    def __call__(self, data, cell_start, cell_size, n_probe_list, threshold, precomputed=None, query=None,
+                 codebook=None, distance="euclidean", is_empty=None, n_split=None, slots_hint=None):
+        """Plain PQ.
+          data: [m // 4, n_data, 4] uint8 (CellContainer._storage)
+          precomputed: [m, n_query, 256] float32 (AdcLutHip), or None with query [d, n_query] and codebook
+                       [m, ds, 256] float32, from which the workgroup builds the same table (`distance` as AdcLutHip)
+          cell_start / cell_size: [n_query, max_n_probe] int64; n_probe_list: [n_query] int64
+          threshold: a Python float, or [n_query] float32 -- one per query
+          is_empty: [n_data] uint8, or None when no slot inside a cell is a tombstone
+        returns (lims [n_query + 1] int64, values [total] float32, address [total] int64): the hits of query q are
+        values[lims[q]:lims[q+1]] / address[lims[q]:lims[q+1]], probe rank ascending, then address ascending.
+        Synchronises once: the number of hits sizes the outputs.
+        """
+        n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
+        ds = 0
+        if precomputed is not None:
+            assert precomputed.shape == (self.m, n_query, 256) and precomputed.dtype == torch.float32
+            precomputed, query, codebook = precomputed.contiguous(), None, None
+        else:
+            assert query is not None and codebook is not None
+            query, codebook, ds = self._check_fused(query, codebook, n_query)
+        assert distance in ("euclidean", "cosine", "inner")
+        threshold = _checked_threshold(threshold, n_query)
+        require_gpu(data, precomputed, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                    _tensor_or_none(threshold))
+        device = data.device
+        inputs = (ptr(data), ptr(precomputed), ptr(query), ptr(codebook), ds, metric_code(distance), ptr(is_empty),
+                  ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+
+        def passes():
+            split = self._n_split(n_query, device, slots_hint) if n_split is None else n_split
+            self.last_n_split = split
+            n_seg = load().tpq_ivfpq_range_segments(n_query, split)
+            assert n_seg == n_query * split * 8, (n_query, split)
+            shape = (n_data, n_query, n_probe, self.m, split)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivfpq_range_count", device, *inputs, thr, counts, *shape),
+                    lambda thr, *out: call("tpq_ivfpq_range_fill", device, *inputs, thr, *out, *shape))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+    def residual(self, data, base_sims, cell_start, cell_size, n_probe_list, threshold, part1=None, part2=None,
+                 cells=None, full=None, query=None, codebook=None, is_empty=None):
+        """Residual PQ: the value of IVFPQTopkHip.topk_residual_precomputed / topk_residual.
+          base_sims: [n_query, max_n_probe] float32
+          either full [n_query, max_n_probe, m, 256] float32 -- one table per (query, probe) --
+          or part2 [n_cells, m, 256] float32 and cells [n_query, max_n_probe] int64 with part1 [n_query, m, 256]
+          float32 (ResidualPart1Hip) or, instead of part1, query [d, n_query] and codebook [m, ds, 256] float32, from
+          which the workgroup builds it
+          everything else, and the result, as __call__; one workgroup per (query, probe): there is no n_split
+        """
+        n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
+        assert base_sims.shape == (n_query, n_probe) and base_sims.dtype == torch.float32
+        base_sims = base_sims.contiguous()
+        ds = 0
+        if full is not None:
+            assert full.shape == (n_query, n_probe, self.m, 256) and full.dtype == torch.float32
+            full, part1, part2, cells, query, codebook = full.contiguous(), None, None, None, None, None
+        else:
+            assert part2 is not None and cells is not None
+            assert part2.shape[1:] == (self.m, 256) and part2.dtype == torch.float32
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+            part2, cells = part2.contiguous(), cells.contiguous()
+            if part1 is not None:
+                assert part1.shape == (n_query, self.m, 256) and part1.dtype == torch.float32
+                part1, query, codebook = part1.contiguous(), None, None
+            else:
+                assert query is not None and codebook is not None
+                query, codebook, ds = self._check_fused(query, codebook, n_query)
+        threshold = _checked_threshold(threshold, n_query)
+        require_gpu(data, part1, query, codebook, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
+                    n_probe_list, _tensor_or_none(threshold))
+        device = data.device
+        inputs = (ptr(data), ptr(part1), ptr(query), ptr(codebook), ds, ptr(part2), ptr(full), ptr(cells),
+                  ptr(base_sims), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+
+        def passes():
+            n_seg = load().tpq_ivfpq_range_residual_segments(n_query, n_probe)
+            assert n_seg == n_query * n_probe * 8, (n_query, n_probe)
+            shape = (n_data, n_query, n_probe, self.m)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivfpq_range_residual_count", device, *inputs, thr, counts, *shape),
+                    lambda thr, *out: call("tpq_ivfpq_range_residual_fill", device, *inputs, thr, *out, *shape))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+
+# ---- what the range wrappers share --------------------------------------------------------------------------------
+def _checked_threshold(threshold, n_query):
+    """a range search's threshold: a Python float, or one float32 per query (returned contiguous)"""
+    if not torch.is_tensor(threshold):
+        return float(threshold)
+    assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+    return threshold.contiguous()
+
+
+def _tensor_or_none(threshold):
+    return threshold if torch.is_tensor(threshold) else None
+
+
+def _range_two_pass(n_query, device, threshold, passes):
+    """The driver of a two-pass range search: count -> the caller's prefix sum -> one .item() -> fill.
+    `passes()` -- called only for a non-empty batch -- returns (segments, count(thr, counts), fill(thr, offsets,
+    values, address)), the two launches taking device pointers; segment s belongs to query s // (segments // n_query).
+    Returns (lims [n_query + 1] int64, values [total] float32, address [total] int64)."""
+    if n_query == 0:
+        return (torch.zeros(1, device=device, dtype=torch.int64),
+                torch.empty(0, device=device, dtype=torch.float32),
+                torch.empty(0, device=device, dtype=torch.int64))
+    if not torch.is_tensor(threshold):
+        threshold = torch.full((n_query,), threshold, device=device, dtype=torch.float32)
+    n_seg, count, fill = passes()
+    counts = torch.empty(n_seg, device=device, dtype=torch.int32)
+    count(ptr(threshold), ptr(counts))
+    offsets = torch.zeros(n_seg + 1, device=device, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(offsets[-1].item())     # the host sync a variable-size output needs
+    values = torch.empty(total, device=device, dtype=torch.float32)
+    address = torch.empty(total, device=device, dtype=torch.int64)
+    if total:
+        fill(ptr(threshold), ptr(offsets), ptr(values), ptr(address))
+    return offsets[::n_seg // n_query].contiguous(), values, address
