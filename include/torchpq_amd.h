@@ -130,6 +130,29 @@ size_t tpq_ivfpq_scan_tickets_bytes(int nq);
 #define TPQ_SCAN_ROUTE_DUMP_SEL16_W8 17 /* ... eight-wave workgroups (k in (248, 504] on long cells) */
 int tpq_ivfpq_scan_route(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
                          int has_packed, int has_tickets, int residual);
+/* The dispatch order of a large batch.  The large-batch routes (TPQ_SCAN_ROUTE_DUMP_*) run one workgroup per query, and
+ * workgroups start in index order: dispatched longest first, a batch ends on its shortest queries instead of on whichever
+ * came last.  The scan entry points compute the order themselves, per call, on the stream (two small launches ahead of
+ * the scan; no host read, no allocation, capturable in a graph), exactly when the batch needs more than one round of
+ * the device's workgroup slots, holds at most 20 480 queries and the workspace has room for it behind the lists the
+ * call uses -- three int32 per query, each array rounded up to 256 bytes, out of what tpq_ivfpq_scan_workspace_bytes
+ * already covers; a smaller workspace keeps index order.  Results do not depend on the order.
+ * tpq_ivfpq_scan_order is that computation on its own:
+ *   work[q]  = sum over p < n_probe_list[q] (clamped to [0, max_nprobe]) of ceil(cell_size[q][p] / 2^tile_shift), a
+ *              negative size counting 0 and a probe whose start equals the previous probe's start counting 0 (the scan
+ *              skips it); saturates at 2^31 - 1
+ *   order    i32 [nq]  a permutation of the queries, work non-increasing, equal work by ascending query
+ *   rank     i32 [nq]  its inverse: rank[order[i]] == i
+ * work is i32 [nq] like the other two; 0 <= tile_shift <= 16 (the scan's tiles: 64 slots at m > 32, 256 at m <= 32).
+ * The ranking compares every pair of queries: its time grows with nq squared (about 18 us at 10 000 queries).
+ * tpq_ivfpq_scan_ordered answers, without launching anything, whether a scan call with these arguments -- those of
+ * tpq_ivfpq_scan_route, the workgroup slots of the device (0 = ask the current device) and the workspace size the
+ * caller passes -- is dispatched in that order: 1 / 0, or -1 for arguments the entry points reject. */
+int tpq_ivfpq_scan_order(const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list, int nq,
+                         int max_nprobe, int tile_shift, int32_t* order, int32_t* rank, int32_t* work,
+                         tpq_stream_t stream);
+int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
+                           int has_packed, int has_tickets, int residual, int slots, size_t workspace_bytes);
 int tpq_ivfpq_scan_topk_packed_tickets(const uint8_t* packed, const uint8_t* codes, const float* lut,
                                        const uint8_t* is_empty, const int64_t* cell_start,
                                        const int64_t* cell_size, const int64_t* n_probe_list,

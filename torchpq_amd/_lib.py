@@ -39,6 +39,8 @@ SIGNATURES = {
                                     _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ivfpq_scan_tickets_bytes": (_sz, [_i]),
     "tpq_ivfpq_scan_route": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i]),
+    "tpq_ivfpq_scan_order": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tpq_ivfpq_scan_ordered": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _sz]),
     "tpq_ivfpq_scan_topk_packed_tickets": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                                 _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp]),
     "tpq_ivfpq_search_fused_tickets": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -31,6 +31,7 @@
 #include <chrono>
 
 #include "scan_device.h"
+#include "scan_order.h"
 #include "scan_ref.h"
 
 namespace tpq {
@@ -267,10 +268,11 @@ static void dump_tail(int nq, int nw, int RL, int slots, int* unsplit, int* part
 }
 
 // What a packed call runs, decided once per call by plan_scan -- a pure host function (no HIP call: the route query,
-// tpq_ivfpq_scan_route, answers without a GPU) -- and executed by run_packed without re-deriving any of it.  Two things
-// stay with the executor because they need the device or the caller's buffer: the dump routes' split tail (dump_tail,
-// from the device's workgroup slots) and, when the caller's workspace is too small for it, the tail kept whole.  Both
-// change the parts a query is dealt in, never the route.
+// tpq_ivfpq_scan_route, answers without a GPU) -- and executed by run_packed without re-deriving any of it.  How a dump
+// route deals its workgroups -- the split tail and the dispatch order -- needs the device's workgroup slots and the size
+// of the caller's buffer: plan_dump_dispatch adds it to the plan from those two numbers (pure as well: the executor asks
+// the device, tpq_ivfpq_scan_ordered takes them as arguments).  It changes the parts a query is dealt in and the order
+// the queries start in, never the route.
 struct ScanPlan {
   int route = -1;            // TPQ_SCAN_ROUTE_*, -1 = the entry point rejects the call
   int R = 0;                 // registers of the merged list (list_regs_packed(k))
@@ -281,6 +283,10 @@ struct ScanPlan {
   int n_split = 1;           // workgroups per query (the dump routes: 1 before the split tail)
   bool fuse = false;         // one-launch finish
   bool small_lists = false;  // per-wave lists shorter than k + kBandSlack
+  // dump routes, by plan_dump_dispatch:
+  int unsplit = 0;           // ScanArgs::unsplit (0: every query is dealt in `parts`)
+  int parts = 1;             // workgroups per query of the split tail
+  bool ordered = false;      // queries dispatched longest first (scan_order.hip)
 };
 
 static ScanPlan plan_scan(const ScanArgs& a, bool residual) {
@@ -339,19 +345,58 @@ static ScanPlan plan_scan(const ScanArgs& a, bool residual) {
   return p;
 }
 
-extern "C" int tpq_ivfpq_scan_route(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
-                                    int has_lut, int has_packed, int has_tickets, int residual) {
-  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
-  if (!has_packed) return TPQ_SCAN_ROUTE_REF;
+// The dump routes' dispatch, from the device's workgroup slots and the caller's workspace:
+//  * the split tail (dump_tail; a workspace sized by an older rule keeps the tail whole);
+//  * the order: on exactly when the batch needs more than one round of workgroup slots -- below that there is no ragged
+//    end to shorten and the call costs what it did -- and is within the ranking's limit (kOrderMaxQueries), and the
+//    workspace has room for the order behind the lists in use (tpq_ivfpq_scan_workspace_bytes covers 16 lists of two
+//    registers per query, a call uses parts x waves x RL of them: the size the caller is told does not change; a
+//    workspace without the room keeps index order).
+static void plan_dump_dispatch(ScanPlan& p, int nq, int slots, size_t workspace_bytes) {
+  int unsplit = nq, parts = 1;
+  if (p.mode != kDumpSel16W8) dump_tail(nq, p.waves, p.RL, slots, &unsplit, &parts);
+  if (parts > 1 && workspace_bytes < ws_bytes_for(nq, p.RL, parts * p.waves)) unsplit = nq, parts = 1;
+  p.parts = parts;
+  p.unsplit = parts > 1 ? unsplit : 0;  // (0 with one part per query: "all queries split 1 way")
+  p.ordered = slots > 0 && nq > slots && nq <= kOrderMaxQueries &&
+              workspace_bytes >= ws_bytes_for(nq, p.RL, parts * p.waves) + order_ws_bytes(nq);
+}
+static bool is_dump_route(int route) {
+  return route == TPQ_SCAN_ROUTE_DUMP_F32 || route == TPQ_SCAN_ROUTE_DUMP_SEL16 || route == TPQ_SCAN_ROUTE_DUMP_SEL16_W8;
+}
+
+// the arguments a route query stands for (pointers are only tested against nullptr)
+static ScanArgs route_query_args(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                 int has_lut, int has_tickets) {
   ScanArgs a{};
   static const float dummy_lut = 0.f;
   static int32_t dummy_tickets = 0;
-  a.lut = has_lut ? &dummy_lut : nullptr;   // (only tested against nullptr)
+  a.lut = has_lut ? &dummy_lut : nullptr;
   a.ds = has_lut ? 0 : ds;
   a.nq = nq; a.k = k; a.n_split = n_split; a.m = m; a.max_nprobe = max_nprobe;
   a.slots_hint = slots_hint;
   a.tickets = has_tickets ? &dummy_tickets : nullptr;
-  return plan_scan(a, residual != 0).route;
+  return a;
+}
+
+extern "C" int tpq_ivfpq_scan_route(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                    int has_lut, int has_packed, int has_tickets, int residual) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return TPQ_SCAN_ROUTE_REF;
+  return plan_scan(route_query_args(nq, k, n_split, m, ds, max_nprobe, slots_hint, has_lut, has_tickets), residual != 0)
+      .route;
+}
+
+extern "C" int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                      int has_lut, int has_packed, int has_tickets, int residual, int slots,
+                                      size_t workspace_bytes) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return 0;
+  ScanPlan p =
+      plan_scan(route_query_args(nq, k, n_split, m, ds, max_nprobe, slots_hint, has_lut, has_tickets), residual != 0);
+  if (!is_dump_route(p.route)) return 0;
+  plan_dump_dispatch(p, nq, slots > 0 ? slots : dump_slots(*packed_unit(m), p.mode), workspace_bytes);
+  return p.ordered ? 1 : 0;
 }
 
 static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
@@ -361,7 +406,7 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
   TPQ_REQUIRE(a.packed != nullptr, "ivfpq_scan_packed: null packed pointer");
   if (a.nq == 0) return TPQ_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const ScanPlan p = plan_scan(a, ra != nullptr);
+  ScanPlan p = plan_scan(a, ra != nullptr);
   if (p.route == TPQ_SCAN_ROUTE_REF) {
     a.n_split = p.n_split;
     return ra ? run_residual_ref(a, *ra, st) : run_ref(a, workspace, workspace_bytes, st);
@@ -397,15 +442,22 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
     case TPQ_SCAN_ROUTE_DUMP_F32:
     case TPQ_SCAN_ROUTE_DUMP_SEL16:
     case TPQ_SCAN_ROUTE_DUMP_SEL16_W8: {
-      int unsplit = nq, parts = 1;
-      if (p.mode != kDumpSel16W8) dump_tail(nq, p.waves, p.RL, dump_slots(u, p.mode), &unsplit, &parts);
-      // (a caller's workspace sized by an older rule: the tail stays whole)
-      if (parts > 1 && (!workspace || workspace_bytes < ws_bytes_for(nq, p.RL, parts * p.waves))) unsplit = nq, parts = 1;
-      a.n_split = parts;
-      a.unsplit = parts > 1 ? unsplit : 0;  // (0 with one part per query: "all queries split 1 way")
-      rc = need_ws(workspace, workspace_bytes, ws_bytes_for(nq, p.RL, parts * p.waves), "ivfpq_scan_packed");
+      plan_dump_dispatch(p, nq, dump_slots(u, p.mode), workspace ? workspace_bytes : 0);
+      a.n_split = p.parts;
+      a.unsplit = p.unsplit;
+      const size_t lists_bytes = ws_bytes_for(nq, p.RL, p.parts * p.waves);
+      rc = need_ws(workspace, workspace_bytes, lists_bytes, "ivfpq_scan_packed");
       if (rc) return rc;
-      fill_ws(a, workspace, p.RL, parts * p.waves);
+      fill_ws(a, workspace, p.RL, p.parts * p.waves);
+      if (p.ordered) {  // order, rank and the work they are ranked by: behind the lists in use
+        int* o = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + lists_bytes);
+        const size_t stride = order_ws_bytes(nq) / 3 / sizeof(int);
+        rc = launch_scan_order(a.cell_start, a.cell_size, a.n_probe_list, nq, a.max_nprobe, packed_tile_shift(a.m), o,
+                               o + stride, o + 2 * stride, st);
+        if (rc) return rc;
+        a.order = o;
+        a.rank = o + stride;
+      }
       rc = u.dump(a, p.RL, p.Rf, p.mode, st);
       break;
     }

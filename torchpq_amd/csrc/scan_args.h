@@ -70,9 +70,15 @@ struct ScanArgs {
   // workgroups each (0 = every query is split n_split ways, the meaning of n_split everywhere else).  A batch that is
   // not a multiple of the chip's workgroup slots ends with a round of few workgroups, each as long as a whole query
   // (1 250 queries on 1 024 slots: two rounds for 1.22 rounds of work); the queries of that last round are dealt
-  // as short workgroups instead -- they start last (workgroups are dispatched in index order) and fill the slots
+  // as short workgroups instead -- they start last (workgroups are dispatched in blockIdx order) and fill the slots
   // the long ones leave.  The lists keep the stride of n_split parts for every query.
   int unsplit;
+  // dump mode, dispatch order (scan_order.hip): order[i] = the query the i-th workgroup (the i-th group of n_split
+  // workgroups, past `unsplit`) scans -- the batch's queries longest first, so that the batch ends on its shortest --,
+  // rank = its inverse: a query runs unsplit when rank[q] < unsplit.  nullptr = index order.  Everything else is
+  // indexed by the query, as before: the results do not depend on the order.
+  const int* order;
+  const int* rank;
 };
 
 // scan_packed_kernel modes beyond the fused finish (RM > 0) and the pools (RM = -1, -2, -3): "dump" -- the scan

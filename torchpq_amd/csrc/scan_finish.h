@@ -133,7 +133,8 @@ __global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kerne
   for (int q = (int)blockIdx.x * kFinishWaves + wave; q < a.nq; q += (int)gridDim.x * kFinishWaves) {
     if (a.flags[q] == a.epoch) continue;  // the scan left the query to the exact kernel
     // (tail split: an unsplit query filled the lists of its one part only; the stride is that of n_split parts)
-    const int n_lists = q < a.unsplit ? nw_scan : n_lists_all;
+    // (dispatch order, ScanArgs::rank: the unsplit queries are the first `unsplit` of the order)
+    const int n_lists = (a.rank ? a.rank[q] : q) < a.unsplit ? nw_scan : n_lists_all;
     const int T = n_lists * RL;  // chunks in use
     // the query: component i in lane i % 64 of register i / 64; |q_j|^2 (ascending-dimension fma chain) in lane j
     float xv[2] = {0.f, 0.f}, q2v = 0.f;

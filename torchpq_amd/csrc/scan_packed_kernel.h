@@ -143,6 +143,11 @@ __global__ __launch_bounds__(scan_waves(M, RM) * 64, 4) void scan_packed_kernel(
     part = b - (q - first) * a.n_split;
     parts = a.n_split;
   }
+  // (dispatch order, ScanArgs::order: the position dealt above is a RANK -- workgroups start in blockIdx order, the
+  // longest queries first, the split tail is the shortest; one wave-uniform load, the pointer is null in index order)
+  if constexpr (DUMP) {
+    if (a.order) q = __builtin_amdgcn_readfirstlane(a.order[q]);
+  }
   TPQ_PROF(a, blockIdx.x, 0);
   int n_probe = (int)a.n_probe_list[q];
   n_probe = n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);

@@ -39,6 +39,11 @@ class IVFPQTopkHip:
         self.keep_workspace = False   # diagnostics: keep the last call's workspace in `last_workspace`
         self.last_workspace = None
         self.last_call = None         # diagnostics: the arguments of the last topk / topk_fused call (`last_route()`)
+        # diagnostics / tests: bytes of workspace to hand to the library instead of tpq_ivfpq_scan_workspace_bytes (a
+        # caller that sizes its workspace by an older rule); `last_workspace_bytes`: what the last call handed over
+        self.workspace_bytes = None
+        self.last_workspace_bytes = None
+        self._last_device = None
 
     def _tickets(self, n_query, n_split, device):
         """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
@@ -101,6 +106,25 @@ class IVFPQTopkHip:
         """diagnostics: route(...) of the last topk / topk_fused call"""
         return None if self.last_call is None else self.route(**self.last_call)
 
+    def ordered(self, workspace_bytes, slots=0):
+        """diagnostics: whether the last topk / topk_fused call, handed `workspace_bytes` of workspace, dispatches its
+        queries longest first (tpq_ivfpq_scan_ordered: the library's own rule, nothing is launched; `slots`: the
+        device's workgroup slots, 0 = ask the device the call ran on)"""
+        if self.last_call is None:
+            return None
+        c = self.last_call
+        with torch.cuda.device(self._last_device):
+            code = load().tpq_ivfpq_scan_ordered(int(c["n_query"]), int(c["k"]), int(c["n_split"]), self.m, int(c["ds"]),
+                                                  int(c["n_probe"]), int(c["slots_hint"] or 0), int(bool(c["has_lut"])),
+                                                  int(bool(c["packed"]) and self.m in PACKED_M), int(c["n_split"] > 1),
+                                                  int(bool(c.get("residual", False))), int(slots), int(workspace_bytes))
+        return code == 1
+
+    def last_ordered(self):
+        """diagnostics: whether the last topk / topk_fused call dispatched its queries longest first (csrc/scan_order.hip:
+        a large batch of more than one round of workgroup slots whose workspace has room for the order)"""
+        return None if self.last_call is None else self.ordered(self.last_workspace_bytes)
+
     def _n_split(self, n_query, device, slots_hint=None):
         """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
         if self.n_cus is None:
@@ -126,6 +150,9 @@ class IVFPQTopkHip:
         self.last_call = dict(n_query=n_query, k=k, n_split=n_split, n_probe=n_probe, slots_hint=slots_hint,
                               packed=packed is not None, **route)
         ws_bytes = lib.tpq_ivfpq_scan_workspace_bytes(n_query, k, n_split, self.m)
+        if self.workspace_bytes is not None:
+            ws_bytes = int(self.workspace_bytes)
+        self.last_workspace_bytes, self._last_device = ws_bytes, device
         ws = torch.empty(max(ws_bytes, 1), device=device, dtype=torch.uint8)
         ev = None
         if self.record_events is not None:
@@ -311,6 +338,25 @@ class IVFPQTopkHip:
         assert cells.shape == cell_start.shape and cells.dtype == torch.int64
         return self._residual(data, part1, part2, None, cells, base_sims, is_empty, cell_start,
                               cell_size, n_probe_list, n_candidates, address2id)
+
+
+class ScanOrderHip:
+    """The dispatch order of a large batch on its own (tpq_ivfpq_scan_order, csrc/scan_order.hip): the queries by the
+    tiles of 2^tile_shift slots they scan, longest first -- what the large-batch scan routes compute per call."""
+
+    def __call__(self, cell_start, cell_size, n_probe_list, tile_shift=6):
+        """cell_start / cell_size [n_query, max_n_probe] int64, n_probe_list [n_query] int64 -> (order, rank, work),
+        int32 [n_query] each: work non-increasing along order, equal work by ascending query; rank[order[i]] == i"""
+        n_query, n_probe = cell_start.shape
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        require_gpu(cell_start, cell_size, n_probe_list)
+        order, rank, work = (torch.empty(n_query, device=cell_start.device, dtype=torch.int32) for _ in range(3))
+        if n_query:
+            call("tpq_ivfpq_scan_order", cell_start.device, ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+                 n_query, n_probe, int(tile_shift), ptr(order), ptr(rank), ptr(work))
+        return order, rank, work
 
 
 class ResidualSlotTermsHip:
