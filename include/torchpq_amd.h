@@ -567,6 +567,42 @@ int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_
                           int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQ4Index list scan + top-k: product-quantized lists with 16 centroids per sub-quantizer (4-bit codes; the
+ * reference began such a path, top-1 only, and has no index for it).
+ *
+ * Codes        m sub-quantizers, m % 8 == 0, 8 <= m <= 256, sub-vector length ds = d / m >= 1, 16 centroids each.
+ *              A vector's code is m / 2 bytes: byte b holds sub-quantizer 2 b in bits 0-3 and sub-quantizer 2 b + 1
+ *              in bits 4-7.
+ * codes        u8 [m / 8][n_slots][4]: CellContainer._storage of code_size = m / 2, contiguous_size = 4.  Read as
+ *              32-bit little-endian words it is [m / 8][n_slots]: word w of slot s holds sub-quantizers 8 w ... 8 w + 7,
+ *              lowest nibble first.
+ * query        f32 [d][nq], d = m * ds (pre-normalised by the host for TPQ_METRIC_INNER)
+ * codebook     f32 [m][ds][16]
+ * is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, n_slots, nq, max_nprobe, k, n_split, workspace:
+ *              as tpq_ivfflat_scan_topk
+ *
+ * Table entry of sub-quantizer j and centroid c (all fp32, no fma, i ascending, e starts at 0.f):
+ *       TPQ_METRIC_NEG_SQ_L2:  t = q[j*ds + i] - codebook[j][i][c];  e = e - t*t
+ *       TPQ_METRIC_INNER:      e = e + q[j*ds + i] * codebook[j][i][c]
+ * -- the arithmetic of tpq_ivfflat_scan_topk's value over the sub-vector; NOT the 2 q.c - |q|^2 - |c|^2 form of
+ * tpq_adc_lut.  The table (m x 16 floats per query) is built inside the scan workgroup and never exists in memory.
+ * Value of a slot:  v = 0.f;  for j = 0 ... m - 1 ascending:  v = v + table[j][code_j]  (one fp32 add per step).
+ * Candidates, order and padding are exactly those of tpq_ivfflat_scan_topk: the first n_probe_list[q] cells
+ * (clamped to [0, max_nprobe]); a probe whose start equals the previous probe's start is skipped; slots outside the
+ * storage are cut; tombstones are skipped when is_empty is given; a NaN value never enters; the k best by (value
+ * descending, address ascending); (-inf, -1) beyond them.  The result does not depend on n_split.
+ * An m outside the above, ds < 1 or a k outside [1, 1024] returns TPQ_ERR_UNSUPPORTED (as does n_slots >= 2^31 - 1,
+ * or a d / max_nprobe whose query and probe table do not fit the LDS next to the table); nothing is launched.
+ * Workspace: tpq_ivfpq4_scan_workspace_bytes(nq, k, n_split) bytes (0 when n_split == 1).  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+size_t tpq_ivfpq4_scan_workspace_bytes(int nq, int k, int n_split);
+int tpq_ivfpq4_scan_topk(const uint8_t* codes, const float* query, const float* codebook, const uint8_t* is_empty,
+                         const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                         float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq, int max_nprobe,
+                         int k, int metric, int n_split, void* workspace, size_t workspace_bytes,
+                         tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * IVFFlatIndex range search: every stored vector of the probed cells whose value reaches a threshold (no
  * reference counterpart).  vectors, query, is_empty, cell_start, cell_size, n_probe_list, n_slots, d, nq,
  * max_nprobe, metric and n_split are those of tpq_ivfflat_scan_topk.

@@ -3,6 +3,7 @@
 # Incremental: every object carries the compiler's own dependency list (build/<obj>.d, -MD), so a change to
 # one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
 # k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip and scan_flat.hip alone;
+# scan_pq4.hip (the 4-bit list scan) takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it;
 # scan_range.hip (IVFPQ range search) takes scan_shared.h and scan_args.h only, so the other scan headers leave it alone;
 # scan_order.hip (the large batches' dispatch order) takes scan_order.h alone, which scan.hip shares; fp16_cascade.h
 # rebuilds the four cascade units (cascade_core, assign_cascade, probe_sims, lloyd) and assign_fast; row_select.h (the
@@ -45,7 +46,7 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_flat.hip scan_range.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_flat.hip scan_pq4.hip scan_range.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   if stale "$obj" "${HERE}/${src}"; then

@@ -1,0 +1,126 @@
+"""IVFPQ4Index: coarse quantizer and inverted lists of 4-bit product-quantized codes.
+
+Sixteen centroids per sub-quantizer, two sub-quantizers per byte: half the code bytes of IVFPQIndex at a given
+n_subvectors.  The container is CellContainer unchanged with code_size = n_subvectors // 2 and contiguous_size = 4, so
+`_storage` is uint8 [n_subvectors // 8, capacity, 4]; the list scan (tpq_ivfpq4_scan_topk, csrc/scan_pq4.hip) reads it
+in place -- a 16-entry table row has no LDS bank conflicts whatever the codes are, so there is no scan-layout copy --
+and builds the query's table (n_subvectors x 16 floats) inside the scan workgroup.  add / expand / remove / tombstones /
+`_address2id` / state_dict are the container's.  No residual PQ, no range search, no captured graph.
+
+The coarse step is IVFPQIndex's (index/_coarse.py).
+"""
+import torch
+
+from ..codec import PQ4Codec
+from ..container import CellContainer
+from ..kernels import IVFPQ4TopkHip
+from ._coarse import CoarseProbeMixin
+
+
+class IVFPQ4Index(CoarseProbeMixin, CellContainer):
+    def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None, expand_step_size=128,
+                 expand_mode="double", distance="euclidean", device="cuda:0", verbose=0):
+        if torch.device(device).type == "cuda":
+            assert torch.cuda.is_available(), "cuda is not available"
+        assert d_vector % n_subvectors == 0
+        assert n_subvectors % 8 == 0, "codes are stored 8 sub-quantizers per word (two per byte, contiguous_size=4)"
+        assert 8 <= n_subvectors <= 256
+        assert distance in ("euclidean", "cosine")
+        super().__init__(code_size=n_subvectors // 2, n_cells=n_cells, dtype="uint8", device=device,
+                         initial_size=initial_size, expand_step_size=expand_step_size,
+                         expand_mode=expand_mode, use_inverse_id_mapping=True, contiguous_size=4,
+                         verbose=verbose)
+        self.d_vector = d_vector
+        self.n_subvectors = n_subvectors
+        self.d_subvector = d_vector // n_subvectors
+        self.distance = distance
+        self.verbose = verbose
+        self.use_cublas = True
+        self._init_coarse(n_cells, verbose)
+        self.pq_codec = PQ4Codec(d_vector=d_vector, n_subvectors=n_subvectors, distance=distance, verbose=verbose)
+        self._pq4_topk = IVFPQ4TopkHip(m=n_subvectors)
+        self.to(device)
+
+    # ---- knobs (as IVFPQIndex) -------------------------------------------------------------------------
+    def _codec_knob(codec, attr, typed):
+        def getter(self):
+            return getattr(getattr(self, codec).kmeans, attr)
+
+        def setter(self, value):
+            if typed:
+                assert type(value) is int
+                assert value > 0
+            assert not getattr(self, codec).is_trained, f"{codec} is already trained"
+            setattr(getattr(self, codec).kmeans, attr, value)
+        return property(getter, setter)
+
+    vq_codec_max_iter = _codec_knob("vq_codec", "max_iter", True)
+    vq_codec_n_redo = _codec_knob("vq_codec", "n_redo", True)
+    vq_codec_tolerance = _codec_knob("vq_codec", "tol", False)
+    pq_codec_max_iter = _codec_knob("pq_codec", "max_iter", True)
+    pq_codec_n_redo = _codec_knob("pq_codec", "n_redo", True)
+    pq_codec_tolerance = _codec_knob("pq_codec", "tol", False)
+    del _codec_knob
+
+    def _after_load_state_dict(self):
+        self.to(self.device)
+        super()._after_load_state_dict()
+
+    # ---- train / encode / add --------------------------------------------------------------------------
+    def train(self, x, force_retrain=False):
+        """x [d_vector, n_data] f32: coarse k-means (n_cells) then 16-centroid PQ codebooks."""
+        if self.vq_codec.is_trained and self.pq_codec.is_trained and not force_retrain:
+            self.print_message("index is already trained", 1)
+            return
+        x = self._prepare(x)
+        self.print_message("start training VQ codec...", 1)
+        self.vq_codec.train(x)
+        self.print_message("start training PQ codec...", 1)
+        self.pq_codec.train(x)
+        self.print_message("index is trained successfully!", 1)
+
+    def encode(self, x):
+        """x [d_vector, n] f32 -> packed PQ codes [n_subvectors // 2, n] uint8"""
+        return self.pq_codec.encode(self._prepare(x))
+
+    def decode(self, x):
+        """packed codes [n_subvectors // 2, n] uint8 -> [d_vector, n] f32"""
+        assert len(x.shape) == 2
+        assert x.shape[0] * 2 == self.n_subvectors
+        return self.pq_codec.decode(x.to(self.device))
+
+    def add(self, x, ids=None, return_address=False):
+        """x [d_vector, n] f32, optional ids [n] int64 (default arange + max_id + 1);
+        returns ids (and the slot addresses if return_address)."""
+        x = self._prepare(x)
+        assigned_cells = self.vq_codec.encode(x)
+        codes = self.pq_codec.encode(x)
+        return super().add(codes, cells=assigned_cells, ids=ids, return_address=return_address)
+
+    # ---- search ----------------------------------------------------------------------------------------
+    def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
+        """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
+        (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
+        the coarse step already gathered them.)"""
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        vals, address = self._pq4_topk(
+            self._storage, x, self.pq_codec.codebook, cell_start, cell_size, n_probe_list, k, is_empty=is_empty,
+            distance=self.distance, slots_hint=slots_hint)
+        ids = self.get_id_by_address(address)
+        return (vals, ids, address) if return_address else (vals, ids)
+
+    def graphed_search(self, n_query, k=1):
+        raise NotImplementedError("GraphedSearch captures IVFPQIndex.search only")
+
+    def search(self, x, k=1, return_address=False):
+        """x [d_vector, n_query] f32 -> (values f32 [n_query, k] descending, ids int64 [n_query, k][, address]);
+        values are -squared-L2 (euclidean) or the cosine similarity of the PQ reconstruction; (-inf, -1) pads."""
+        x = self._prepare(x)
+        assert 0 < k <= 1024
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        vals, ids, address = self._search_batches(x, lambda xb, sims, cells, n_probe_list, extents: self.search_cells(
+            x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=True,
+            _extents=extents))
+        return (vals, ids, address) if return_address else (vals, ids)

@@ -1,5 +1,5 @@
 """The list scans and what feeds them: IVFPQ top-k (plain, fused LUT, residual), the LUT and residual tables, the
-IVFPQR re-rank, the IVFFlat scan and range search, the IVFPQ range search."""
+IVFPQR re-rank, the IVFFlat scan and range search, the 4-bit IVFPQ4 scan, the IVFPQ range search."""
 import torch
 
 from .._lib import check, load, ptr, require_gpu, stream_ptr
@@ -517,6 +517,61 @@ class IVFFlatTopkHip:
         call("tpq_ivfflat_scan_topk", device,
              ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
              ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
+             ws_bytes)
+        return values, address
+
+
+class IVFPQ4TopkHip:
+    """The list scan of IVFPQ4Index (tpq_ivfpq4_scan_topk, csrc/scan_pq4.hip): 4-bit product-quantized lists, the
+    table built inside the scan workgroup; codes, table entry, value and order are defined in include/torchpq_amd.h."""
+
+    def __init__(self, m=8):
+        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    _n_split = IVFFlatTopkHip._n_split
+
+    def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, k, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          codes: [m // 8, n_slots, 4] uint8 (CellContainer._storage of code_size = m // 2)
+          query: [d, n_query] float32 (normalised by the caller for "cosine"); codebook: [m, d // m, 16] float32
+          cell_start / cell_size: [n_query, max_n_probe] int64; n_probe_list: [n_query] int64
+          is_empty: [n_slots] uint8, or None when no slot inside a cell is a tombstone
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        n_slots = codes.shape[1]
+        m, ds, kk = codebook.shape
+        n_query, n_probe = cell_start.shape
+        assert m == self.m and kk == 16 and ds >= 1
+        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+        assert cell_start.dtype == cell_size.dtype == torch.int64
+        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+        if is_empty is not None:
+            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list)
+        device = codes.device
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        if n_split is None:
+            n_split = self._n_split(n_query, device, slots_hint)
+        self.last_n_split = n_split
+        ws_bytes = load().tpq_ivfpq4_scan_workspace_bytes(n_query, k, n_split)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+        call("tpq_ivfpq4_scan_topk", device,
+             ptr(codes), ptr(query), ptr(codebook), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+             ptr(values), ptr(address), n_slots, m, ds, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
              ws_bytes)
         return values, address
 
