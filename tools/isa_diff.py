@@ -6,7 +6,11 @@ assembly with build.sh's flags; kernels are paired by symbol and compared as tex
 the `.amdhsa_` block (registers, LDS, scratch, wave limits), comments stripped, local labels renumbered in order of
 appearance.  Prints the kernel count per unit and every kernel that differs, is missing or is new; exit status 1 if any.
 
-    python tools/isa_diff.py [--parent HEAD] [--jobs 8] [--cache DIR] [unit ...]
+    python tools/isa_diff.py [--parent HEAD] [--jobs 8] [--cache DIR] [--explain] [unit ...]
+
+--explain adds, for every kernel that differs, the `.amdhsa_` lines that changed, the instruction total before and after
+and the count delta per mnemonic.  A kernel whose parameter types were renamed (another mangled symbol, the same name) is
+paired by its demangled name (c++filt) instead of being reported as missing and new.
 
 A unit is a file of torchpq_amd/csrc, `scan_packed.hip:64` for one per-M unit, or `old.hip=new1.hip+new2.hip` for a
 unit the working tree has split: the parent's kernels of old.hip against the union of the new units'.  The left side
@@ -57,8 +61,35 @@ def kernels(path):
     return out
 
 
+def unqualified(symbols):
+    """{demangled name without its parameter list: symbol}"""
+    if not symbols:
+        return {}
+    try:
+        names = subprocess.run(["c++filt", *symbols], stdout=subprocess.PIPE, text=True, check=True).stdout.split("\n")
+    except (OSError, subprocess.CalledProcessError):  # no demangler: the kernels stay "missing" and "new"
+        return {}
+    return {n[:n.rindex("(")] if "(" in n else n: s for n, s in zip(names, symbols)}
+
+
+def explain(old, new):
+    """what changed in a kernel that differs: its resource lines, the instruction total, the count per mnemonic"""
+    from collections import Counter
+    split = lambda t: ({l.split()[0]: " ".join(l.split()[1:]) for l in t.split("\n") if l.startswith(".amdhsa_")},
+                       Counter(l.split()[0] for l in t.split("\n") if not l.startswith(".") and not l.endswith(":")))
+    (ro, co), (rn, cn) = split(old), split(new)
+    out = [f"{k} {ro.get(k, '(absent)')}  ->  {rn.get(k, '(absent)')}" for k in sorted(set(ro) | set(rn)) if ro.get(k) != rn.get(k)]
+    to, tn = sum(co.values()), sum(cn.values())
+    out.append(f"instructions {to} -> {tn} ({100.0 * (tn - to) / to:+.2f} %)")
+    delta = {k: cn[k] - co[k] for k in sorted(set(co) | set(cn)) if cn[k] != co[k]}
+    out.append("per mnemonic: " + (", ".join(f"{k} {v:+d}" for k, v in delta.items()) or "equal counts (operands differ)"))
+    return ["      " + l for l in out]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--explain", action="store_true", help="for every kernel that differs: the .amdhsa_ lines that "
+                    "changed, the instruction count before and after, the count delta per mnemonic")
     ap.add_argument("--parent", default="HEAD")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--cache", default=None, help="directory that keeps the parent's assembly")
@@ -88,9 +119,20 @@ def main():
                     kk = kernels(os.path.join(d, asm(n)))
                     twice += [f"twice {k}" for k in kk if k in side]
                     side.update(kk)
-            diff = twice + [f"missing {k}" for k in ko if k not in kn] + [f"new {k}" for k in kn if k not in ko] + \
-                   [f"differs {k}" for k in ko if k in kn and ko[k] != kn[k]]
-            print("\n  ".join([f"{u}: {len(ko)} kernels before, {len(kn)} after, {len(diff)} not identical"] + diff))
+            # a kernel whose parameter TYPES were renamed has another symbol: paired by its name without the parameter list
+            lost, came = unqualified([k for k in ko if k not in kn]), unqualified([k for k in kn if k not in ko])
+            moved = {symbol: came[name] for name, symbol in lost.items() if name in came}
+            diff = twice + [f"missing {k}" for k in ko if k not in kn and k not in moved] + \
+                   [f"new {k}" for k in kn if k not in ko and k not in moved.values()]
+            notes = {}
+            for k in ko:
+                k2 = moved.get(k, k)
+                if k2 in kn and ko[k] != kn[k2]:
+                    diff.append(f"differs {k}")
+                    notes[diff[-1]] = explain(ko[k], kn[k2]) if a.explain else []
+            print("\n  ".join([f"{u}: {len(ko)} kernels before, {len(kn)} after, {len(diff)} not identical"] +
+                              [f"same name, other parameter types: {k} -> {v}" for k, v in moved.items()] +
+                              [l for d in diff for l in [d] + notes.get(d, [])]))
             bad += len(diff)
     print("identical" if not bad else f"{bad} kernel(s) not identical")
     return 1 if bad else 0

@@ -2,9 +2,11 @@
 # Builds libtorchpq_amd.so for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
 # Incremental: every object carries the compiler's own dependency list (build/<obj>.d, -MD), so a change to
 # one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
-# k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip and scan_flat.hip alone;
-# scan_pq4.hip (the 4-bit list scan) takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it;
-# scan_range.hip (IVFPQ range search) takes scan_shared.h and scan_args.h only, so the other scan headers leave it alone;
+# k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip, scan_flat.hip and
+# scan_pq4.hip alone (the 4-bit list scan takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it);
+# scan_list.h (the frame of a list kernel) is included by scan_ref.h, scan_range.hip and, for clamped_n_probe, scan_packed_kernel.h,
+# so a change to it rebuilds every scan unit; scan_range.hip (IVFPQ range search) takes scan_list.h, scan_shared.h and
+# scan_args.h only, so the other scan headers -- the packed ones above all -- leave it alone;
 # scan_order.hip (the large batches' dispatch order) takes scan_order.h alone, which scan.hip shares; fp16_cascade.h
 # rebuilds the four cascade units (cascade_core, assign_cascade, probe_sims, lloyd) and assign_fast; row_select.h (the
 # row select's device code) rebuilds select, coarse_probe and probe_sims; probe_fast.h rebuilds coarse_probe and

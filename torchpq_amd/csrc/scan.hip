@@ -50,29 +50,23 @@ __global__ __launch_bounds__(256) void residual_part1_kernel(const float* __rest
 }
 
 
-template <int R>
-static int launch_ref(ScanArgs a, hipStream_t st) {
-  const size_t lds = scan_lds_bytes_ref(a.m, R, a.max_nprobe, fused_floats_of(a));
-  int rc = set_lds(scan_ref_kernel<R>, lds, "scan_ref_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(scan_ref_kernel<R>, dim3((unsigned)a.nq * a.n_split), dim3(kScanThreads), lds,
-                     st, a);
-  TPQ_LAUNCH_CHECK("scan_ref_kernel");
-  if (a.n_split > 1) {
-    hipLaunchKernelGGL(scan_merge_kernel<R>, dim3(a.nq), dim3(64), 0, st, a);
-    TPQ_LAUNCH_CHECK("scan_merge_kernel");
-  }
-  return TPQ_OK;
+// LDS of the reference-layout kernels: the m KiB table in region0, the staged query behind the frame
+static size_t ref_lds_bytes(int m, int R, int max_nprobe, int fused_floats) {
+  return list_scan_lds_bytes(list_region0((size_t)m * 1024, R), max_nprobe, (size_t)fused_floats * 4);
 }
 
 static int dispatch_ref(const ScanArgs& a, int R, hipStream_t st) {
-  return with_list_regs(R, [&](auto r_c) { return launch_ref<decltype(r_c)::value>(a, st); });
+  return with_list_regs(R, [&](auto r_c) {
+    constexpr int RC = decltype(r_c)::value;
+    return launch_list_scan(scan_ref_kernel<RC>, scan_merge_kernel<RC>, "scan_ref_kernel", a,
+                            ref_lds_bytes(a.m, RC, a.max_nprobe, fused_floats_of(a)), st);
+  });
 }
 
 static int run_residual_ref(ScanArgs a, ResidualArgs ra, hipStream_t st) {
   const int R = list_regs(a.k);
   const bool build_part1 = !ra.full && !ra.part1;
-  const size_t lds = scan_lds_bytes_ref(a.m, R, a.max_nprobe, build_part1 ? a.m * a.ds + a.m : 0);
+  const size_t lds = ref_lds_bytes(a.m, R, a.max_nprobe, build_part1 ? a.m * a.ds + a.m : 0);
   auto go = [&](auto kernel) -> int {
     int rc2 = set_lds(kernel, lds, "scan_residual_kernel");
     if (rc2) return rc2;
@@ -474,20 +468,7 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
   return redo_flagged(a, ra, st);
 }
 
-// ---- entry points ------------------------------------------------------------------------------------
-// the arguments every scan entry point shares, set by name (the rest of ScanArgs stays zero)
-static ScanArgs scan_args(const uint8_t* codes, const uint8_t* packed, const float* lut, const uint8_t* is_empty,
-                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
-                          float* out_vals, int64_t* out_addr, const int64_t* address2id, int64_t* out_ids,
-                          int64_t n_slots, int nq, int max_nprobe, int m, int k, int n_split) {
-  ScanArgs a{};
-  a.codes = codes; a.packed = packed; a.lut = lut; a.is_empty = is_empty;
-  a.cell_start = cell_start; a.cell_size = cell_size; a.n_probe_list = n_probe_list;
-  a.out_vals = out_vals; a.out_addr = out_addr; a.address2id = address2id; a.out_ids = out_ids;
-  a.n_slots = n_slots; a.nq = nq; a.max_nprobe = max_nprobe; a.m = m; a.k = k; a.n_split = n_split;
-  return a;
-}
-
+// ---- entry points (their ScanArgs: scan_args, scan_list.h) ---------------------------------------------
 extern "C" size_t tpq_ivfpq_scan_tickets_bytes(int nq) { return nq > 0 ? (size_t)nq * sizeof(int32_t) : 0; }
 
 extern "C" int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes,
@@ -623,11 +604,7 @@ __global__ __launch_bounds__(256) void residual_slot_term_kernel(
     float v = 0.f;
     for (int g = 0; g < G; ++g) {
       const uint32_t w = codes32[(int64_t)g * n_slots + s];
-      const float* row = p2 + g * 1024;
-      v += row[w & 255u];
-      v += row[256 + ((w >> 8) & 255u)];
-      v += row[512 + ((w >> 16) & 255u)];
-      v += row[768 + (w >> 24)];
+      v = lut_word(v, p2 + g * 1024, w);
     }
     slot_term[s] = v;
   }

@@ -1,4 +1,5 @@
 // IVF list scan, host side: list sizing, LDS and workspace sizes, argument checks.  Needs TPQ_PACKED_M_LIST (scan_device.h).
+// (check_lds, need_ws and what the list entry points share: scan_list.h, which scan_packed_kernel.h brings in)
 #pragma once
 #include "scan_args.h"
 #include "scan_packed_kernel.h"
@@ -61,14 +62,7 @@ static int pool_capacity(int k, int m) {  // (16 / 32 registers per lane at read
   return (k <= 512 && m > 32) ? 1024 : 2048;
 }  // (16 / 32 registers per lane at read-back)
 
-static size_t scan_lds_bytes_ref(int m, int R, int max_nprobe, int fused_floats) {
-  const int lut_bytes = m * 1024;
-  const int list_bytes = kScanWaves * R * 64 * 8;
-  const int region0 = lut_bytes > list_bytes ? lut_bytes : list_bytes;
-  size_t b = (size_t)region0 + kScanWaves * 512 + (size_t)(3 * max_nprobe + 1) * 4 + 4 +
-             (size_t)fused_floats * 4;
-  return (b + 15) & ~(size_t)15;
-}
+// (the reference-layout kernels: list_scan_lds_bytes, scan_list.h)
 static size_t scan_lds_bytes_packed(int m, int R, int max_nprobe, int fused_floats, bool res) {
   const int nw = packed_waves(m);
   size_t b = (size_t)m * 1024 + packed_aux_bytes(R, m) + nw * 512 +
@@ -106,10 +100,7 @@ TPQ_PACKED_M_LIST(TPQ_DECLARE_PACKED)
 
 template <class K>
 static int set_lds(K kernel, size_t bytes, const char* name) {
-  if (bytes > 160 * 1024) {
-    set_error("%s: needs %zu bytes of LDS (> 160 KiB per CU on gfx950)", name, bytes);
-    return TPQ_ERR_UNSUPPORTED;
-  }
+  if (int rc = check_lds(name, bytes)) return rc;
   return check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
                    name);
@@ -164,14 +155,6 @@ static int validate(const ScanArgs& a) {
   TPQ_REQUIRE(a.n_split >= 1 && a.n_split <= 1024, "ivfpq_scan: n_split=%d out of range", a.n_split);
   TPQ_REQUIRE((a.out_ids == nullptr) || (a.address2id != nullptr),
               "ivfpq_scan: out_ids given without address2id");
-  return TPQ_OK;
-}
-
-static int need_ws(const void* ws, size_t have, size_t need, const char* who) {
-  if (need && (!ws || have < need)) {
-    set_error("%s: workspace too small (%zu < %zu)", who, have, need);
-    return TPQ_ERR_WORKSPACE;
-  }
   return TPQ_OK;
 }
 

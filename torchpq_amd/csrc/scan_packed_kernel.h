@@ -1,6 +1,6 @@
 // IVF list scan: the packed-layout kernel -- wave, slot and tile policy, scan_packed_kernel and its stages.
 #pragma once
-#include "scan_shared.h"
+#include "scan_list.h"  // clamped_n_probe
 #include "scan_lut.h"
 #include "scan_exact.h"
 
@@ -149,8 +149,7 @@ __global__ __launch_bounds__(scan_waves(M, RM) * 64, 4) void scan_packed_kernel(
     if (a.order) q = __builtin_amdgcn_readfirstlane(a.order[q]);
   }
   TPQ_PROF(a, blockIdx.x, 0);
-  int n_probe = (int)a.n_probe_list[q];
-  n_probe = n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);
+  const int n_probe = clamped_n_probe(a, q);
 
   unsigned* jmax = reinterpret_cast<unsigned*>(qv_all);  // [M] (the queues are not live yet)
   if (threadIdx.x < M) jmax[threadIdx.x] = 0u;

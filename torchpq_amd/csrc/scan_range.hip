@@ -17,29 +17,22 @@
 //
 // LDS: the m KiB table, the staged query when the table is built here, the probe table (plain).  Nothing else: no
 // candidate lists, no shared threshold, no barrier after staging.
-#include "scan_shared.h"
+#include "scan_list.h"
 
 namespace tpq {
 namespace pqrange {
 
-constexpr int kRowGroup = 4;               // row loads in flight per lane, as scan_ref_kernel's group
-constexpr size_t kLdsLimit = 160 * 1024;   // per CU on gfx950
-
-struct RangeArgs {
-  const float* threshold;       // [nq]
-  int* wave_counts;             // count pass: [segments]
-  const int64_t* wave_offsets;  // fill pass: [segments + 1] exclusive prefix sums of the counts
-};
-
-__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // LDS: [table m KiB][query m * ds floats, when the table is built in the workgroup][probe table, plain only]
 __host__ __device__ constexpr size_t query_bytes(int m, int ds) { return align16((size_t)m * ds * 4); }
 static size_t lds_bytes(int m, int ds_staged, int probe_entries) {
-  return (size_t)m * 1024 + query_bytes(m, ds_staged) + (probe_entries ? (size_t)(3 * probe_entries + 1) * 4 : 0);
+  return (size_t)m * 1024 + query_bytes(m, ds_staged) + (probe_entries ? probe_table_bytes(probe_entries) : 0);
 }
+
+constexpr int kRowGroup = 4;  // row loads in flight per lane, as scan_ref_kernel's group
 
 // The value of scan_ref_kernel / scan_residual_kernel: v starts at `v` (0.f, or the probe's base similarity) and adds
 // lut[j][code_j] for j ascending, one fp32 add each.  `col` is the slot's dword of row 0, rows are `stride` dwords apart.
+// (The look-ups stay written out, as in scan_ref_kernel: see lut_word, scan_list.h.)
 __device__ __forceinline__ float slot_value(const uint32_t* __restrict__ col, int64_t stride, const float* lut, int G,
                                             float v) {
   int g = 0;
@@ -69,8 +62,8 @@ __device__ __forceinline__ float slot_value(const uint32_t* __restrict__ col, in
   return v;
 }
 
-// One tile of one cell: lane `lane` owns slot start + off.  Only slots inside [start, start + size) AND inside the
-// storage are read (a cell that leaves the storage is cut); tombstones are skipped; NaN fails `v >= thr` on either side.
+// One tile of one cell: the lane owns slot start + off.  Only slots inside [start, start + size) AND inside the storage
+// are read (a cell that leaves the storage is cut); tombstones are skipped; NaN fails `v >= thr` on either side.
 // RESIDUAL: the value is canonicalised with + 0.0f, as scan_residual_kernel pushes it.
 template <bool RESIDUAL>
 __device__ __forceinline__ bool tile_hit(const ScanArgs& a, const float* lut, int start, int size, int off, float base,
@@ -85,29 +78,6 @@ __device__ __forceinline__ bool tile_hit(const ScanArgs& a, const float* lut, in
   return v >= thr;
 }
 
-// A wave's segment.  Count pass: the number of hits.  Fill pass: hits are appended from `pos` on, in lane order, and
-// nothing is stored at or beyond `end` -- with other inputs than the count pass had (or offsets that are not its prefix
-// sums) hits are dropped, never stored in the next segment.
-template <bool FILL>
-struct Segment {
-  int64_t pos, end;
-  int n;
-  __device__ __forceinline__ void emit(const ScanArgs& a, bool hit, float v, int s) {
-    const unsigned long long mask = __ballot(hit);
-    if constexpr (FILL) {
-      const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-      const int64_t o = pos + rank;
-      if (hit && o < end) {
-        a.out_vals[o] = v;
-        a.out_addr[o] = (int64_t)s;
-      }
-      pos += __popcll(mask);
-    } else {
-      n += __popcll(mask);
-    }
-  }
-};
-
 // ---- plain PQ ----------------------------------------------------------------------------------------------------
 template <bool FILL>
 __device__ __forceinline__ void range_body(const ScanArgs& a, const RangeArgs& r, char* smem) {
@@ -116,46 +86,34 @@ __device__ __forceinline__ void range_body(const ScanArgs& a, const RangeArgs& r
   const int64_t seg = (int64_t)blockIdx.x * kScanWaves;
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
-  Segment<FILL> out{0, 0, 0};
-  if constexpr (FILL) {
-    // a workgroup without a hit leaves before it stages anything (the same two words for every thread: uniform)
-    if (r.wave_offsets[seg + kScanWaves] <= r.wave_offsets[seg]) return;
-    out.pos = r.wave_offsets[seg + wave];
-    out.end = r.wave_offsets[seg + wave + 1];
-  }
+  if (Segment<FILL>::no_hit(r, seg)) return;
+  Segment<FILL> out(r, seg, wave);
   float* lut = reinterpret_cast<float*>(smem);
   float* xq = reinterpret_cast<float*>(smem + (size_t)a.m * 1024);
-  int* ptab = reinterpret_cast<int*>(smem + (size_t)a.m * 1024 + (a.lut ? 0 : query_bytes(a.m, a.ds)));
-  const ProbeTable tab{ptab, ptab + a.max_nprobe, ptab + 2 * a.max_nprobe};
-  int n_probe = (int)a.n_probe_list[q];
-  n_probe = n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);
+  const ProbeTable tab =
+      probe_table_at(smem + (size_t)a.m * 1024 + (a.lut ? 0 : query_bytes(a.m, a.ds)), a.max_nprobe);
+  const int n_probe = clamped_n_probe(a, q);
   if (wave == 0) build_probe_table(a, q, n_probe, tab);
   if (!a.lut) stage_query(a, q, xq, kScanThreads);
   stage_lut_linear(a, q, lut, xq);
   __syncthreads();
-  if constexpr (FILL) {
-    if (out.pos < 0 || out.end <= out.pos) return;  // an empty segment: no code is read
-  }
+  if (out.empty()) return;  // no code is read
   // the part's tiles are scan_ref_kernel's; the wave's chunk of them is contiguous
-  const int total_tiles = tab.tile_begin[n_probe];
-  const int t_begin = (int)(((int64_t)total_tiles * part) / a.n_split);
-  const int t_end = (int)(((int64_t)total_tiles * (part + 1)) / a.n_split);
-  const int n_tiles = t_end - t_begin;
-  const int T0 = t_begin + (int)(((int64_t)n_tiles * wave) / kScanWaves);
-  const int T1 = t_begin + (int)(((int64_t)n_tiles * (wave + 1)) / kScanWaves);
+  const TileRange t = part_tiles(tab.tile_begin[n_probe], part, a.n_split);
+  const TileRange c = wave_chunk(t.begin, t.end, wave);
   const float thr = r.threshold[q];
   int p = 0;
-  for (int T = T0; T < T1; ++T) {
-    while (T >= tab.tile_begin[p + 1]) ++p;
+  for (int T = c.begin; T < c.end; ++T) {
     float v;
     int s;
+    p = probe_of(tab, p, T);
+    // (the cell's extent is read ahead of the offset here: through tile_at, which reads the offset first, these two
+    // kernels compile to other code)
     const bool hit = tile_hit<false>(a, lut, tab.start[p], tab.size[p], ((T - tab.tile_begin[p]) << 6) + lane, 0.f,
                                      thr, v, s);
     out.emit(a, hit, v, s);
   }
-  if constexpr (!FILL) {
-    if (lane == 0) r.wave_counts[seg + wave] = out.n;
-  }
+  out.close(r, seg, wave);
 }
 
 __global__ __launch_bounds__(kScanThreads) void ivfpq_range_count_kernel(ScanArgs a, RangeArgs r) {
@@ -177,15 +135,10 @@ __device__ __forceinline__ void residual_body(const ScanArgs& a, const ResidualA
   const int64_t seg = (int64_t)blockIdx.x * kScanWaves;
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
-  Segment<FILL> out{0, 0, 0};
-  if constexpr (FILL) {
-    if (r.wave_offsets[seg + kScanWaves] <= r.wave_offsets[seg]) return;  // (uniform) no hit: nothing is staged
-    out.pos = r.wave_offsets[seg + wave];
-    out.end = r.wave_offsets[seg + wave + 1];
-  }
+  if (Segment<FILL>::no_hit(r, seg)) return;
+  Segment<FILL> out(r, seg, wave);
   // the probe's extent, by the rules of fetch_probes: beyond n_probe_list[q], empty, or the previous probe's start again
-  int n_probe = (int)a.n_probe_list[q];
-  n_probe = n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);
+  const int n_probe = clamped_n_probe(a, q);
   int start = 0, size = 0;
   if (p < n_probe) {
     const int64_t at = (int64_t)q * a.max_nprobe + p;
@@ -205,39 +158,19 @@ __device__ __forceinline__ void residual_body(const ScanArgs& a, const ResidualA
   float* xq = reinterpret_cast<float*>(smem + (size_t)a.m * 1024);
   const bool build_part1 = !ra.full && !ra.part1;
   if (build_part1) stage_query(a, q, xq, kScanThreads);
-  const int n4 = a.m * 64;  // float4 count of one table
-  float4* dst = reinterpret_cast<float4*>(lut);
-  if (ra.full) {
-    const float4* __restrict__ src = reinterpret_cast<const float4*>(ra.full) + ((int64_t)q * a.max_nprobe + p) * n4;
-    for (int i = threadIdx.x; i < n4; i += kScanThreads) dst[i] = src[i];
-  } else {
-    const float4* __restrict__ s1 = reinterpret_cast<const float4*>(ra.part1) + (int64_t)q * n4;
-    const float4* __restrict__ s2 =
-        reinterpret_cast<const float4*>(ra.part2) + ra.cells[(int64_t)q * a.max_nprobe + p] * (int64_t)n4;
-    for (int i = threadIdx.x; i < n4; i += kScanThreads) {
-      const float4 x = build_part1 ? fused_lut4(a, i >> 6, i & 63, xq) : s1[i];
-      const float4 y = s2[i];
-      dst[i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
-    }
-  }
+  build_residual_lut(a, ra, q, p, lut, xq, build_part1);
   __syncthreads();
-  if constexpr (FILL) {
-    if (out.pos < 0 || out.end <= out.pos) return;  // an empty segment: no code is read
-  }
+  if (out.empty()) return;  // no code is read
   const float base = ra.base_sims[(int64_t)q * a.max_nprobe + p];
   const float thr = r.threshold[q];
-  const int tiles = (size + 63) >> 6;
-  const int T0 = (int)(((int64_t)tiles * wave) / kScanWaves);
-  const int T1 = (int)(((int64_t)tiles * (wave + 1)) / kScanWaves);
-  for (int T = T0; T < T1; ++T) {
+  const TileRange c = wave_chunk(0, (size + 63) >> 6, wave);
+  for (int T = c.begin; T < c.end; ++T) {
     float v;
     int s;
     const bool hit = tile_hit<true>(a, lut, start, size, (T << 6) + lane, base, thr, v, s);
     out.emit(a, hit, v, s);
   }
-  if constexpr (!FILL) {
-    if (lane == 0) r.wave_counts[seg + wave] = out.n;
-  }
+  out.close(r, seg, wave);
 }
 
 __global__ __launch_bounds__(kScanThreads) void ivfpq_range_residual_count_kernel(ScanArgs a, ResidualArgs ra,
@@ -259,13 +192,9 @@ static int check_common(const char* what, const uint8_t* codes, const int64_t* c
                         const float* out_vals, const int64_t* out_addr, bool fill, int64_t n_slots, int nq,
                         int max_nprobe, int m, int64_t groups_per_query, int* done) {
   *done = 0;
-  TPQ_REQUIRE(nq >= 0 && max_nprobe >= 1, "%s: bad nq/max_nprobe (%d, %d)", what, nq, max_nprobe);
+  if (int rc = check_batch(what, nq, max_nprobe)) return rc;
   TPQ_REQUIRE(m >= 4 && m % 4 == 0, "%s: n_subvectors=%d must be a positive multiple of 4", what, m);
-  TPQ_REQUIRE(n_slots >= 0, "%s: n_slots=%lld", what, (long long)n_slots);
-  if (n_slots >= (int64_t)kPadIdx) {
-    set_error("%s: n_slots=%lld >= 2^31-1 is not supported", what, (long long)n_slots);
-    return TPQ_ERR_UNSUPPORTED;
-  }
+  if (int rc = check_n_slots(what, n_slots)) return rc;
   if (m > 156) {  // (the m KiB table and anything at all beside it: the limit of the top-k scan)
     set_error("%s: n_subvectors=%d > 156: the table does not fit the 160 KiB of LDS of a CU", what, m);
     return TPQ_ERR_UNSUPPORTED;
@@ -279,14 +208,6 @@ static int check_common(const char* what, const uint8_t* codes, const int64_t* c
               "%s: null pointer argument", what);
   TPQ_REQUIRE((int64_t)nq * groups_per_query < 0x7fffffffLL, "%s: %lld workgroups", what,
               (long long)nq * groups_per_query);
-  return TPQ_OK;
-}
-
-static int check_lds(const char* what, size_t lds) {
-  if (lds > kLdsLimit) {
-    set_error("%s: needs %zu bytes of LDS (> 160 KiB per CU on gfx950)", what, lds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
   return TPQ_OK;
 }
 
@@ -309,26 +230,14 @@ static int range_pass(const char* what, const uint8_t* codes, const float* lut, 
   }
   const size_t lds = lds_bytes(m, lut ? 0 : ds, max_nprobe);
   if (int rc = check_lds(what, lds)) return rc;
-  ScanArgs a{};
-  a.codes = codes;
-  a.lut = lut;
+  ScanArgs a = scan_args(codes, nullptr, lut, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, nullptr,
+                         nullptr, n_slots, nq, max_nprobe, m, 0, n_split);
   if (!lut) {
     a.query = query;
     a.codebook = codebook;
     a.ds = ds;
     a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
   }
-  a.is_empty = is_empty;
-  a.cell_start = cell_start;
-  a.cell_size = cell_size;
-  a.n_probe_list = n_probe_list;
-  a.out_vals = out_vals;
-  a.out_addr = out_addr;
-  a.n_slots = n_slots;
-  a.nq = nq;
-  a.max_nprobe = max_nprobe;
-  a.m = m;
-  a.n_split = n_split;
   const RangeArgs r{threshold, wave_counts, fill ? wave_offsets : nullptr};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)nq * n_split), block(kScanThreads);
@@ -356,25 +265,14 @@ static int residual_pass(const char* what, const uint8_t* codes, const float* pa
   if (build_part1) TPQ_REQUIRE(ds >= 1 && ds <= 1024, "%s: bad sub-vector length %d", what, ds);
   const size_t lds = lds_bytes(m, build_part1 ? ds : 0, 0);
   if (int rc = check_lds(what, lds)) return rc;
-  ScanArgs a{};
-  a.codes = codes;
+  ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         nullptr, nullptr, n_slots, nq, max_nprobe, m, 0, 1);
   if (build_part1) {
     a.query = query;
     a.codebook = codebook;
     a.ds = ds;
     a.euclid = 2;  // part1 = 2 q_j . r_jc (fused_lut4)
   }
-  a.is_empty = is_empty;
-  a.cell_start = cell_start;
-  a.cell_size = cell_size;
-  a.n_probe_list = n_probe_list;
-  a.out_vals = out_vals;
-  a.out_addr = out_addr;
-  a.n_slots = n_slots;
-  a.nq = nq;
-  a.max_nprobe = max_nprobe;
-  a.m = m;
-  a.n_split = 1;
   const ResidualArgs ra{full_lut ? nullptr : part1, part2, full_lut, cells, base_sims, nullptr, nullptr};
   const RangeArgs r{threshold, wave_counts, fill ? wave_offsets : nullptr};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

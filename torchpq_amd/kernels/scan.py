@@ -466,6 +466,30 @@ class IVFPQRerankHip:
         return topk_result(values, address, ids)
 
 
+# ---- what the list-scan wrappers share -----------------------------------------------------------------------------
+def _check_lists(n_data, is_empty, cell_start, cell_size, n_probe_list):
+    """the list arguments of a scan over a storage of n_data slots -> (n_query, n_probe)"""
+    n_query, n_probe = cell_start.shape
+    assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
+    assert cell_start.dtype == cell_size.dtype == torch.int64
+    assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
+    if is_empty is not None:
+        assert is_empty.shape == (n_data,) and is_empty.dtype == torch.uint8
+    return n_query, n_probe
+
+
+def _split_and_workspace(scan, workspace_bytes, n_query, k, n_split, slots_hint, device):
+    """What the IVFFlat and IVFPQ4 top-k wrappers do before their call, for a batch that is not empty: pick n_split
+    (recorded in scan.last_n_split) and size the workspace with the library's `workspace_bytes(n_query, k, n_split)`.
+    Returns (n_split, ws, ws_bytes)."""
+    if n_split is None:
+        n_split = scan._n_split(n_query, device, slots_hint)
+    scan.last_n_split = n_split
+    ws_bytes = workspace_bytes(n_query, k, n_split)
+    ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+    return n_split, ws, ws_bytes
+
+
 class IVFFlatTopkHip:
     """The list scan of IVFFlatIndex (tpq_ivfflat_scan_topk, csrc/scan_flat.hip): the probed cells hold the vectors
     themselves; value and order are defined in include/torchpq_amd.h."""
@@ -496,11 +520,7 @@ class IVFFlatTopkHip:
         n_query, n_probe = cell_start.shape
         assert query.shape == (d, n_query)
         assert vectors.dtype == query.dtype == torch.float32
-        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
-        assert cell_start.dtype == cell_size.dtype == torch.int64
-        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
-        if is_empty is not None:
-            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
         assert distance in ("euclidean", "cosine", "inner")
         assert 0 < k <= 1024
         query = query.contiguous()
@@ -509,11 +529,8 @@ class IVFFlatTopkHip:
         values, address = alloc_pair(n_query, k, device)
         if n_query == 0:
             return values, address
-        if n_split is None:
-            n_split = self._n_split(n_query, device, slots_hint)
-        self.last_n_split = n_split
-        ws_bytes = load().tpq_ivfflat_scan_workspace_bytes(n_query, k, n_split)
-        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfflat_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
         call("tpq_ivfflat_scan_topk", device,
              ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
              ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
@@ -549,11 +566,7 @@ class IVFPQ4TopkHip:
         assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
         assert query.shape == (m * ds, n_query)
         assert query.dtype == codebook.dtype == torch.float32
-        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
-        assert cell_start.dtype == cell_size.dtype == torch.int64
-        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
-        if is_empty is not None:
-            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
         assert distance in ("euclidean", "cosine", "inner")
         assert 0 < k <= 1024
         query = query.contiguous()
@@ -564,11 +577,8 @@ class IVFPQ4TopkHip:
         values, address = alloc_pair(n_query, k, device)
         if n_query == 0:
             return values, address
-        if n_split is None:
-            n_split = self._n_split(n_query, device, slots_hint)
-        self.last_n_split = n_split
-        ws_bytes = load().tpq_ivfpq4_scan_workspace_bytes(n_query, k, n_split)
-        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
         call("tpq_ivfpq4_scan_topk", device,
              ptr(codes), ptr(query), ptr(codebook), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
              ptr(values), ptr(address), n_slots, m, ds, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
@@ -603,11 +613,7 @@ class IVFFlatRangeHip:
         n_query, n_probe = cell_start.shape
         assert query.shape == (d, n_query)
         assert vectors.dtype == query.dtype == torch.float32
-        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
-        assert cell_start.dtype == cell_size.dtype == torch.int64
-        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
-        if is_empty is not None:
-            assert is_empty.shape == (n_slots,) and is_empty.dtype == torch.uint8
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
         assert distance in ("euclidean", "cosine", "inner")
         threshold = _checked_threshold(threshold, n_query)
         query = query.contiguous()
@@ -645,11 +651,7 @@ class IVFPQRangeHip:
         n_data = data.shape[1]
         n_query, n_probe = cell_start.shape
         assert data.shape == (self.m // 4, n_data, 4) and data.dtype == torch.uint8
-        assert cell_size.shape == (n_query, n_probe) and n_probe >= 1
-        assert cell_start.dtype == cell_size.dtype == torch.int64
-        assert n_probe_list.shape == (n_query,) and n_probe_list.dtype == torch.int64
-        if is_empty is not None:
-            assert is_empty.shape == (n_data,) and is_empty.dtype == torch.uint8
+        _check_lists(n_data, is_empty, cell_start, cell_size, n_probe_list)
         return n_data, n_query, n_probe
 
     def _check_fused(self, query, codebook, n_query):
