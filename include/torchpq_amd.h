@@ -603,6 +603,41 @@ int tpq_ivfpq4_scan_topk(const uint8_t* codes, const float* query, const float* 
                          tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQ4Index list scan + top-k over RESIDUAL codes (IVFPQ4Index(pq_use_residual=True)): a slot of cell c holds the
+ * 4-bit code of x - centroid(c), so the table depends on the probe.  No reference counterpart.
+ *
+ * codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, n_slots, m, ds, nq,
+ * max_nprobe, k, metric, n_split, workspace: as tpq_ivfpq4_scan_topk
+ * centroids    f32 [n_cells][d], cell-major: one centroid is one contiguous row (the TRANSPOSE of the coarse
+ *              codebook [d][n_cells] of tpq_ivfpq_coarse_probe)
+ * cells        i64 [nq][max_nprobe]: the probed cells, in the positions of cell_start / cell_size
+ *
+ * All fp32, no fma, each operation rounded on its own.  Reconstruction of dimension j*ds + i of a code of probe p
+ * whose sub-quantizer j holds centroid index c:
+ *       y = centroids[cells[q][p]][j*ds + i] + codebook[j][i][c]                     (one add)
+ * Table entry of (p, j, c), i ascending, e starts at 0.f:
+ *       TPQ_METRIC_NEG_SQ_L2:  t = q[j*ds + i] - y;  e = e - t*t
+ *       TPQ_METRIC_INNER:      e = e + q[j*ds + i] * y
+ * Value of a slot scanned under probe p:  v = 0.f;  for j = 0 ... m - 1 ascending:  v = v + table_p[j][code_j].
+ * So the value is the metric between the query and the vector centroid + codeword, summed sub-vector by sub-vector;
+ * with all-zero centroids it is tpq_ivfpq4_scan_topk's, bit for bit.  The tables (m x 16 floats per query and probe)
+ * are built inside the scan workgroup, once per scanned probe and part, and never exist in memory.
+ * Candidates, the skipped duplicate probe, the cut at the storage, tombstones, the exclusion of NaN values, the order
+ * (value descending, address ascending), the padding and the independence of n_split are exactly those of
+ * tpq_ivfpq4_scan_topk (a slot of two overlapping cells is valued under each probe that scans it).
+ * A cell index outside [0, n_cells) in a scanned probe is the caller's error; it is clamped into the range, so nothing
+ * outside `centroids` is read.  Unsupported shapes as tpq_ivfpq4_scan_topk (the LDS holds two buffers of up to eight
+ * tables here, 64 KiB at most, next to the query); n_cells < 1 or a null centroids / cells is TPQ_ERR_INVALID_ARGUMENT; nothing is launched.
+ * Workspace: tpq_ivfpq4_scan_workspace_bytes(nq, k, n_split) bytes.  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+int tpq_ivfpq4_scan_residual_topk(const uint8_t* codes, const float* query, const float* codebook,
+                                  const float* centroids, const int64_t* cells, int n_cells, const uint8_t* is_empty,
+                                  const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                  float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq,
+                                  int max_nprobe, int k, int metric, int n_split, void* workspace,
+                                  size_t workspace_bytes, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * IVFFlatIndex range search: every stored vector of the probed cells whose value reaches a threshold (no
  * reference counterpart).  vectors, query, is_empty, cell_start, cell_size, n_probe_list, n_slots, d, nq,
  * max_nprobe, metric and n_split are those of tpq_ivfflat_scan_topk.

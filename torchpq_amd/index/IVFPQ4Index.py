@@ -5,21 +5,31 @@ n_subvectors.  The container is CellContainer unchanged with code_size = n_subve
 `_storage` is uint8 [n_subvectors // 8, capacity, 4]; the list scan (tpq_ivfpq4_scan_topk, csrc/scan_pq4.hip) reads it
 in place -- a 16-entry table row has no LDS bank conflicts whatever the codes are, so there is no scan-layout copy --
 and builds the query's table (n_subvectors x 16 floats) inside the scan workgroup.  add / expand / remove / tombstones /
-`_address2id` / state_dict are the container's.  No residual PQ, no range search, no captured graph.
+`_address2id` / state_dict are the container's.  No range search, no captured graph.
+
+`pq_use_residual=True` (semantically IVFPQIndex's): the PQ is learnt on, and a slot holds the code of,
+x - centroid(cell(x)); `encode` returns (pq_code, vq_code) and `decode` takes that pair and returns centroid + codeword.
+The list scan is then tpq_ivfpq4_scan_residual_topk: the scan workgroup rebuilds its n_subvectors x 16 table for every
+probe from the query, the codebook and the probed cell's centroid, so a value is the metric between the query and exactly
+what `decode` returns, and no table exists in memory.  The only derived state is a cell-major copy of the coarse codebook
+([n_cells, d_vector] floats), cached, rebuilt when the coarse codebook changes and not part of the state_dict.  For
+"cosine" the residuals are those of the normalised vectors and a value is the inner product with the reconstruction.
 
 The coarse step is IVFPQIndex's (index/_coarse.py).
 """
 import torch
 
+from .. import util
 from ..codec import PQ4Codec
 from ..container import CellContainer
-from ..kernels import IVFPQ4TopkHip
+from ..kernels import IVFPQ4ResidualTopkHip, IVFPQ4TopkHip
 from ._coarse import CoarseProbeMixin
 
 
 class IVFPQ4Index(CoarseProbeMixin, CellContainer):
     def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None, expand_step_size=128,
-                 expand_mode="double", distance="euclidean", device="cuda:0", verbose=0):
+                 expand_mode="double", distance="euclidean", device="cuda:0", pq_use_residual=False,
+                 verbose=0):
         if torch.device(device).type == "cuda":
             assert torch.cuda.is_available(), "cuda is not available"
         assert d_vector % n_subvectors == 0
@@ -35,10 +45,11 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
         self.d_subvector = d_vector // n_subvectors
         self.distance = distance
         self.verbose = verbose
+        self.pq_use_residual = bool(pq_use_residual)
         self.use_cublas = True
         self._init_coarse(n_cells, verbose)
         self.pq_codec = PQ4Codec(d_vector=d_vector, n_subvectors=n_subvectors, distance=distance, verbose=verbose)
-        self._pq4_topk = IVFPQ4TopkHip(m=n_subvectors)
+        self._pq4_topk = (IVFPQ4ResidualTopkHip if self.pq_use_residual else IVFPQ4TopkHip)(m=n_subvectors)
         self.to(device)
 
     # ---- knobs (as IVFPQIndex) -------------------------------------------------------------------------
@@ -68,7 +79,8 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
 
     # ---- train / encode / add --------------------------------------------------------------------------
     def train(self, x, force_retrain=False):
-        """x [d_vector, n_data] f32: coarse k-means (n_cells) then 16-centroid PQ codebooks."""
+        """x [d_vector, n_data] f32: coarse k-means (n_cells) then 16-centroid PQ codebooks (of the residuals
+        x - centroid(cell(x)) with pq_use_residual; the caller's tensor is left as it is)."""
         if self.vq_codec.is_trained and self.pq_codec.is_trained and not force_retrain:
             self.print_message("index is already trained", 1)
             return
@@ -76,15 +88,33 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
         self.print_message("start training VQ codec...", 1)
         self.vq_codec.train(x)
         self.print_message("start training PQ codec...", 1)
-        self.pq_codec.train(x)
+        self.pq_codec.train(self._residual(x, self.vq_codec.encode(x)) if self.pq_use_residual else x)
         self.print_message("index is trained successfully!", 1)
 
+    def _residual(self, x, vq_code):
+        """a prepared x minus the centroids of `vq_code`, in a tensor of its own"""
+        return (x - self.vq_codec.decode(vq_code)).contiguous()
+
+    def _encode_raw(self, x):
+        """(pq_code, vq_code) of a prepared x: the residual's code with pq_use_residual"""
+        vq_code = self.vq_codec.encode(x)
+        return self.pq_codec.encode(self._residual(x, vq_code) if self.pq_use_residual else x), vq_code
+
     def encode(self, x):
-        """x [d_vector, n] f32 -> packed PQ codes [n_subvectors // 2, n] uint8"""
-        return self.pq_codec.encode(self._prepare(x))
+        """x [d_vector, n] f32 -> packed PQ codes [n_subvectors // 2, n] uint8; with pq_use_residual the pair
+        (pq_code, vq_code [n] int64) of the residual x - centroid"""
+        x = self._prepare(x)
+        return self._encode_raw(x) if self.pq_use_residual else self.pq_codec.encode(x)
 
     def decode(self, x):
-        """packed codes [n_subvectors // 2, n] uint8 -> [d_vector, n] f32"""
+        """packed codes [n_subvectors // 2, n] uint8 -> [d_vector, n] f32; with pq_use_residual `x` is the pair
+        (pq_code, vq_code) and the result is centroid + codeword (one fp32 add: what the list scan values)"""
+        if self.pq_use_residual:
+            assert len(x) == 2
+            pq_code, vq_code = x
+            assert pq_code.shape[0] * 2 == self.n_subvectors
+            assert pq_code.shape[1] == vq_code.shape[0]
+            return self.vq_codec.decode(vq_code.to(self.device)) + self.pq_codec.decode(pq_code.to(self.device))
         assert len(x.shape) == 2
         assert x.shape[0] * 2 == self.n_subvectors
         return self.pq_codec.decode(x.to(self.device))
@@ -92,21 +122,30 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
     def add(self, x, ids=None, return_address=False):
         """x [d_vector, n] f32, optional ids [n] int64 (default arange + max_id + 1);
         returns ids (and the slot addresses if return_address)."""
-        x = self._prepare(x)
-        assigned_cells = self.vq_codec.encode(x)
-        codes = self.pq_codec.encode(x)
+        codes, assigned_cells = self._encode_raw(self._prepare(x))
         return super().add(codes, cells=assigned_cells, ids=ids, return_address=return_address)
 
     # ---- search ----------------------------------------------------------------------------------------
+    def _cell_major_centroids(self):
+        """the coarse codebook [d_vector, n_cells] as [n_cells, d_vector] (one centroid per row, what the residual
+        scan reads), rebuilt when the codebook changes: the identity-and-version cache of _probe_prepared"""
+        cb = self.vq_codec.codebook
+        key = (cb.data_ptr(), tuple(cb.shape), util.tensor_version(cb))
+        cached = getattr(self, "_centroid_rows_cache", None)
+        if cached is None or cached[0] != key or cached[2] is not cb or cb.is_inference():
+            self._centroid_rows_cache = cached = (key, cb.t().contiguous(), cb)
+        return cached[1]
+
     def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
         (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
         the coarse step already gathered them.)"""
         n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
                                                                                         _extents)
+        tables = (self._cell_major_centroids(), cells) if self.pq_use_residual else ()
         vals, address = self._pq4_topk(
-            self._storage, x, self.pq_codec.codebook, cell_start, cell_size, n_probe_list, k, is_empty=is_empty,
-            distance=self.distance, slots_hint=slots_hint)
+            self._storage, x, self.pq_codec.codebook, *tables, cell_start, cell_size, n_probe_list, k,
+            is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
         ids = self.get_id_by_address(address)
         return (vals, ids, address) if return_address else (vals, ids)
 

@@ -586,6 +586,57 @@ class IVFPQ4TopkHip:
         return values, address
 
 
+class IVFPQ4ResidualTopkHip:
+    """The list scan of IVFPQ4Index(pq_use_residual=True) (tpq_ivfpq4_scan_residual_topk, csrc/scan_pq4.hip): 4-bit
+    codes of x - centroid(cell); the table of every scanned probe is built inside the scan workgroup from the query,
+    the codebook and the probed cell's centroid; defined in include/torchpq_amd.h."""
+
+    def __init__(self, m=8):
+        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    _n_split = IVFFlatTopkHip._n_split
+
+    def __call__(self, codes, query, codebook, centroids, cells, cell_start, cell_size, n_probe_list, k,
+                 is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
+        """
+          codes, query, codebook, cell_start, cell_size, n_probe_list, is_empty: as IVFPQ4TopkHip
+          centroids: [n_cells, d] float32, one coarse centroid per row
+          cells: [n_query, max_n_probe] int64, the probed cells (values in [0, n_cells))
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        n_slots = codes.shape[1]
+        m, ds, kk = codebook.shape
+        n_query, n_probe = cell_start.shape
+        assert m == self.m and kk == 16 and ds >= 1
+        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == centroids.dtype == torch.float32
+        assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
+        assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        centroids = centroids.contiguous()
+        cells, cell_start, cell_size = cells.contiguous(), cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(codes, query, codebook, centroids, cells, is_empty, cell_start, cell_size, n_probe_list)
+        device = codes.device
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
+        call("tpq_ivfpq4_scan_residual_topk", device,
+             ptr(codes), ptr(query), ptr(codebook), ptr(centroids), ptr(cells), centroids.shape[0], ptr(is_empty),
+             ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(values), ptr(address), n_slots, m, ds, n_query,
+             n_probe, k, metric_code(distance), n_split, ptr(ws), ws_bytes)
+        return values, address
+
+
 class IVFFlatRangeHip:
     """Range search over the lists of IVFFlatIndex (tpq_ivfflat_range_count / tpq_ivfflat_range_fill,
     csrc/scan_flat.hip): every candidate of IVFFlatTopkHip whose value is >= the query's threshold, in scan order;
