@@ -195,6 +195,51 @@ int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes, 
                                    int nq, int max_nprobe, int m, int k, int n_split, void* workspace,
                                    size_t workspace_bytes, int32_t* tickets, int64_t slots_hint,
                                    tpq_stream_t stream);
+/* The cell-major form of the m = 64 large-batch route (TPQ_SCAN_ROUTE_DUMP_SEL16).
+ * tpq_ivfpq_search_fused_cells: the arguments of tpq_ivfpq_search_fused_tickets plus the probed cells themselves --
+ * `cells` i64 [nq][max_nprobe], the ids behind cell_start / cell_size, in [0, n_cells); NULL gives
+ * tpq_ivfpq_search_fused_tickets.  On a cell-dense batch (every code byte is read by hundreds of queries) the call then
+ *   1. runs the route over each query's first 4 probes only: its exact top-k of those cells, tau_q = the k-th value;
+ *   2. seeds the query's lists with that top-k;
+ *   3. lists the remaining (query, probe) pairs by cell;
+ *   4. decodes every listed cell once per 128 of its queries and takes the values of all of them from fp16 matrix-core
+ *      products (three products of two-piece splits; rigorous error bound delta_q), appending every slot that may reach
+ *      tau_q to the query's list;
+ *   5. evaluates the lists exactly with the route's own finish kernel and redoes flagged queries (a list that overflowed,
+ *      a NaN / Inf query, a cell id out of range, data outside the fp16 scale's range) with the exact kernel.
+ * Same results, bit for bit.  All on `stream`, no host read, no allocation; the workspace is the one
+ * tpq_ivfpq_scan_workspace_bytes sizes, and a smaller one keeps the query-major path.
+ * tpq_ivfpq_scan_cell_major answers, without launching anything, whether a call with these arguments -- those of
+ * tpq_ivfpq_scan_route, the number of cells, the slots of the storage and the workspace size the caller passes -- takes
+ * the form when it hands over its cells: 1 / 0, or -1 for arguments the entry points reject.  The rule: the four-wave
+ * route, k <= 128, more than 4 probes, nq * slots_hint / n_slots >= 96 and room in the workspace behind the lists in use.
+ * tpq_ivfpq_cell_candidates is steps 3-4 on their own, with the caller's thresholds (m == 64, ds 1 or 2): for the
+ * probes first_probe <= p < n_probe_list[q] of every query, every live slot whose fast value is >= threshold[q] - delta_q.
+ *   out_count i32 [nq]             candidates admitted (beyond `capacity`: counted, not stored, out_flags[q] = 1)
+ *   out_keys  u32 [nq][capacity]   order-preserving image of the fast value (a float f: bits | 2^31 when f >= 0, ~bits
+ *                                  otherwise), in no particular order; out_addr u32 [nq][capacity]: ~slot; entries past
+ *                                  the count hold ~(2^31 - 1) in out_addr and nothing in out_keys
+ *   out_delta f32 [nq]             2 delta_q: every stored slot's exact value is >= threshold[q] - 2 delta_q
+ *   out_flags i32 [nq]             1: the query took no part (NaN / Inf, a cell out of range, unscalable) or overflowed
+ * capacity: a multiple of 64; workspace: tpq_ivfpq_cell_candidates_workspace_bytes. */
+int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes, const float* query,
+                                 const float* codebook, int ds, int metric, const uint8_t* is_empty,
+                                 const int64_t* cell_start, const int64_t* cell_size,
+                                 const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
+                                 const int64_t* address2id, int64_t* out_ids, int64_t n_slots,
+                                 int nq, int max_nprobe, int m, int k, int n_split, void* workspace,
+                                 size_t workspace_bytes, int32_t* tickets, int64_t slots_hint,
+                                 const int64_t* cells, int n_cells, tpq_stream_t stream);
+int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
+                              int has_packed, int has_tickets, int residual, int n_cells, int64_t n_slots,
+                              size_t workspace_bytes);
+size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe);
+int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const float* codebook, int ds, int metric,
+                              const uint8_t* is_empty, const int64_t* cell_start, const int64_t* cell_size,
+                              const int64_t* n_probe_list, const int64_t* cells, int n_cells, int first_probe,
+                              const float* threshold, int64_t n_slots, int nq, int max_nprobe, int m, int capacity,
+                              int32_t* out_count, uint32_t* out_keys, uint32_t* out_addr, float* out_delta,
+                              int32_t* out_flags, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * SURVEY 8(f)-3  residual-PQ list scan (pq_use_residual=True)

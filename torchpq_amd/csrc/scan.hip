@@ -30,6 +30,7 @@
 #include <atomic>
 #include <chrono>
 
+#include "scan_cells.h"
 #include "scan_device.h"
 #include "scan_order.h"
 #include "scan_ref.h"
@@ -104,9 +105,11 @@ struct PackedUnit {
   int (*pool)(const ScanArgs& a, int RL, hipStream_t st);
   int (*dump)(const ScanArgs& a, int RL, int Rf, int mode, hipStream_t st);
   int (*dump_occupancy)(int mode);
+  int (*finish)(const ScanArgs& a, int chunks, int Rf, hipStream_t st);
 };
 static const PackedUnit* packed_unit(int m) {
-#define TPQ_UNIT(M) {M, dispatch_packed_##M, dispatch_pool_##M, dispatch_dump_##M, dump_occupancy_##M},
+#define TPQ_UNIT(M) \
+  {M, dispatch_packed_##M, dispatch_pool_##M, dispatch_dump_##M, dump_occupancy_##M, dispatch_finish_##M},
   static const PackedUnit units[] = {TPQ_PACKED_M_LIST(TPQ_UNIT)};
 #undef TPQ_UNIT
   for (const PackedUnit& u : units)
@@ -393,8 +396,87 @@ extern "C" int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds,
   return p.ordered ? 1 : 0;
 }
 
+// ---- the cell-major form of the m = 64 large-batch route (scan_cells.hip) ---------------------------
+// The route stays TPQ_SCAN_ROUTE_DUMP_SEL16; the form is what a call that hands over its probed cells runs when
+//  * the plan is the four-wave route (fused table, ds <= 2, >= 1 024 queries), k <= 128, more than kCellP0 probes;
+//  * the batch is cell-dense: the mean code byte is read nq x slots_hint / n_slots >= kCellMinRereads times;
+//  * the query's lists as 16 (or 8) chunks of 64 keys -- the finish kernel's forms -- and the inversion arrays fit the
+//    workspace: behind the lists in use, as the order does; tpq_ivfpq_scan_workspace_bytes stays what it is.
+// Pure host arithmetic: tpq_ivfpq_scan_cell_major answers without a GPU.  Returns the chunks per query, 0 = today's path.
+struct CellMajor {
+  const int64_t* cells;  // [nq][max_nprobe]
+  int n_cells;
+};
+static int cell_major_chunks(const ScanArgs& a, const ScanPlan& p, bool residual, int n_cells, size_t workspace_bytes) {
+  if (residual || p.route != TPQ_SCAN_ROUTE_DUMP_SEL16 || a.lut || a.m != 64 || a.ds < 1 || a.ds > 2) return 0;
+  if (a.k > 128 || a.max_nprobe <= kCellP0 || n_cells < 1 || a.n_slots <= 0 || a.slots_hint <= 0) return 0;
+  if ((int64_t)a.nq * a.slots_hint < (int64_t)kCellMinRereads * a.n_slots) return 0;
+  if ((int64_t)a.nq * a.max_nprobe >= 0x7fffffffLL) return 0;
+  const size_t extra = cell_extra_bytes(a.nq, a.max_nprobe, n_cells, kCellP0);
+  for (int chunks = 16; chunks >= 8; chunks >>= 1)
+    if ((a.k + 63) / 64 < chunks && workspace_bytes >= ws_bytes_for(a.nq, 1, chunks) + extra) return chunks;
+  return 0;
+}
+
+// stages 1-5 (the flag-gated redo over ALL probes is the caller's next line, as on every dump route)
+static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const CellMajor& cm, int chunks, void* workspace,
+                          size_t workspace_bytes, hipStream_t st) {
+  const int nq = a.nq;
+  // 1. the threshold pass: today's route -- order, split tail, scan, finish -- over each query's first kCellP0 probes;
+  //    it leaves the exact top-k of those cells in out_vals / out_addr
+  ScanArgs t = a;
+  t.probe_cap = kCellP0;
+  plan_dump_dispatch(p, nq, dump_slots(u, p.mode), workspace_bytes);
+  t.n_split = p.parts;
+  t.unsplit = p.unsplit;
+  const size_t lists_bytes = ws_bytes_for(nq, p.RL, p.parts * p.waves);
+  int rc = need_ws(workspace, workspace_bytes, lists_bytes, "ivfpq_scan_packed");
+  if (rc) return rc;
+  fill_ws(t, workspace, p.RL, p.parts * p.waves);
+  if (p.ordered) {
+    int* o = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + lists_bytes);
+    const size_t stride = order_ws_bytes(nq) / 3 / sizeof(int);
+    rc = launch_scan_order(a.cell_start, a.cell_size, a.n_probe_list, nq, a.max_nprobe, packed_tile_shift(a.m), o,
+                           o + stride, o + 2 * stride, st, kCellP0);
+    if (rc) return rc;
+    t.order = o;
+    t.rank = o + stride;
+  }
+  rc = u.dump(t, p.RL, p.Rf, p.mode, st);
+  if (rc) return rc;
+  // 2-4. seeds, inversion, candidates: the query's lists are `chunks` lists of one chunk each from here on
+  a.n_split = 1;
+  a.unsplit = 0;
+  fill_ws(a, workspace, 1, chunks);
+  CellArgs c{};
+  c.codes = a.codes; c.query = a.query; c.codebook = a.codebook; c.is_empty = a.is_empty;
+  c.cell_start = a.cell_start; c.cell_size = a.cell_size; c.n_probe_list = a.n_probe_list; c.cells = cm.cells;
+  c.n_slots = a.n_slots; c.nq = nq; c.max_nprobe = a.max_nprobe; c.n_cells = cm.n_cells; c.ds = a.ds;
+  c.euclid = a.euclid; c.p0 = kCellP0; c.k = a.k; c.chunks = chunks; c.epoch = a.epoch; c.rel = cell_delta_rel(a.ds);
+  c.seed_vals = a.out_vals; c.seed_addr = a.out_addr;
+  c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
+  c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
+  cell_fill_extras(c, reinterpret_cast<char*>(workspace) + ws_bytes_for(nq, 1, chunks));
+  rc = launch_cell_candidates(c, st);
+  if (rc) return rc;
+  // 5. the finish kernel over the filled chunks: F_k, the cut at F_k - 2 delta_q, the survivors -- seeds included --
+  //    evaluated exactly
+  return u.finish(a, chunks, p.Rf, st);
+}
+
+extern "C" int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                         int has_lut, int has_packed, int has_tickets, int residual, int n_cells,
+                                         int64_t n_slots, size_t workspace_bytes) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return 0;
+  ScanArgs a = route_query_args(nq, k, n_split, m, ds, max_nprobe, slots_hint, has_lut, has_tickets);
+  a.n_slots = n_slots;
+  const ScanPlan p = plan_scan(a, residual != 0);
+  return cell_major_chunks(a, p, residual != 0, n_cells, workspace_bytes) ? 1 : 0;
+}
+
 static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
-                      tpq_stream_t stream) {
+                      tpq_stream_t stream, const CellMajor* cm = nullptr) {
   int rc = validate(a);
   if (rc) return rc;
   TPQ_REQUIRE(a.packed != nullptr, "ivfpq_scan_packed: null packed pointer");
@@ -436,6 +518,10 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
     case TPQ_SCAN_ROUTE_DUMP_F32:
     case TPQ_SCAN_ROUTE_DUMP_SEL16:
     case TPQ_SCAN_ROUTE_DUMP_SEL16_W8: {
+      if (const int chunks = cm ? cell_major_chunks(a, p, ra != nullptr, cm->n_cells, workspace ? workspace_bytes : 0) : 0) {
+        rc = run_cell_major(a, p, u, *cm, chunks, workspace, workspace_bytes, st);
+        break;
+      }
       plan_dump_dispatch(p, nq, dump_slots(u, p.mode), workspace ? workspace_bytes : 0);
       a.n_split = p.parts;
       a.unsplit = p.unsplit;
@@ -447,7 +533,7 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
         int* o = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + lists_bytes);
         const size_t stride = order_ws_bytes(nq) / 3 / sizeof(int);
         rc = launch_scan_order(a.cell_start, a.cell_size, a.n_probe_list, nq, a.max_nprobe, packed_tile_shift(a.m), o,
-                               o + stride, o + 2 * stride, st);
+                               o + stride, o + 2 * stride, st, 0);
         if (rc) return rc;
         a.order = o;
         a.rank = o + stride;
@@ -471,6 +557,29 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
 // ---- entry points (their ScanArgs: scan_args, scan_list.h) ---------------------------------------------
 extern "C" size_t tpq_ivfpq_scan_tickets_bytes(int nq) { return nq > 0 ? (size_t)nq * sizeof(int32_t) : 0; }
 
+extern "C" int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes,
+                                            const float* query, const float* codebook, int ds,
+                                            int metric, const uint8_t* is_empty,
+                                            const int64_t* cell_start, const int64_t* cell_size,
+                                            const int64_t* n_probe_list, float* out_vals,
+                                            int64_t* out_addr, const int64_t* address2id,
+                                            int64_t* out_ids, int64_t n_slots, int nq, int max_nprobe,
+                                            int m, int k, int n_split, void* workspace,
+                                            size_t workspace_bytes, int32_t* tickets,
+                                            int64_t slots_hint, const int64_t* cells, int n_cells,
+                                            tpq_stream_t stream) {
+  TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER,
+              "ivfpq_search_fused: bad metric %d", metric);
+  TPQ_REQUIRE(ds >= 1 && ds <= 1024, "ivfpq_search_fused: bad sub-vector length %d", ds);
+  ScanArgs a = scan_args(codes, packed, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  a.query = query; a.codebook = codebook; a.ds = ds; a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
+  a.tickets = tickets; a.slots_hint = slots_hint;
+  const CellMajor cm{cells, n_cells};
+  return packed ? run_packed(a, nullptr, workspace, workspace_bytes, stream, cells ? &cm : nullptr)
+                : run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes,
                                               const float* query, const float* codebook, int ds,
                                               int metric, const uint8_t* is_empty,
@@ -481,15 +590,9 @@ extern "C" int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8
                                               int m, int k, int n_split, void* workspace,
                                               size_t workspace_bytes, int32_t* tickets,
                                               int64_t slots_hint, tpq_stream_t stream) {
-  TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER,
-              "ivfpq_search_fused: bad metric %d", metric);
-  TPQ_REQUIRE(ds >= 1 && ds <= 1024, "ivfpq_search_fused: bad sub-vector length %d", ds);
-  ScanArgs a = scan_args(codes, packed, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
-                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
-  a.query = query; a.codebook = codebook; a.ds = ds; a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
-  a.tickets = tickets; a.slots_hint = slots_hint;
-  return packed ? run_packed(a, nullptr, workspace, workspace_bytes, stream)
-                : run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return tpq_ivfpq_search_fused_cells(packed, codes, query, codebook, ds, metric, is_empty, cell_start, cell_size,
+                                      n_probe_list, out_vals, out_addr, address2id, out_ids, n_slots, nq, max_nprobe, m,
+                                      k, n_split, workspace, workspace_bytes, tickets, slots_hint, nullptr, 0, stream);
 }
 
 extern "C" int tpq_ivfpq_search_fused(const uint8_t* packed, const uint8_t* codes,

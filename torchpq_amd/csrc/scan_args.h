@@ -79,6 +79,9 @@ struct ScanArgs {
   // indexed by the query, as before: the results do not depend on the order.
   const int* order;
   const int* rank;
+  // probe cap (the cell-major form's threshold pass, scan_cells.h): every kernel that walks a query's probes takes
+  // min(n_probe_list[q], probe_cap) of them -- clamped_n_probe (scan_list.h), scan_work_kernel.  0 = no cap.
+  int probe_cap;
 };
 
 // scan_packed_kernel modes beyond the fused finish (RM > 0) and the pools (RM = -1, -2, -3): "dump" -- the scan

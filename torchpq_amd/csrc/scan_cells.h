@@ -1,0 +1,70 @@
+// IVF list scan, cell-major form of the m = 64 large-batch route (scan_cells.hip): what scan.hip and the unit share.
+#pragma once
+#include "common.h"
+
+namespace tpq {
+
+// probes per query the threshold pass scans with the query-major route (profiles/cell_major_bench.json)
+#ifndef TPQ_CELL_P0
+#define TPQ_CELL_P0 4  // (variant builds: the A/B of 3, 4 and 6)
+#endif
+constexpr int kCellP0 = TPQ_CELL_P0;
+// the form applies from this many re-reads of the mean code byte on (nq x slots_hint / n_slots)
+constexpr int kCellMinRereads = 96;
+constexpr int kCellQSplit = 256;  // halfs per query of the split copy: [hi, lo][128 components]
+constexpr int kCellGroup = 32;   // queries per candidate block: the 32 MFMA columns of a wave
+
+struct CellArgs {
+  const uint8_t* codes;          // reference layout [16][n_slots][4]
+  const float* query;            // [64 ds][nq]
+  const float* codebook;         // [64][ds][256]
+  const uint8_t* is_empty;       // nullable
+  const int64_t* cell_start;     // [nq][max_nprobe]
+  const int64_t* cell_size;
+  const int64_t* n_probe_list;   // [nq]
+  const int64_t* cells;          // [nq][max_nprobe]
+  int64_t n_slots;
+  int nq, max_nprobe, n_cells, ds, euclid;
+  int p0;                        // the pairs listed are (q, p), p0 <= p < n_probe_list[q]
+  int k;                         // seeds per query (0: none)
+  int chunks;                    // capacity of a query's lists in chunks of 64 keys, seed chunks included
+  int epoch;                     // flags[q] == epoch: the query takes no part / overflowed
+  float rel;                     // delta_q = rel (|q| + |x|max)^2
+  const float* seed_vals;        // [nq][k]: the threshold pass's result, tau_q = its k-th value ...
+  const int64_t* seed_addr;
+  const float* thr_in;           // ... or (k == 0) the caller's thresholds [nq]
+  unsigned* keys;                // [nq][chunks * 64] value images
+  unsigned* idx;                 // [nq][chunks * 64] ~address
+  int* list_evict;               // [nq][chunks], zeroed (nullable)
+  int* flags;                    // [nq]
+  float* ws_delta;               // [nq] <- 2 delta_q
+  // behind the lists (cell_extra_bytes): every array rounded up to 256 bytes
+  float* params;                 // [4] max |codebook|, sum_j max_c |c_jc|^2, 0 / 1: the codebook can be scaled
+  float* thr;                    // [nq] tau_q - delta_q
+  float* qscale;                 // [nq] the query's power-of-two scale
+  float* qnorm;                  // [nq] |q|^2
+  int* cnt;                      // [nq] candidates admitted (beyond the capacity: counted, not stored)
+  int* hist;                     // [n_cells] pairs per cell, then the scatter's cursor
+  int* cell_off;                 // [n_cells + 1]
+  int* blk_off;                  // [n_cells + 1] exclusive prefix of ceil(pairs / kCellGroup)
+  int* cell_st;                  // [n_cells] start and size of a listed cell
+  int* cell_sz;
+  int* pairs;                    // [nq (max_nprobe - p0)] the queries, grouped by cell
+  _Float16* qsplit;              // [nq][2][128] the fp16 pieces of s_q q (hi, lo)
+};
+
+inline size_t cell_align(size_t x) { return (x + 255) & ~(size_t)255; }
+inline size_t cell_extra_bytes(int nq, int max_nprobe, int n_cells, int p0) {
+  const int np = max_nprobe > p0 ? max_nprobe - p0 : 0;
+  return 256 + 4 * cell_align((size_t)nq * 4) + cell_align((size_t)n_cells * 4) +
+         2 * cell_align(((size_t)n_cells + 1) * 4) + 2 * cell_align((size_t)n_cells * 4) +
+         cell_align((size_t)nq * np * 4) + cell_align((size_t)nq * kCellQSplit * 2);
+}
+// points the extras of `a` into `at` (cell_extra_bytes of it)
+void cell_fill_extras(CellArgs& a, void* at);
+// delta_q / (|q| + |x|max)^2 (derivation: scan_cells.hip)
+float cell_delta_rel(int ds);
+// stages 2-4 on `st`: seed (or the caller's thresholds), inversion, candidates
+int launch_cell_candidates(const CellArgs& a, hipStream_t st);
+
+}  // namespace tpq

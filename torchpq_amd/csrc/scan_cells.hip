@@ -1,0 +1,561 @@
+// IVF list scan, m = 64, large fused batches: the candidates of a batch taken CELL BY CELL on the fp16 matrix cores.
+//
+// The query-major scan (scan_packed_kernel) decodes every code byte once per query that probes its cell: ~300 times
+// per launch on a cell-dense batch.  Here a probed cell is decoded once per group of 32 of its queries -- a look-up of
+// ready-made fp16 pieces, no table address arithmetic per query -- and the values of the group come from one small GEMM,
+// (decoded slots x 64 ds) . (64 ds x queries), on v_mfma_f32_32x32x16_f16.
+// The values are a SELECTION key only: scan.hip seeds each query's lists with the exact top-k of its first kCellP0
+// probes (the query-major route with a probe cap), this unit appends every slot of the other probes that may reach that
+// top-k, and scan_finish_exact_kernel evaluates the lists exactly.  Nothing here selects, merges or redoes.
+//
+// Kernels (all on the caller's stream; no host read, no allocation):
+//   cell_prep_kernel     one block: the codebook's max |entry| (-> the power-of-two scale s_x) and X^2 = sum_j max_c
+//                        |c_jc|^2 >= |x|^2 of every decodable slot; zeroes the histogram.
+//   cell_seed_kernel     one wave per query: tau_q (the k-th seed, or the caller's threshold), the query's scale s_q and
+//                        |q|^2, delta_q, the admission threshold tau_q - delta_q and ws_delta = 2 delta_q; the seeds into the
+//                        first ceil(k / 64) chunks of the query's lists in the finish kernel's format (value image,
+//                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words; the histogram of the
+//                        query's listed probes.  A query that was flagged before, has a non-finite component, norm or
+//                        threshold (NaN, +inf), cannot be scaled or lists a cell outside [0, n_cells) is flagged and takes
+//                        no further part (tau = -inf is a threshold like any other: everything is admitted, and what
+//                        does not fit flags the query below).
+//   cell_scan_kernel     one block: exclusive prefixes of the histogram (pairs) and of ceil(pairs / 32) (blocks).
+//   cell_scatter_kernel  one wave per query: pairs[cursor[cell]++] = q, and the cell's extent.  The order inside a
+//                        cell varies from run to run; nothing downstream depends on it.
+//   cell_cand_kernel     one block of work per (cell, group of <= 32 listed queries), taken by ONE WAVE, query per MFMA
+//                        column: a lane owns one query, threshold and scales in registers, its B operand read as 16-byte
+//                        pieces of the seed kernel's split copy.  One workgroup of eight waves per CU stages the codebook in
+//                        LDS once -- already scaled and split into its two fp16 pieces, 128 KiB at ds = 2 -- and its waves
+//                        take blocks from a counter, independently: no barrier after the staging.  Per tile of 32 slots,
+//                        lane (row, half) reads the 8 code dwords of its half of every k-step from the reference layout
+//                        [16][n_slots][4] (coalesced over slots, one tile ahead) and gathers its A operand straight from
+//                        the codebook in LDS; |x'|^2 rides along (an fma chain over the same pieces, the two half-waves
+//                        added) and reaches the accumulator's rows through 128 bytes of LDS per wave.
+//                        A probe listed twice in a row is skipped as the scan skips it (fetch_probes, scan_shared.h).
+//                        (Measured on the headline batch, 10 000 queries x 28 listed probes: sub-vectors gathered from
+//                        the fp32 codebook in global memory into a staged 128-slot tile, 2.66 ms; this form with the
+//                        queries read from [d][nq] per block, 1.06 ms; with the split copy, 0.91 ms; with the norms of a
+//                        tile read in four 16-byte LDS reads and the codes loaded a tile ahead, 0.81 ms.)
+//
+// Arithmetic.  q' = s_q q = qh + ql + rq,  x' = s_x x = xh + xl + rx  (h = fp16(.), l = fp16(. - h); s_q, s_x powers of
+// two with max |q'_i|, max |s_x c| in [2^12, 2^13): no piece overflows, and the scaling is exact).  Per component
+//   |r| <= 2^-22 |.| + eta,  eta = 2^-14   (a piece below the fp16 normal range, flushed or not).
+// S = sum over the k-steps of (xl qh + xh ql + xh qh) on the MFMA, the small products of a step first, fp32 accumulation;
+//   fast = 2 S / (s_q s_x) - |x|^2 - |q|^2   (euclidean; |x|^2 an fp32 fma chain of the decoding thread over (xh + xl)^2, unscaled; |q|^2
+//   an fp32 sum of the seed kernel)         or   S / (s_q s_x)   (inner product).
+// Against g = 2 q.x - |x|^2 - |q|^2 in real numbers, with Q = |q'|, X = |x'| and B = |q| + |x|max (|x|max^2 = X^2 above;
+// 2 |q| |x| <= B^2 / 2; D = 64 ds components, N = 3 D MFMA terms):
+//   dropped product and piece residues  |ql.xl + rq.x' + (qh + ql).rx| <= 3.03 2^-22 Q X + 1.01 eta sqrt(D) (Q + X)
+//   fp32 accumulation, any order        N roundings of at most 2^-23 sum |terms| <= 1.003 N 2^-23 Q X
+//     -> in value units (x 2 / (s_q s_x)):  (3.03 2^-22 + 1.003 N 2^-23) B^2 / 2  +  1.01 sqrt(D) 2^-26 B^2
+//        (1 / s_x <= 2^-12 |x|max and 1 / s_q <= 2^-12 |q|, so eta (Q + X) / (s_q s_x) <= eta 2^-12 B^2 / 2)
+//   the norm chains                     (D + 1) 2^-24 (|x|^2 + |q|^2) <= (D + 1) 2^-24 B^2
+//   |x|^2 taken from the pieces         sum_i (xh + xl)_i^2 / s_x^2: 2^-21 |x|^2 + 2 eta sqrt(D) |x| / s_x <= 14 2^-24 B^2
+//   the two subtractions, tau - delta   2^-22 B^2
+//   the exact chain's own rounding      the reference's value is sum_j fl(fl(2 dot_j - |q_j|^2) - |c_j|^2), ascending j:
+//                                       (ds + 3) 2^-24 sum_j (|q_j| + |c_j|)^2 + (m - 1) 2^-24 sum_j |val_j|
+//                                       <= 1.001 (m + ds + 2) 2^-24 B^2
+// delta_q = 1.25 x the sum (cell_delta_rel) x B^2, B evaluated upwards.  The inner product's errors are a subset.
+// Every slot whose exact value is >= tau_q has fast >= tau_q - delta_q and is admitted; every admitted slot has an exact
+// value >= tau_q - 2 delta_q.  Rows past the cell's size and tombstones never pass.  A candidate beyond the capacity of
+// the query's lists is not written: the query is flagged for the exact kernel.
+#include <cmath>
+
+#include "mfma_util.h"
+#include "scan_cells.h"
+#include "wave_topk.h"
+
+namespace tpq {
+
+float cell_delta_rel(int ds) {
+  const double D = 64.0 * ds, N = 3.0 * D, u = 1.0 / 16777216.0;  // u = 2^-24
+  const double sum = 0.5 * (3.03 * 4 * u + 1.003 * N * 2 * u) + 1.01 * std::sqrt(D) * u / 4 + (D + 1) * u + 14 * u + 4 * u +
+                     1.001 * (64 + ds + 2) * u;
+  return (float)(1.25 * sum * (1.0 + 1.0 / 1024));  // (+ 2^-10: B^2 and the product are evaluated in fp32)
+}
+
+void cell_fill_extras(CellArgs& a, void* at) {
+  char* p = reinterpret_cast<char*>(at);
+  auto take = [&](size_t bytes) {
+    char* r = p;
+    p += cell_align(bytes);
+    return r;
+  };
+  const int np = a.max_nprobe > a.p0 ? a.max_nprobe - a.p0 : 0;
+  a.params = reinterpret_cast<float*>(take(256));
+  a.thr = reinterpret_cast<float*>(take((size_t)a.nq * 4));
+  a.qscale = reinterpret_cast<float*>(take((size_t)a.nq * 4));
+  a.qnorm = reinterpret_cast<float*>(take((size_t)a.nq * 4));
+  a.cnt = reinterpret_cast<int*>(take((size_t)a.nq * 4));
+  a.hist = reinterpret_cast<int*>(take((size_t)a.n_cells * 4));
+  a.cell_off = reinterpret_cast<int*>(take(((size_t)a.n_cells + 1) * 4));
+  a.blk_off = reinterpret_cast<int*>(take(((size_t)a.n_cells + 1) * 4));
+  a.cell_st = reinterpret_cast<int*>(take((size_t)a.n_cells * 4));
+  a.cell_sz = reinterpret_cast<int*>(take((size_t)a.n_cells * 4));
+  a.pairs = reinterpret_cast<int*>(take((size_t)a.nq * np * 4));
+  a.qsplit = reinterpret_cast<_Float16*>(take((size_t)a.nq * kCellQSplit * 2));
+}
+
+constexpr int kCellScaleExp = 12;   // the largest scaled component lies in [2^12, 2^13)
+constexpr int kCellMaxExp = 40;     // data whose largest component is outside 2^+-40 goes to the exact kernel
+constexpr unsigned kMaxFiniteBits = 0x7f7fffffu;
+
+// 2^e, |e| <= 126
+__device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+__device__ __forceinline__ int exp_of_bits(unsigned bits) { return (int)((bits >> 23) & 255u) - 127; }
+
+__global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
+  __shared__ unsigned maxbits_s;
+  __shared__ float c2max_s[64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) maxbits_s = 0u;
+  for (int i = tid; i < a.n_cells; i += 1024) a.hist[i] = 0;
+  __syncthreads();
+  unsigned mb = 0u;
+  for (int j = wave; j < 64; j += 16) {
+    float c2m = 0.f;
+    for (int c = lane; c < 256; c += 64) {
+      float c2 = 0.f;
+      for (int e = 0; e < a.ds; ++e) {
+        const float y = a.codebook[((int64_t)j * a.ds + e) * 256 + c];
+        const unsigned b = __float_as_uint(y) & 0x7fffffffu;
+        mb = b > mb ? b : mb;
+        c2 = fmaf(y, y, c2);
+      }
+      c2m = fmaxf(c2m, c2);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c2m = fmaxf(c2m, __shfl_xor(c2m, d, 64));
+    if (lane == 0) c2max_s[j] = c2m;
+  }
+  atomicMax(&maxbits_s, mb);
+  __syncthreads();
+  if (tid == 0) {
+    float x2 = 0.f;
+    for (int j = 0; j < 64; ++j) x2 += c2max_s[j];
+    x2 *= 1.0001f;  // (upwards: 64 + ds roundings of 2^-24 each)
+    const unsigned bits = maxbits_s;
+    const int e = exp_of_bits(bits);
+    const bool ok = bits != 0u && bits <= kMaxFiniteBits && e >= -kCellMaxExp && e <= kCellMaxExp && x2 <= 3e38f;
+    a.params[0] = __uint_as_float(bits);
+    a.params[1] = x2;
+    a.params[2] = ok ? 1.f : 0.f;
+    a.params[3] = ok ? pow2i(kCellScaleExp - e) : 0.f;  // s_x
+    reinterpret_cast<int*>(a.params)[8] = 0;            // cell_cand_kernel's block counter
+  }
+}
+
+// the listed probes of query q: p0 <= p < n_probe_list[q] (clamped), the cell not empty and not the previous probe's again
+struct ListedProbe {
+  bool listed;
+  int cell;
+};
+__device__ __forceinline__ int cell_n_probe(const CellArgs& a, int q) {
+  const int n = (int)a.n_probe_list[q];
+  return n < 0 ? 0 : (n > a.max_nprobe ? a.max_nprobe : n);
+}
+__device__ __forceinline__ ListedProbe listed_probe(const CellArgs& a, int q, int p) {
+  const int64_t o = (int64_t)q * a.max_nprobe + p;
+  const int64_t st = a.cell_start[o], sz = a.cell_size[o];
+  const bool again = p > 0 && a.cell_start[o - 1] == st;
+  return ListedProbe{sz > 0 && !again, (int)a.cells[o]};
+}
+
+__global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (q >= a.nq) return;  // (wave-uniform)
+  const int D = 64 * a.ds;
+  const float x0 = lane < D ? a.query[(int64_t)lane * a.nq + q] : 0.f;
+  const float x1 = 64 + lane < D ? a.query[(int64_t)(64 + lane) * a.nq + q] : 0.f;
+  unsigned mb = __float_as_uint(x0) & 0x7fffffffu;
+  const unsigned mb1 = __float_as_uint(x1) & 0x7fffffffu;
+  mb = mb1 > mb ? mb1 : mb;
+  float q2 = fmaf(x1, x1, x0 * x0);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)mb, d, 64);
+    mb = o > mb ? o : mb;
+    q2 += __shfl_xor(q2, d, 64);
+  }
+  const int n_probe = cell_n_probe(a, q);
+  bool bad_cell = false;
+  for (int p = a.p0 + lane; p < n_probe; p += 64) {
+    const int64_t c = a.cells[(int64_t)q * a.max_nprobe + p];
+    bad_cell = bad_cell || c < 0 || c >= (int64_t)a.n_cells;
+  }
+  bad_cell = __ballot(bad_cell) != 0ull;
+  const float tau = a.k > 0 ? a.seed_vals[(int64_t)q * a.k + a.k - 1] : a.thr_in[q];
+  const int eq = exp_of_bits(mb);
+  const bool flagged = a.k > 0 && a.flags[q] == a.epoch;
+  const bool scalable = a.params[2] != 0.f && mb != 0u && mb <= kMaxFiniteBits && eq >= -kCellMaxExp &&
+                        eq <= kCellMaxExp && q2 <= 3e38f;
+  const bool tau_ok = tau == tau && tau != INFINITY;  // (-inf: fewer than k seeds -- everything is admitted)
+  const bool active = !flagged && scalable && tau_ok && !bad_cell;
+  if (!active) {
+    if (lane == 0) {
+      a.flags[q] = a.epoch;
+      a.cnt[q] = 0;
+      a.thr[q] = INFINITY;
+    }
+    return;
+  }
+  const float B = sqrtf(q2) * 1.000001f + sqrtf(a.params[1]) * 1.000001f;
+  const float delta = a.rel * (B * B);
+  if (lane == 0) {
+    a.thr[q] = tau - delta;
+    a.ws_delta[q] = 2.f * delta;
+    a.qscale[q] = pow2i(kCellScaleExp - eq);
+    a.qnorm[q] = q2;
+    a.cnt[q] = 0;
+    if (a.k == 0) a.flags[q] = 0;
+  }
+  if (a.list_evict && lane < a.chunks) a.list_evict[(int64_t)q * a.chunks + lane] = 0;
+  {
+    // the pieces of s_q q, component-major per query: the candidate kernel's B operand is 16 contiguous bytes of it
+    const float sq = pow2i(kCellScaleExp - eq);
+    _Float16* qs = a.qsplit + (int64_t)q * kCellQSplit;
+    const float y0 = x0 * sq, y1 = x1 * sq;
+    const _Float16 h0 = (_Float16)y0, h1 = (_Float16)y1;
+    if (lane < D) {
+      qs[lane] = h0;
+      qs[128 + lane] = (_Float16)(y0 - (float)h0);
+    }
+    if (64 + lane < D) {
+      qs[64 + lane] = h1;
+      qs[192 + lane] = (_Float16)(y1 - (float)h1);
+    }
+  }
+  const int64_t base = (int64_t)q * a.chunks * 64;
+  const int seed_chunks = (a.k + 63) / 64;
+  for (int t = 0; t < a.chunks; ++t) {
+    const int e = t * 64 + lane;
+    Key key = pad_key();
+    if (e < a.k) {
+      const int64_t ad = a.seed_addr[(int64_t)q * a.k + e];
+      if (ad >= 0) key = make_key(a.seed_vals[(int64_t)q * a.k + e], (int)ad);
+    }
+    if (t < seed_chunks) a.keys[base + e] = key.hi;
+    a.idx[base + e] = key.lo;
+  }
+  for (int p = a.p0 + lane; p < n_probe; p += 64) {
+    const ListedProbe lp = listed_probe(a, q, p);
+    if (lp.listed) atomicAdd(&a.hist[lp.cell], 1);
+  }
+}
+
+__global__ __launch_bounds__(1024) void cell_scan_kernel(CellArgs a) {
+  __shared__ int sp[2][1024], sb[2][1024];
+  const int tid = (int)threadIdx.x;
+  const int per = (a.n_cells + 1023) / 1024;
+  const int lo = tid * per < a.n_cells ? tid * per : a.n_cells;
+  const int hi = lo + per < a.n_cells ? lo + per : a.n_cells;
+  int np = 0, nb = 0;
+  for (int c = lo; c < hi; ++c) {
+    const int h = a.hist[c];
+    np += h;
+    nb += (h + kCellGroup - 1) / kCellGroup;
+  }
+  sp[0][tid] = np;
+  sb[0][tid] = nb;
+  __syncthreads();
+  int cur = 0;
+  for (int d = 1; d < 1024; d <<= 1) {  // inclusive scan, double-buffered
+    const int vp = sp[cur][tid] + (tid >= d ? sp[cur][tid - d] : 0);
+    const int vb = sb[cur][tid] + (tid >= d ? sb[cur][tid - d] : 0);
+    sp[cur ^ 1][tid] = vp;
+    sb[cur ^ 1][tid] = vb;
+    cur ^= 1;
+    __syncthreads();
+  }
+  int op = sp[cur][tid] - np, ob = sb[cur][tid] - nb;  // exclusive
+  for (int c = lo; c < hi; ++c) {
+    const int h = a.hist[c];
+    a.cell_off[c] = op;
+    a.blk_off[c] = ob;
+    a.hist[c] = op;  // the scatter's cursor
+    op += h;
+    ob += (h + kCellGroup - 1) / kCellGroup;
+  }
+  if (tid == 1023) {
+    a.cell_off[a.n_cells] = sp[cur][1023];
+    a.blk_off[a.n_cells] = sb[cur][1023];
+  }
+}
+
+__global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (q >= a.nq) return;
+  if (a.flags[q] == a.epoch) return;
+  const int n_probe = cell_n_probe(a, q);
+  for (int p = a.p0 + lane; p < n_probe; p += 64) {
+    const ListedProbe lp = listed_probe(a, q, p);
+    if (!lp.listed) continue;
+    const int pos = atomicAdd(&a.hist[lp.cell], 1);
+    a.pairs[pos] = q;
+    const int64_t o = (int64_t)q * a.max_nprobe + p;
+    a.cell_st[lp.cell] = (int)a.cell_start[o];  // (every query lists the cell with the same extent)
+    a.cell_sz[lp.cell] = (int)a.cell_size[o];
+  }
+}
+
+template <int DS>
+struct CellBook {
+  static constexpr int KS = 4 * DS;                            // MFMA k-steps of 16 components
+  static constexpr size_t kBook = (size_t)64 * 256 * 4 * DS;   // the split codebook: [j][c] -> DS hi pieces, DS lo pieces
+  static constexpr int kWaves = 8;
+  static constexpr size_t kBytes = kBook + kWaves * 32 * 4;    // + per wave: |x|^2 of the tile's 32 rows (NaN: not live)
+};
+
+__device__ __forceinline__ unsigned pack_f16x2(_Float16 lo, _Float16 hi) {
+  return (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
+}
+__device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+
+// One workgroup of eight waves per CU stages the split codebook once; every WAVE then takes blocks -- (cell, group of
+// <= 32 listed queries) -- from a counter (cell_prep_kernel zeroes it) and never meets the others again.  Per tile of 32
+// slots, lane (row, half) loads the 8 code dwords that hold its half of every k-step and gathers its A operand -- the
+// pieces of 8 components -- straight from the codebook in LDS: no staged tile, no barrier.
+template <int DS>
+__global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
+  using T = CellBook<DS>;
+  constexpr int KS = T::KS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned* book = reinterpret_cast<unsigned*>(smem);  // DS = 2: [j][c] (h0 h1, l0 l1); DS = 1: [j][c] (h l)
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* x2w = reinterpret_cast<float*>(smem + T::kBook) + wave * 32;
+  int* work = reinterpret_cast<int*>(a.params) + 8;
+  const int n_blocks = a.blk_off[a.n_cells];
+  const int col = lane & 31, half = lane >> 5;
+  const float sx = a.params[3];
+  const float inv_sx = 1.f / sx;  // (a power of two: exact)
+  const float inv_sx2 = inv_sx * inv_sx;
+  for (int i = tid; i < 64 * 256; i += 512) {  // entry (j, c)
+    const int j = i >> 8, c = i & 255;
+    _Float16 h[DS], l[DS];
+#pragma unroll
+    for (int e = 0; e < DS; ++e) {
+      const float ys = a.codebook[(j * DS + e) * 256 + c] * sx;
+      h[e] = (_Float16)ys;
+      l[e] = (_Float16)(ys - (float)h[e]);
+    }
+    if constexpr (DS == 2) {
+      book[2 * i] = pack_f16x2(h[0], h[1]);
+      book[2 * i + 1] = pack_f16x2(l[0], l[1]);
+    } else {
+      book[i] = pack_f16x2(h[0], l[0]);
+    }
+  }
+  __syncthreads();
+  const int64_t cap = (int64_t)a.chunks * 64;
+  const int seed_entries = ((a.k + 63) / 64) * 64;
+  for (;;) {
+    int b = 0;
+    if (lane == 0) b = atomicAdd(work, 1);
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b >= n_blocks) break;
+    // the block's cell: blk_off[c] <= b < blk_off[c + 1]
+    int lo = 0, hi = a.n_cells;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (a.blk_off[mid] <= b) lo = mid; else hi = mid;
+    }
+    const int c = lo, g = b - a.blk_off[c];
+    const int first = a.cell_off[c] + g * kCellGroup;
+    const int n_listed = a.cell_off[c + 1] - first;
+    const int nqs = n_listed < kCellGroup ? n_listed : kCellGroup;
+    const int64_t st = a.cell_st[c];
+    int sz = a.cell_sz[c];
+    if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (an extent outside the storage is never read)
+    // this lane's query: pieces of s_q q for the B operand, threshold and scales
+    const bool qvalid = col < nqs;
+    const int q = qvalid ? a.pairs[first + col] : 0;
+    const float sq = qvalid ? a.qscale[q] : 0.f;
+    const float thr = qvalid ? a.thr[q] : INFINITY;
+    const float q2 = qvalid ? a.qnorm[q] : 0.f;
+    const float unscale = qvalid ? (1.f / sq) * inv_sx : 0.f;
+    f16x8 qh[KS], ql[KS];
+    const _Float16* __restrict__ qs = a.qsplit + (int64_t)q * kCellQSplit + 8 * half;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      qh[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 16 * s) : z);
+      ql[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 128 + 16 * s) : z);
+    }
+    // the code dwords of this lane's components: k-step s holds components [16 s + 8 half, + 8), i.e. sub-quantizers
+    // [(16 s + 8 half) / DS, + 8 / DS): one dword at ds = 2, two at ds = 1.  Loaded one tile ahead.
+    auto load_tile = [&](int r0, uint32_t (&w)[8], bool& live) {
+      const bool rv = r0 + col < sz;
+      const int64_t slot = st + (rv ? r0 + col : 0);
+      const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(a.codes) + slot;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int gq = DS == 2 ? 2 * i + half : 4 * (i >> 1) + 2 * half + (i & 1);
+        w[i] = rv ? cw[(int64_t)gq * a.n_slots] : 0u;
+      }
+      live = rv && !(a.is_empty && a.is_empty[slot]);
+    };
+    uint32_t w[8], wn[8];
+    bool live = false, live_n = false;
+    if (sz > 0) load_tile(0, w, live);
+    for (int r0 = 0; r0 < sz; r0 += 32) {
+      if (r0 + 32 < sz) load_tile(r0 + 32, wn, live_n);
+      f32x16 acc = zero_f32x16();
+      float x2 = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        u32x4 vh, vl;
+        if constexpr (DS == 2) {
+          const int j0 = 8 * s + 4 * half;
+          uint2 en[4];
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb)
+            en[bb] = reinterpret_cast<const uint2*>(book)[(j0 + bb) * 256 + (int)((w[s] >> (8 * bb)) & 255u)];
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) {
+            const float v0 = f16_lo(en[bb].x) + f16_lo(en[bb].y), v1 = f16_hi(en[bb].x) + f16_hi(en[bb].y);
+            x2 = fmaf(v0, v0, x2);
+            x2 = fmaf(v1, v1, x2);
+          }
+          vh = u32x4{en[0].x, en[1].x, en[2].x, en[3].x};
+          vl = u32x4{en[0].y, en[1].y, en[2].y, en[3].y};
+        } else {
+          const int j0 = 16 * s + 8 * half;
+          unsigned en[8];
+#pragma unroll
+          for (int bb = 0; bb < 8; ++bb)
+            en[bb] = book[(j0 + bb) * 256 + (int)((w[2 * s + (bb >> 2)] >> (8 * (bb & 3))) & 255u)];
+#pragma unroll
+          for (int bb = 0; bb < 8; ++bb) {
+            const float v0 = f16_lo(en[bb]) + f16_hi(en[bb]);
+            x2 = fmaf(v0, v0, x2);
+          }
+          vh = u32x4{(en[0] & 0xffffu) | (en[1] << 16), (en[2] & 0xffffu) | (en[3] << 16),
+                        (en[4] & 0xffffu) | (en[5] << 16), (en[6] & 0xffffu) | (en[7] << 16)};
+          vl = u32x4{(en[0] >> 16) | (en[1] & 0xffff0000u), (en[2] >> 16) | (en[3] & 0xffff0000u),
+                     (en[4] >> 16) | (en[5] & 0xffff0000u), (en[6] >> 16) | (en[7] & 0xffff0000u)};
+        }
+        // the three products of the k-step, the small ones first (the bound holds for any order of accumulation)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vl), qh[s], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), ql[s], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), qh[s], acc, 0, 0, 0);
+      }
+      // |x'|^2 of the row: this lane's half of the components and the other half-wave's
+      x2 += __shfl_xor(x2, 32, 64);
+      // (a row past the cell's size or a tombstone: NaN, which no comparison passes)
+      if (half == 0) x2w[col] = live ? x2 * inv_sx2 : __builtin_nanf("");
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      // accumulator register 4 g + i holds row 8 g + 4 half + i of the tile: four 16-byte reads bring the 16 norms
+      float fast[16];
+      unsigned pass = 0u;
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const f32x4 xr = *reinterpret_cast<const f32x4*>(x2w + 8 * gq + 4 * half);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 4 * gq + i;
+          const float dot = acc[r] * unscale;
+          fast[r] = a.euclid ? (2.f * dot - xr[i]) - q2 : dot;
+          pass |= (qvalid && xr[i] == xr[i] && fast[r] >= thr) ? (1u << r) : 0u;
+        }
+      }
+      if (pass != 0u) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if ((pass >> r) & 1u) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], 1);
+            if (e < cap) {
+              a.keys[(int64_t)q * cap + e] = f2key(fast[r]);
+              a.idx[(int64_t)q * cap + e] = ~(unsigned)(st + r0 + row);
+            } else {
+              a.flags[q] = a.epoch;
+            }
+          }
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+      for (int i = 0; i < 8; ++i) w[i] = wn[i];
+      live = live_n;
+    }
+  }
+}
+
+int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
+  if (a.nq <= 0) return TPQ_OK;
+  hipLaunchKernelGGL(cell_prep_kernel, dim3(1), dim3(1024), 0, st, a);
+  TPQ_LAUNCH_CHECK("cell_prep_kernel");
+  const dim3 per_query((unsigned)((a.nq + 3) / 4));
+  hipLaunchKernelGGL(cell_seed_kernel, per_query, dim3(256), 0, st, a);
+  TPQ_LAUNCH_CHECK("cell_seed_kernel");
+  hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+  TPQ_LAUNCH_CHECK("cell_scan_kernel");
+  hipLaunchKernelGGL(cell_scatter_kernel, per_query, dim3(256), 0, st, a);
+  TPQ_LAUNCH_CHECK("cell_scatter_kernel");
+  // one workgroup of eight waves per CU, fewer when the call cannot list that many (cell, group) blocks: at most one
+  // per listed cell plus one per full group of pairs
+  const int64_t np = (int64_t)a.nq * (a.max_nprobe > a.p0 ? a.max_nprobe - a.p0 : 0);
+  int64_t blocks = (int64_t)a.n_cells + np / kCellGroup;
+  if (blocks > np) blocks = np;
+  if (blocks < 1) return TPQ_OK;
+  blocks = (blocks + 7) / 8;
+  int dev = 0, n_cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
+    n_cus = 256;
+  if (blocks > n_cus) blocks = n_cus;
+  if (a.ds == 1)
+    return launch_with_lds(cell_cand_kernel<1>, "cell_cand_kernel", dim3((unsigned)blocks), dim3(512),
+                           CellBook<1>::kBytes, st, a);
+  return launch_with_lds(cell_cand_kernel<2>, "cell_cand_kernel", dim3((unsigned)blocks), dim3(512),
+                         CellBook<2>::kBytes, st, a);
+}
+
+}  // namespace tpq
+
+using namespace tpq;
+
+extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const float* codebook, int ds,
+                                         int metric, const uint8_t* is_empty, const int64_t* cell_start,
+                                         const int64_t* cell_size, const int64_t* n_probe_list, const int64_t* cells,
+                                         int n_cells, int first_probe, const float* threshold, int64_t n_slots, int nq,
+                                         int max_nprobe, int m, int capacity, int32_t* out_count, uint32_t* out_keys,
+                                         uint32_t* out_addr, float* out_delta, int32_t* out_flags, void* workspace,
+                                         size_t workspace_bytes, tpq_stream_t stream) {
+  TPQ_REQUIRE(codes && query && codebook && cell_start && cell_size && n_probe_list && cells && threshold &&
+                  out_count && out_keys && out_addr && out_delta && out_flags,
+              "ivfpq_cell_candidates: null pointer argument");
+  TPQ_REQUIRE(m == 64 && (ds == 1 || ds == 2), "ivfpq_cell_candidates: m = 64 and ds <= 2 only (m=%d, ds=%d)", m, ds);
+  TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER, "ivfpq_cell_candidates: bad metric %d",
+              metric);
+  TPQ_REQUIRE(nq >= 0 && max_nprobe >= 1 && n_cells >= 1 && first_probe >= 0 && n_slots >= 0 &&
+                  n_slots < 0x7fffffffLL && (int64_t)nq * max_nprobe < 0x7fffffffLL,
+              "ivfpq_cell_candidates: bad shape (nq=%d, max_nprobe=%d, n_cells=%d, first_probe=%d)", nq, max_nprobe,
+              n_cells, first_probe);
+  TPQ_REQUIRE(capacity >= 64 && capacity % 64 == 0 && capacity <= 65536,
+              "ivfpq_cell_candidates: capacity=%d must be a multiple of 64 in [64, 65536]", capacity);
+  const size_t need = cell_extra_bytes(nq, max_nprobe, n_cells, first_probe);
+  if (!workspace || workspace_bytes < need) {
+    set_error("ivfpq_cell_candidates: workspace too small (%zu < %zu)", workspace_bytes, need);
+    return TPQ_ERR_WORKSPACE;
+  }
+  CellArgs a{};
+  a.codes = codes; a.query = query; a.codebook = codebook; a.is_empty = is_empty;
+  a.cell_start = cell_start; a.cell_size = cell_size; a.n_probe_list = n_probe_list; a.cells = cells;
+  a.n_slots = n_slots; a.nq = nq; a.max_nprobe = max_nprobe; a.n_cells = n_cells; a.ds = ds;
+  a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
+  a.p0 = first_probe; a.k = 0; a.chunks = capacity / 64; a.epoch = 1; a.rel = cell_delta_rel(ds);
+  a.thr_in = threshold;
+  a.keys = out_keys; a.idx = out_addr; a.flags = out_flags; a.ws_delta = out_delta;
+  cell_fill_extras(a, workspace);
+  a.cnt = out_count;
+  return launch_cell_candidates(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe) {
+  if (nq <= 0 || max_nprobe < 1 || n_cells < 1 || first_probe < 0) return 0;
+  return cell_extra_bytes(nq, max_nprobe, n_cells, first_probe);
+}

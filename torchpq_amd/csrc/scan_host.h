@@ -94,7 +94,8 @@ static bool fuse_fits(int m, int RM) {
   int dispatch_packed_##M(const ScanArgs& a, const ResidualArgs* ra, int RL, int R, hipStream_t st); \
   int dispatch_pool_##M(const ScanArgs& a, int RL, hipStream_t st);                                  \
   int dispatch_dump_##M(const ScanArgs& a, int RL, int R, int mode, hipStream_t st);                 \
-  int dump_occupancy_##M(int mode);
+  int dump_occupancy_##M(int mode);                                                                  \
+  int dispatch_finish_##M(const ScanArgs& a, int chunks, int R, hipStream_t st);
 TPQ_PACKED_M_LIST(TPQ_DECLARE_PACKED)
 #undef TPQ_DECLARE_PACKED
 

@@ -14,10 +14,11 @@ __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~(siz
 // a probe table of max_nprobe cells: start, size, and the exclusive prefix of the tiles (one more entry)
 __host__ __device__ constexpr size_t probe_table_bytes(int max_nprobe) { return (size_t)(3 * max_nprobe + 1) * 4; }
 
-// the query's probe count, clamped to [0, max_nprobe]
+// the query's probe count, clamped to [0, max_nprobe] -- and to the call's probe cap, when it has one
 __device__ __forceinline__ int clamped_n_probe(const ScanArgs& a, int q) {
   const int n_probe = (int)a.n_probe_list[q];
-  return n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);
+  const int n = n_probe < 0 ? 0 : (n_probe > a.max_nprobe ? a.max_nprobe : n_probe);
+  return (a.probe_cap > 0 && n > a.probe_cap) ? a.probe_cap : n;
 }
 
 // ---- LDS of a top-k list kernel: [region0][queues 8 x 512][probe table 3 n + 1][tau][tail] ------------------------

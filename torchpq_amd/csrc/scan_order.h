@@ -13,8 +13,10 @@ constexpr int kOrderMaxQueries = 20480;
 inline size_t order_ws_bytes(int nq) { return 3 * (((size_t)nq * 4 + 255) & ~(size_t)255); }
 
 // order[i] = the query dispatched i-th (work non-increasing, equal work by ascending query), rank = its inverse,
-// work[q] = tiles of 2^tile_shift slots the query scans; two launches on `st`
+// work[q] = tiles of 2^tile_shift slots the query scans -- of its first `probe_cap` probes when that is positive
+// (ScanArgs::probe_cap); two launches on `st`
 int launch_scan_order(const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list, int nq,
-                      int max_nprobe, int tile_shift, int* order, int* rank, int* work, hipStream_t st);
+                      int max_nprobe, int tile_shift, int* order, int* rank, int* work, hipStream_t st,
+                      int probe_cap);
 
 }  // namespace tpq

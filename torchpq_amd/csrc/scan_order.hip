@@ -25,12 +25,13 @@ __global__ __launch_bounds__(256) void scan_work_kernel(const int64_t* __restric
                                                         const int64_t* __restrict__ cell_size,
                                                         const int64_t* __restrict__ n_probe_list,
                                                         int* __restrict__ work, int nq, int max_nprobe,
-                                                        int tile_shift) {
+                                                        int tile_shift, int probe_cap) {
   const int lane = (int)(threadIdx.x & 63);
   const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (q >= nq) return;  // (wave-uniform)
   int n_probe = (int)n_probe_list[q];
   n_probe = n_probe < 0 ? 0 : (n_probe > max_nprobe ? max_nprobe : n_probe);
+  if (probe_cap > 0 && n_probe > probe_cap) n_probe = probe_cap;  // (the scan's own cap: clamped_n_probe)
   const int64_t* __restrict__ cs = cell_start + (int64_t)q * max_nprobe;
   const int64_t* __restrict__ cz = cell_size + (int64_t)q * max_nprobe;
   unsigned long long tiles = 0ull;
@@ -83,10 +84,11 @@ __global__ __launch_bounds__(kOrderWaves * 64) void scan_order_rank_kernel(const
 }
 
 int launch_scan_order(const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list, int nq,
-                      int max_nprobe, int tile_shift, int* order, int* rank, int* work, hipStream_t st) {
+                      int max_nprobe, int tile_shift, int* order, int* rank, int* work, hipStream_t st,
+                      int probe_cap) {
   if (nq <= 0) return TPQ_OK;
   hipLaunchKernelGGL(scan_work_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, cell_start, cell_size,
-                     n_probe_list, work, nq, max_nprobe, tile_shift);
+                     n_probe_list, work, nq, max_nprobe, tile_shift, probe_cap);
   TPQ_LAUNCH_CHECK("scan_work_kernel");
   hipLaunchKernelGGL(scan_order_rank_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(kOrderWaves * 64), 0, st, work,
                      order, rank, nq);
@@ -104,5 +106,5 @@ extern "C" int tpq_ivfpq_scan_order(const int64_t* cell_start, const int64_t* ce
   TPQ_REQUIRE(nq >= 0 && max_nprobe >= 1, "ivfpq_scan_order: bad nq/max_nprobe (%d, %d)", nq, max_nprobe);
   TPQ_REQUIRE(tile_shift >= 0 && tile_shift <= 16, "ivfpq_scan_order: tile_shift=%d out of range [0, 16]", tile_shift);
   return tpq::launch_scan_order(cell_start, cell_size, n_probe_list, nq, max_nprobe, tile_shift, order, rank, work,
-                                reinterpret_cast<hipStream_t>(stream));
+                                reinterpret_cast<hipStream_t>(stream), 0);
 }

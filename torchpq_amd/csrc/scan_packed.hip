@@ -186,6 +186,18 @@ int TPQ_CAT(dispatch_dump_, TPQ_PACKED_M)(const ScanArgs& a, int RL, int R, int 
   return dispatch_dump_mode<TPQ_PACKED_M, kDumpSel16>(a, RL, R, st);
 }
 
+// the finish kernel on its own (the cell-major form, scan_cells.hip): a query's lists arrive as `chunks` (8 or 16) lists
+// of one chunk of 64 keys each; R = registers of the exact list (dump_finish_regs)
+int TPQ_CAT(dispatch_finish_, TPQ_PACKED_M)(const ScanArgs& a, int chunks, int R, hipStream_t st) {
+  if constexpr (dump_built(TPQ_PACKED_M, kDumpSel16)) {
+    if (R <= 2) return launch_finish<2, TPQ_PACKED_M>(a, chunks, 1, st);
+    if (R == 4) return launch_finish<4, TPQ_PACKED_M>(a, chunks, 1, st);
+    if (R == 8) return launch_finish<8, TPQ_PACKED_M>(a, chunks, 1, st);
+  }
+  set_error("scan_packed (finish): no instantiation for %d list registers at m = %d", R, TPQ_PACKED_M);
+  return TPQ_ERR_UNSUPPORTED;
+}
+
 // workgroups of the dump-mode scan kernel (RL = 1, a 64-probe table, fused LUT at ds = 2) one CU holds; 0 = not built
 template <int M, int MODE>
 static int dump_occupancy_of() {

@@ -28,6 +28,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     # the LUT is built inside the scan workgroups (no [m, nq, 256] table in HBM) up to this
     # sub-vector length; the workgroup then reads m * ds KiB of L2-resident codebook per query
     fused_lut_max_subvector = 4
+    use_cell_major = True
 
     def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None,
                  expand_step_size=128, expand_mode="double", distance="euclidean",
@@ -60,6 +61,9 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         self._fp16_scale_mode = "a"
         self.use_packed_layout = True   # MI355X scan layout (bank-conflict-free LDS look-ups)
         self.use_fused_lut = True       # build the ADC LUT inside the scan workgroups (no HBM table)
+        # hand the probed cells to the fused scan: a large cell-dense batch at m = 64 may then take the cell-major
+        # form (csrc/scan_cells.hip; the library's rule decides, IVFPQTopkHip.last_cell_major() tells)
+        self.use_cell_major = True
 
         self._init_coarse(n_cells, verbose)
         self.pq_codec = PQCodec(d_vector=d_vector, n_subvectors=n_subvectors, n_clusters=256,
@@ -288,7 +292,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         elif fused:
             found = self._ivfpq_topk.topk_fused(
                 packed=self._scan_layout(), query=x, codebook=self.pq_codec.codebook, k=k, distance=self.distance,
-                slots_hint=slots_hint, **lists)
+                slots_hint=slots_hint, cells=cells if self.use_cell_major else None, n_cells=self.n_cells, **lists)
         else:
             found = self._ivfpq_topk.topk(
                 packed=self._scan_layout(), precomputed=self.pq_codec.precompute_adc(x), k=k,

@@ -44,6 +44,7 @@ class IVFPQTopkHip:
         self.workspace_bytes = None
         self.last_workspace_bytes = None
         self._last_device = None
+        self._last_cells = None       # (n_cells, n_slots) when the last call handed over its probed cells
 
     def _tickets(self, n_query, n_split, device):
         """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
@@ -125,6 +126,29 @@ class IVFPQTopkHip:
         a large batch of more than one round of workgroup slots whose workspace has room for the order)"""
         return None if self.last_call is None else self.ordered(self.last_workspace_bytes)
 
+    def cell_major(self, workspace_bytes, n_cells, n_slots):
+        """diagnostics: whether the last topk_fused call, handed `workspace_bytes` of workspace and the probed cells of
+        an index of `n_cells` cells over `n_slots` slots, takes the cell-major form of the large-batch route
+        (tpq_ivfpq_scan_cell_major: the library's own rule, nothing is launched)"""
+        if self.last_call is None:
+            return None
+        c = self.last_call
+        code = load().tpq_ivfpq_scan_cell_major(int(c["n_query"]), int(c["k"]), int(c["n_split"]), self.m, int(c["ds"]),
+                                                 int(c["n_probe"]), int(c["slots_hint"] or 0), int(bool(c["has_lut"])),
+                                                 int(bool(c["packed"]) and self.m in PACKED_M), int(c["n_split"] > 1),
+                                                 int(bool(c.get("residual", False))), int(n_cells), int(n_slots),
+                                                 int(workspace_bytes))
+        return code == 1
+
+    def last_cell_major(self):
+        """diagnostics: whether the last topk / topk_fused call ran the cell-major form (csrc/scan_cells.hip): it handed
+        over its cells and the library's rule took them"""
+        if self.last_call is None:
+            return None
+        if self._last_cells is None:
+            return False
+        return self.cell_major(self.last_workspace_bytes, *self._last_cells)
+
     def _n_split(self, n_query, device, slots_hint=None):
         """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
         if self.n_cus is None:
@@ -134,10 +158,12 @@ class IVFPQTopkHip:
         per_cu, waves = (4, 4) if self.m <= 32 else (2, 8) if self.m <= 64 else (1, 16)
         return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
 
-    def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed, **route):
+    def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed,
+              cells=None, n_cells=0, **route):
         """What topk / topk_fused / topk_residual_packed share once their arguments are checked: the outputs, the
         split, the diagnostics, the workspace and the call of `name` -- its own `inputs`, then the arguments every
-        scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint)."""
+        scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint; `cells`:
+        it takes the probed cells and their number behind those)."""
         n_data, device = data.shape[1], data.device
         n_query, n_probe = cell_start.shape
         values, address, ids = alloc_topk(n_query, k, device, address2id)
@@ -149,6 +175,7 @@ class IVFPQTopkHip:
         self.last_n_split = n_split  # diagnostics / tests: workgroups per query of the last call
         self.last_call = dict(n_query=n_query, k=k, n_split=n_split, n_probe=n_probe, slots_hint=slots_hint,
                               packed=packed is not None, **route)
+        self._last_cells = (int(n_cells), int(n_data)) if cells is not None else None
         ws_bytes = lib.tpq_ivfpq_scan_workspace_bytes(n_query, k, n_split, self.m)
         if self.workspace_bytes is not None:
             ws_bytes = int(self.workspace_bytes)
@@ -163,6 +190,8 @@ class IVFPQTopkHip:
             if ticketed:
                 tickets = self._tickets(n_query, n_split, device) if packed is not None else None
                 tail = (ptr(tickets), int(slots_hint or 0))
+                if cells is not None:
+                    tail += (ptr(cells), int(n_cells))
             rc = getattr(lib, name)(*inputs, ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data, n_query,
                                     n_probe, self.m, k, n_split, ptr(ws), ws_bytes, *tail, stream_ptr(device))
             if rc != 0 and ticketed:
@@ -216,10 +245,12 @@ class IVFPQTopkHip:
 
     def topk_fused(self, data, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
                    n_candidates, distance="euclidean", packed=None, address2id=None, n_split=None,
-                   slots_hint=None):
+                   slots_hint=None, cells=None, n_cells=0):
         """precompute_adc + topk in one pass: the LUT is built inside the scan workgroups
         (query [d, n_query] f32, codebook [m, ds, 256] f32); results identical to
-        topk(precomputed=AdcLutHip()(query, codebook))."""
+        topk(precomputed=AdcLutHip()(query, codebook)).  `cells` [n_query, max_n_probe] int64 -- the probed cells
+        behind cell_start / cell_size, ids in [0, n_cells) -- lets a cell-dense large batch at m = 64 take the
+        cell-major form (tpq_ivfpq_search_fused_cells; `last_cell_major()`): same results."""
         n_data = data.shape[1]
         n_query, n_probe = cell_start.shape
         m, ds, kk = codebook.shape
@@ -237,6 +268,12 @@ class IVFPQTopkHip:
                     address2id)
         inputs = (ptr(packed), ptr(data), ptr(query), ptr(codebook), ds, metric_code(distance), ptr(is_empty),
                   ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+        if cells is not None:
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64 and n_cells >= 1
+            cells = cells.contiguous()
+            require_gpu(cells)
+            return self._scan("tpq_ivfpq_search_fused_cells", inputs, data, cell_start, address2id, n_candidates,
+                              n_split, slots_hint, packed, True, cells=cells, n_cells=n_cells, ds=ds, has_lut=False)
         return self._scan("tpq_ivfpq_search_fused_tickets", inputs, data, cell_start, address2id, n_candidates,
                           n_split, slots_hint, packed, True, ds=ds, has_lut=False)
 
@@ -338,6 +375,46 @@ class IVFPQTopkHip:
         assert cells.shape == cell_start.shape and cells.dtype == torch.int64
         return self._residual(data, part1, part2, None, cells, base_sims, is_empty, cell_start,
                               cell_size, n_probe_list, n_candidates, address2id)
+
+
+class CellCandidatesHip:
+    """The cell-major candidate pass on its own (tpq_ivfpq_cell_candidates, csrc/scan_cells.hip): for the probes
+    first_probe <= p < n_probe_list[q] of every query, every live slot whose fp16 matrix-core value is >= threshold[q] -
+    delta_q; m = 64, sub-vectors of 1 or 2 components."""
+
+    def __call__(self, data, query, codebook, cells, n_cells, cell_start, cell_size, n_probe_list, threshold,
+                 first_probe=0, capacity=1024, is_empty=None, distance="euclidean"):
+        """-> (count i32 [nq], values f32 [nq, capacity], address i64 [nq, capacity] (-1 past the count), band f32 [nq]
+        = 2 delta_q, flags i32 [nq])"""
+        m, ds, kk = codebook.shape
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert m == 64 and kk == 256 and ds in (1, 2) and query.shape == (m * ds, n_query)
+        assert data.shape == (16, n_data, 4) and data.dtype == torch.uint8
+        assert cells.shape == cell_size.shape == (n_query, n_probe)
+        assert cells.dtype == cell_start.dtype == cell_size.dtype == n_probe_list.dtype == torch.int64
+        assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+        query, codebook, cells = query.contiguous(), codebook.contiguous(), cells.contiguous()
+        require_gpu(data, query, codebook, cells, is_empty, cell_start, cell_size, n_probe_list, threshold)
+        dev = data.device
+        count = torch.zeros(n_query, device=dev, dtype=torch.int32)
+        keys = torch.zeros(n_query, capacity, device=dev, dtype=torch.int32)
+        addr = torch.zeros(n_query, capacity, device=dev, dtype=torch.int32)
+        band = torch.zeros(n_query, device=dev, dtype=torch.float32)
+        flags = torch.zeros(n_query, device=dev, dtype=torch.int32)
+        ws_bytes = load().tpq_ivfpq_cell_candidates_workspace_bytes(n_query, n_probe, int(n_cells), int(first_probe))
+        ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
+        call("tpq_ivfpq_cell_candidates", dev, ptr(data), ptr(query), ptr(codebook), ds, metric_code(distance),
+             ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(cells), int(n_cells),
+             int(first_probe), ptr(threshold), n_data, n_query, n_probe, m, int(capacity), ptr(count), ptr(keys),
+             ptr(addr), ptr(band), ptr(flags), ptr(ws), ws_bytes)
+        address = (~addr).to(torch.int64)
+        stored = torch.arange(capacity, device=dev)[None, :] < count.clamp(max=capacity)[:, None]
+        address = torch.where(stored, address, torch.full_like(address, -1))
+        neg = keys < 0                                  # (the image's top bit: a value >= 0)
+        bits = torch.where(neg, keys & 0x7fffffff, ~keys)
+        values = torch.where(stored, bits.view(torch.float32), torch.full_like(band[:, None].expand_as(bits), -float("inf")))
+        return count, values, address, band, flags
 
 
 class ScanOrderHip:
