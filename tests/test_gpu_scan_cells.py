@@ -44,7 +44,9 @@ def _search(p, k, distance="euclidean", cells=True, packed=True, scan=None):
     scan.keep_workspace = True
     cs, sz = p["start"][p["cells"].clamp(0, p["n_cells"] - 1)].contiguous(), p["sizes"][
         p["cells"].clamp(0, p["n_cells"] - 1)].contiguous()
-    hint = int(p["sizes"].float().mean().item() * p["cells"].shape[1])
+    if "sz" in p:   # (a problem that hands its probes' sizes over itself: void probes, test_gpu_scan_cells_edges.py)
+        sz = p["sz"]
+    hint = p.get("hint") or int(p["sizes"].float().mean().item() * p["cells"].shape[1])
     pk = p.setdefault("packed", K.PackCodesHip()(p["storage"])) if packed else None
     out = scan.topk_fused(p["storage"], p["query"], p["codebook"], p["is_empty"], cs, sz, p["npl"], k,
                           distance=distance, packed=pk, slots_hint=hint,
@@ -84,7 +86,9 @@ def test_equals_the_reference_layout_kernel(nq, n_cells, n_probe, ds, distance, 
 
 
 def test_cells_probed_by_1_127_128_and_129_queries():
-    """the groups of 128 queries of a cell: one query, one short of a full group, a full group, a group and one"""
+    """cells listed by 1, 127, 128 and 129 queries: a candidate block takes a group of 32 (kCellGroup), so these are one
+    short group, three full groups and a group of 31, four full groups, four and a group of one (the edges of a single
+    group -- 31, 32, 33 -- are test_gpu_scan_cells_edges.py's)"""
     nq, n_cells, n_probe = 1300, 16, 8
     p = _problem(5, nq, n_cells, n_probe, 2, ragged=False)
     g = torch.Generator(device=DEV)
@@ -179,8 +183,8 @@ def test_graphed_search_replays_the_form():
 
 @pytest.mark.parametrize("ds,distance", [(2, "euclidean"), (1, "inner")])
 def test_candidate_kernel_against_float64(ds, distance):
-    """returned set contains every slot whose exact value is >= tau, every returned slot has exact >= tau - 2 delta,
-    no duplicates, counts match; exact = the sum in float64"""
+    """returned set contains every slot whose exact value is >= tau, every returned slot has exact >= tau - 2 delta and
+    a value within delta of the exact one, no duplicates, counts match; exact = the sum in float64"""
     from torchpq_amd import kernels as K
     nq, n_cells, n_probe = 300, 8, 6
     p = _problem(17 + ds, nq, n_cells, n_probe, ds, ragged=True)     # 1 045 slots
@@ -210,10 +214,12 @@ def test_candidate_kernel_against_float64(ds, distance):
         p["storage"], p["query"], p["codebook"], p["cells"], n_cells, cs, sz, p["npl"],
         torch.from_numpy(tau).to(DEV), first_probe=first, capacity=2048, is_empty=p["is_empty"], distance=distance)
     torch.cuda.synchronize()
-    count, address, band, flags = (t.cpu().numpy() for t in (count, address, band, flags))
+    count, values, address, band, flags = (t.cpu().numpy() for t in (count, values, address, band, flags))
     assert not flags.any()
     for qi in range(nq):
         got = address[qi, :count[qi]]
+        # the returned value is the selection key: within delta_q = band / 2 of the exact one
+        assert (np.abs(values[qi, :count[qi]].astype(np.float64) - exact[qi, got]) <= band[qi] / 2.0).all()
         assert (address[qi, count[qi]:] == -1).all()
         assert len(set(got.tolist())) == len(got), "duplicates"
         assert live[qi, got].all()
