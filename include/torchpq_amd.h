@@ -213,6 +213,10 @@ int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes, 
  * tpq_ivfpq_scan_route, the number of cells, the slots of the storage and the workspace size the caller passes -- takes
  * the form when it hands over its cells: 1 / 0, or -1 for arguments the entry points reject.  The rule: the four-wave
  * route, k <= 128, more than 4 probes, nq * slots_hint / n_slots >= 96 and room in the workspace behind the lists in use.
+ * tpq_ivfpq_scan_cell_norms, same arguments: whether step 4 of such a call reads the slot norms |x|^2 from an array
+ * computed once per call (cell_norm_kernel) -- 1 when the form is taken and the workspace has room for 4 * n_slots bytes
+ * (rounded up to 256) behind the lists and inversion arrays in use -- or forms them in every candidate block (0).  Same
+ * results either way; 0 wherever tpq_ivfpq_scan_cell_major is 0.
  * tpq_ivfpq_cell_candidates is steps 3-4 on their own, with the caller's thresholds (m == 64, ds 1 or 2): for the
  * probes first_probe <= p < n_probe_list[q] of every query, every live slot whose fast value is >= threshold[q] - delta_q.
  *   out_count i32 [nq]             candidates admitted (beyond `capacity`: counted, not stored, out_flags[q] = 1)
@@ -221,7 +225,10 @@ int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes, 
  *                                  the count hold ~(2^31 - 1) in out_addr and nothing in out_keys
  *   out_delta f32 [nq]             2 delta_q: every stored slot's exact value is >= threshold[q] - 2 delta_q
  *   out_flags i32 [nq]             1: the query took no part (NaN / Inf, a cell out of range, unscalable) or overflowed
- * capacity: a multiple of 64; workspace: tpq_ivfpq_cell_candidates_workspace_bytes. */
+ * capacity: a multiple of 64; workspace: tpq_ivfpq_cell_candidates_workspace_bytes, or
+ * tpq_ivfpq_cell_candidates_norms_workspace_bytes (that size + 4 * n_slots rounded up to 256): a workspace of at least
+ * the larger size takes the slot norms from an array computed once per call, a smaller one forms them in every block;
+ * the same candidates with the same keys either way. */
 int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes, const float* query,
                                  const float* codebook, int ds, int metric, const uint8_t* is_empty,
                                  const int64_t* cell_start, const int64_t* cell_size,
@@ -233,7 +240,12 @@ int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes, co
 int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
                               int has_packed, int has_tickets, int residual, int n_cells, int64_t n_slots,
                               size_t workspace_bytes);
+int tpq_ivfpq_scan_cell_norms(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
+                              int has_packed, int has_tickets, int residual, int n_cells, int64_t n_slots,
+                              size_t workspace_bytes);
 size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe);
+size_t tpq_ivfpq_cell_candidates_norms_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe,
+                                                       int64_t n_slots);
 int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const float* codebook, int ds, int metric,
                               const uint8_t* is_empty, const int64_t* cell_start, const int64_t* cell_size,
                               const int64_t* n_probe_list, const int64_t* cells, int n_cells, int first_probe,

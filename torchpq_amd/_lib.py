@@ -48,7 +48,9 @@ SIGNATURES = {
     "tpq_ivfpq_search_fused_cells": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp, _i, _vp]),
     "tpq_ivfpq_scan_cell_major": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
+    "tpq_ivfpq_scan_cell_norms": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
     "tpq_ivfpq_cell_candidates_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "tpq_ivfpq_cell_candidates_norms_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
     "tpq_ivfpq_cell_candidates": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tpq_ivfpq_scan_topk_residual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

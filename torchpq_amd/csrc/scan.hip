@@ -402,6 +402,8 @@ extern "C" int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds,
 //  * the batch is cell-dense: the mean code byte is read nq x slots_hint / n_slots >= kCellMinRereads times;
 //  * the query's lists as 16 (or 8) chunks of 64 keys -- the finish kernel's forms -- and the inversion arrays fit the
 //    workspace: behind the lists in use, as the order does; tpq_ivfpq_scan_workspace_bytes stays what it is.
+// With room for one more array behind those -- an fp32 per slot (cell_norm_bytes) -- the slot norms are computed once
+// per call (cell_norm_kernel) instead of in every candidate block: cell_major_norms, tpq_ivfpq_scan_cell_norms.
 // Pure host arithmetic: tpq_ivfpq_scan_cell_major answers without a GPU.  Returns the chunks per query, 0 = today's path.
 struct CellMajor {
   const int64_t* cells;  // [nq][max_nprobe]
@@ -416,6 +418,11 @@ static int cell_major_chunks(const ScanArgs& a, const ScanPlan& p, bool residual
   for (int chunks = 16; chunks >= 8; chunks >>= 1)
     if ((a.k + 63) / 64 < chunks && workspace_bytes >= ws_bytes_for(a.nq, 1, chunks) + extra) return chunks;
   return 0;
+}
+static bool cell_major_norms(const ScanArgs& a, int chunks, int n_cells, size_t workspace_bytes) {
+  return chunks > 0 && workspace_bytes >= ws_bytes_for(a.nq, 1, chunks) +
+                                              cell_extra_bytes(a.nq, a.max_nprobe, n_cells, kCellP0) +
+                                              cell_norm_bytes(a.n_slots);
 }
 
 // stages 1-5 (the flag-gated redo over ALL probes is the caller's next line, as on every dump route)
@@ -456,7 +463,8 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   c.seed_vals = a.out_vals; c.seed_addr = a.out_addr;
   c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
   c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
-  cell_fill_extras(c, reinterpret_cast<char*>(workspace) + ws_bytes_for(nq, 1, chunks));
+  const size_t cm_lists = ws_bytes_for(nq, 1, chunks);  // (the gate saw to it: lists and extras fit)
+  cell_fill_extras(c, reinterpret_cast<char*>(workspace) + cm_lists, workspace_bytes - cm_lists);
   rc = launch_cell_candidates(c, st);
   if (rc) return rc;
   // 5. the finish kernel over the filled chunks: F_k, the cut at F_k - 2 delta_q, the survivors -- seeds included --
@@ -473,6 +481,18 @@ extern "C" int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int 
   a.n_slots = n_slots;
   const ScanPlan p = plan_scan(a, residual != 0);
   return cell_major_chunks(a, p, residual != 0, n_cells, workspace_bytes) ? 1 : 0;
+}
+
+extern "C" int tpq_ivfpq_scan_cell_norms(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                         int has_lut, int has_packed, int has_tickets, int residual, int n_cells,
+                                         int64_t n_slots, size_t workspace_bytes) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return 0;
+  ScanArgs a = route_query_args(nq, k, n_split, m, ds, max_nprobe, slots_hint, has_lut, has_tickets);
+  a.n_slots = n_slots;
+  const ScanPlan p = plan_scan(a, residual != 0);
+  const int chunks = cell_major_chunks(a, p, residual != 0, n_cells, workspace_bytes);
+  return cell_major_norms(a, chunks, n_cells, workspace_bytes) ? 1 : 0;
 }
 
 static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,

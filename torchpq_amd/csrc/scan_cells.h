@@ -51,6 +51,8 @@ struct CellArgs {
   int* cell_sz;
   int* pairs;                    // [nq (max_nprobe - p0)] the queries, grouped by cell
   _Float16* qsplit;              // [nq][2][128] the fp16 pieces of s_q q (hi, lo)
+  // behind the extras, when the workspace has the room (cell_norm_bytes); nullptr: the candidate kernel's own chain
+  float* norm;                   // [n_slots] |x'|^2 / s_x^2 of every slot of a listed cell, by address (NaN: tombstone)
 };
 
 inline size_t cell_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -60,8 +62,11 @@ inline size_t cell_extra_bytes(int nq, int max_nprobe, int n_cells, int p0) {
          2 * cell_align(((size_t)n_cells + 1) * 4) + 2 * cell_align((size_t)n_cells * 4) +
          cell_align((size_t)nq * np * 4) + cell_align((size_t)nq * kCellQSplit * 2);
 }
-// points the extras of `a` into `at` (cell_extra_bytes of it)
-void cell_fill_extras(CellArgs& a, void* at);
+// the slot norms of a call (cell_norm_kernel): one fp32 per slot address
+inline size_t cell_norm_bytes(int64_t n_slots) { return cell_align((size_t)(n_slots > 0 ? n_slots : 0) * 4); }
+// points the extras of `a` into `at` (cell_extra_bytes of it); `room` bytes are the caller's from `at` on: the slot
+// norms follow the extras when they fit, else a.norm = nullptr
+void cell_fill_extras(CellArgs& a, void* at, size_t room);
 // delta_q / (|q| + |x|max)^2 (derivation: scan_cells.hip)
 float cell_delta_rel(int ds);
 // stages 2-4 on `st`: seed (or the caller's thresholds), inversion, candidates

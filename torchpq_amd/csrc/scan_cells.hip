@@ -20,8 +20,13 @@
 //                        no further part (tau = -inf is a threshold like any other: everything is admitted, and what
 //                        does not fit flags the query below).
 //   cell_scan_kernel     one block: exclusive prefixes of the histogram (pairs) and of ceil(pairs / 32) (blocks).
-//   cell_scatter_kernel  one wave per query: pairs[cursor[cell]++] = q, and the cell's extent.  The order inside a
-//                        cell varies from run to run; nothing downstream depends on it.
+//   cell_scatter_kernel  one wave per query: pairs[cursor[cell]++] = q; the pair that takes a cell's first position
+//                        writes the cell's extent.  The order inside a cell varies from run to run; nothing downstream
+//                        depends on it.
+//   cell_norm_kernel     when the workspace has room for an fp32 per slot behind the other arrays (CellArgs::norm):
+//                        |x'|^2 / s_x^2 of every slot of a listed cell, NaN for a tombstone, once per call -- the bits
+//                        the candidate kernel's own chain forms in every (cell, block).  A thread per slot over a
+//                        codebook of fp32 sums (hi piece + lo piece) in LDS, cells dealt over one workgroup per CU.
 //   cell_cand_kernel     one block of work per (cell, group of <= 32 listed queries), taken by ONE WAVE, query per MFMA
 //                        column: a lane owns one query, threshold and scales in registers, its B operand read as 16-byte
 //                        pieces of the seed kernel's split copy.  One workgroup of eight waves per CU stages the codebook in
@@ -29,13 +34,20 @@
 //                        take blocks from a counter, independently: no barrier after the staging.  Per tile of 32 slots,
 //                        lane (row, half) reads the 8 code dwords of its half of every k-step from the reference layout
 //                        [16][n_slots][4] (coalesced over slots, one tile ahead) and gathers its A operand straight from
-//                        the codebook in LDS; |x'|^2 rides along (an fma chain over the same pieces, the two half-waves
-//                        added) and reaches the accumulator's rows through 128 bytes of LDS per wave.
+//                        the codebook in LDS; |x'|^2 is cell_norm_kernel's, loaded with the codes (NORMS), or rides
+//                        along (an fma chain over the same pieces, the two half-waves added), and reaches the
+//                        accumulator's rows through 128 bytes of LDS per wave.  A lane's admitted rows of a tile take
+//                        consecutive entries of its query's list from ONE counter update (a returning atomic per row
+//                        was four or five dependent round trips per tile).
 //                        A probe listed twice in a row is skipped as the scan skips it (fetch_probes, scan_shared.h).
 //                        (Measured on the headline batch, 10 000 queries x 28 listed probes: sub-vectors gathered from
 //                        the fp32 codebook in global memory into a staged 128-slot tile, 2.66 ms; this form with the
 //                        queries read from [d][nq] per block, 1.06 ms; with the split copy, 0.91 ms; with the norms of a
-//                        tile read in four 16-byte LDS reads and the codes loaded a tile ahead, 0.81 ms.)
+//                        tile read in four 16-byte LDS reads and the codes loaded a tile ahead, 0.81 ms (0.78 in the
+//                        later record, profiles/cell_norms_bench.json); with the norms of cell_norm_kernel, 0.68 +
+//                        0.03 ms; with one counter update per lane and tile, 0.53 + 0.03 ms.  Two 32-column query sets
+//                        per decode -- 64 queries per block, 252 registers -- ran 0.55 ms and are not built:
+//                        tools/experiments/cell_two_sets.patch.)
 //
 // Arithmetic.  q' = s_q q = qh + ql + rq,  x' = s_x x = xh + xl + rx  (h = fp16(.), l = fp16(. - h); s_q, s_x powers of
 // two with max |q'_i|, max |s_x c| in [2^12, 2^13): no piece overflows, and the scaling is exact).  Per component
@@ -74,8 +86,10 @@ float cell_delta_rel(int ds) {
   return (float)(1.25 * sum * (1.0 + 1.0 / 1024));  // (+ 2^-10: B^2 and the product are evaluated in fp32)
 }
 
-void cell_fill_extras(CellArgs& a, void* at) {
+void cell_fill_extras(CellArgs& a, void* at, size_t room) {
   char* p = reinterpret_cast<char*>(at);
+  const size_t extras = cell_extra_bytes(a.nq, a.max_nprobe, a.n_cells, a.p0);
+  a.norm = room >= extras && room - extras >= cell_norm_bytes(a.n_slots) ? reinterpret_cast<float*>(p + extras) : nullptr;
   auto take = [&](size_t bytes) {
     char* r = p;
     p += cell_align(bytes);
@@ -294,9 +308,11 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
     if (!lp.listed) continue;
     const int pos = atomicAdd(&a.hist[lp.cell], 1);
     a.pairs[pos] = q;
-    const int64_t o = (int64_t)q * a.max_nprobe + p;
-    a.cell_st[lp.cell] = (int)a.cell_start[o];  // (every query lists the cell with the same extent)
-    a.cell_sz[lp.cell] = (int)a.cell_size[o];
+    if (pos == a.cell_off[lp.cell]) {  // the cell's first pair writes its extent (every query lists it with the same)
+      const int64_t o = (int64_t)q * a.max_nprobe + p;
+      a.cell_st[lp.cell] = (int)a.cell_start[o];
+      a.cell_sz[lp.cell] = (int)a.cell_size[o];
+    }
   }
 }
 
@@ -314,11 +330,78 @@ __device__ __forceinline__ unsigned pack_f16x2(_Float16 lo, _Float16 hi) {
 __device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
 __device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
 
+// The slot norms of a call: norm[slot] = |x'|^2 / s_x^2 of every slot of a listed cell, NaN for a tombstone -- the value
+// cell_cand_kernel<DS, false> forms per (cell, block) in its tile loop, here once per slot, with the same bits: per half
+// (components [16 s + 8 half, + 8), s ascending) the chain x2 = fma(v, v, x2) over v = fp32(hi piece) + fp32(lo piece),
+// then half 0 + half 1, then x inv_sx2.  The sums v do not depend on the slot, so the staging forms them once per entry:
+// the book in LDS is [j][c] -> DS fp32 sums (128 KiB at ds = 2).  One workgroup per CU at most, cells dealt round robin,
+// a thread per slot: its 16 code dwords are coalesced over the slots of the cell.
+template <int DS>
+__global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
+  constexpr int KS = 4 * DS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sums = reinterpret_cast<float*>(smem);  // [j][c][DS]
+  const int tid = (int)threadIdx.x;
+  const float sx = a.params[3];
+  const float inv_sx = 1.f / sx;
+  const float inv_sx2 = inv_sx * inv_sx;
+  for (int i = tid; i < 64 * 256; i += 512) {  // entry (j, c)
+    const int j = i >> 8, c = i & 255;
+#pragma unroll
+    for (int e = 0; e < DS; ++e) {
+      const float ys = a.codebook[(j * DS + e) * 256 + c] * sx;
+      const _Float16 h = (_Float16)ys;
+      const _Float16 l = (_Float16)(ys - (float)h);
+      sums[i * DS + e] = (float)h + (float)l;
+    }
+  }
+  __syncthreads();
+  for (int c = (int)blockIdx.x; c < a.n_cells; c += (int)gridDim.x) {
+    if (a.cell_off[c + 1] == a.cell_off[c]) continue;  // not listed: its extent was never written
+    const int64_t st = a.cell_st[c];
+    int sz = a.cell_sz[c];
+    if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (the candidate kernel's check)
+    for (int r = tid; r < sz; r += 512) {
+      const int64_t slot = st + r;
+      const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(a.codes) + slot;
+      uint32_t w[16];  // dword g: the codes of sub-quantizers [4 g, + 4)
+#pragma unroll
+      for (int g = 0; g < 16; ++g) w[g] = cw[(int64_t)g * a.n_slots];
+      const bool empty = a.is_empty && a.is_empty[slot];
+      float x2h[2];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        float x2 = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+#pragma unroll
+          for (int bb = 0; bb < 8 / DS; ++bb) {
+            const int j = (16 * s + 8 * half) / DS + bb;
+            const int code = (int)((w[j >> 2] >> (8 * (j & 3))) & 255u);
+            if constexpr (DS == 2) {
+              const float2 v = reinterpret_cast<const float2*>(sums)[j * 256 + code];
+              x2 = fmaf(v.x, v.x, x2);
+              x2 = fmaf(v.y, v.y, x2);
+            } else {
+              const float v = sums[j * 256 + code];
+              x2 = fmaf(v, v, x2);
+            }
+          }
+        }
+        x2h[half] = x2;
+      }
+      a.norm[slot] = empty ? __builtin_nanf("") : (x2h[0] + x2h[1]) * inv_sx2;
+    }
+  }
+}
+
 // One workgroup of eight waves per CU stages the split codebook once; every WAVE then takes blocks -- (cell, group of
 // <= 32 listed queries) -- from a counter (cell_prep_kernel zeroes it) and never meets the others again.  Per tile of 32
 // slots, lane (row, half) loads the 8 code dwords that hold its half of every k-step and gathers its A operand -- the
 // pieces of 8 components -- straight from the codebook in LDS: no staged tile, no barrier.
-template <int DS>
+// NORMS: the norm of a row is cell_norm_kernel's (a.norm, loaded with the codes, NaN for a row that is not live) instead
+// of the chain over the gathered pieces; the same bits either way.
+template <int DS, bool NORMS>
 __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
   using T = CellBook<DS>;
   constexpr int KS = T::KS;
@@ -386,7 +469,7 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
     }
     // the code dwords of this lane's components: k-step s holds components [16 s + 8 half, + 8), i.e. sub-quantizers
     // [(16 s + 8 half) / DS, + 8 / DS): one dword at ds = 2, two at ds = 1.  Loaded one tile ahead.
-    auto load_tile = [&](int r0, uint32_t (&w)[8], bool& live) {
+    auto load_tile = [&](int r0, uint32_t (&w)[8], bool& live, float& nrm) {
       const bool rv = r0 + col < sz;
       const int64_t slot = st + (rv ? r0 + col : 0);
       const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(a.codes) + slot;
@@ -395,13 +478,17 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
         const int gq = DS == 2 ? 2 * i + half : 4 * (i >> 1) + 2 * half + (i & 1);
         w[i] = rv ? cw[(int64_t)gq * a.n_slots] : 0u;
       }
-      live = rv && !(a.is_empty && a.is_empty[slot]);
+      if constexpr (NORMS)
+        nrm = rv && half == 0 ? a.norm[slot] : __builtin_nanf("");
+      else
+        live = rv && !(a.is_empty && a.is_empty[slot]);
     };
     uint32_t w[8], wn[8];
     bool live = false, live_n = false;
-    if (sz > 0) load_tile(0, w, live);
+    float nrm = 0.f, nrm_n = 0.f;
+    if (sz > 0) load_tile(0, w, live, nrm);
     for (int r0 = 0; r0 < sz; r0 += 32) {
-      if (r0 + 32 < sz) load_tile(r0 + 32, wn, live_n);
+      if (r0 + 32 < sz) load_tile(r0 + 32, wn, live_n, nrm_n);
       f32x16 acc = zero_f32x16();
       float x2 = 0.f;
 #pragma unroll
@@ -414,7 +501,7 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
           for (int bb = 0; bb < 4; ++bb)
             en[bb] = reinterpret_cast<const uint2*>(book)[(j0 + bb) * 256 + (int)((w[s] >> (8 * bb)) & 255u)];
 #pragma unroll
-          for (int bb = 0; bb < 4; ++bb) {
+          for (int bb = 0; bb < 4 && !NORMS; ++bb) {
             const float v0 = f16_lo(en[bb].x) + f16_lo(en[bb].y), v1 = f16_hi(en[bb].x) + f16_hi(en[bb].y);
             x2 = fmaf(v0, v0, x2);
             x2 = fmaf(v1, v1, x2);
@@ -428,7 +515,7 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
           for (int bb = 0; bb < 8; ++bb)
             en[bb] = book[(j0 + bb) * 256 + (int)((w[2 * s + (bb >> 2)] >> (8 * (bb & 3))) & 255u)];
 #pragma unroll
-          for (int bb = 0; bb < 8; ++bb) {
+          for (int bb = 0; bb < 8 && !NORMS; ++bb) {
             const float v0 = f16_lo(en[bb]) + f16_hi(en[bb]);
             x2 = fmaf(v0, v0, x2);
           }
@@ -442,10 +529,14 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), ql[s], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), qh[s], acc, 0, 0, 0);
       }
-      // |x'|^2 of the row: this lane's half of the components and the other half-wave's
-      x2 += __shfl_xor(x2, 32, 64);
       // (a row past the cell's size or a tombstone: NaN, which no comparison passes)
-      if (half == 0) x2w[col] = live ? x2 * inv_sx2 : __builtin_nanf("");
+      if constexpr (NORMS) {
+        if (half == 0) x2w[col] = nrm;
+      } else {
+        // |x'|^2 of the row: this lane's half of the components and the other half-wave's
+        x2 += __shfl_xor(x2, 32, 64);
+        if (half == 0) x2w[col] = live ? x2 * inv_sx2 : __builtin_nanf("");
+      }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       // accumulator register 4 g + i holds row 8 g + 4 half + i of the tile: four 16-byte reads bring the 16 norms
       float fast[16];
@@ -462,17 +553,19 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
         }
       }
       if (pass != 0u) {
+        // one counter round trip per lane and tile, not one per row: the lane's rows take consecutive entries
+        const int n_pass = __builtin_popcount(pass);
+        int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], n_pass);
+        if (e + n_pass > cap) a.flags[q] = a.epoch;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if ((pass >> r) & 1u) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], 1);
             if (e < cap) {
               a.keys[(int64_t)q * cap + e] = f2key(fast[r]);
               a.idx[(int64_t)q * cap + e] = ~(unsigned)(st + r0 + row);
-            } else {
-              a.flags[q] = a.epoch;
             }
+            ++e;
           }
         }
       }
@@ -480,6 +573,7 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) w[i] = wn[i];
       live = live_n;
+      nrm = nrm_n;
     }
   }
 }
@@ -495,6 +589,10 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   TPQ_LAUNCH_CHECK("cell_scan_kernel");
   hipLaunchKernelGGL(cell_scatter_kernel, per_query, dim3(256), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_scatter_kernel");
+  int dev = 0, n_cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
+    n_cus = 256;
   // one workgroup of eight waves per CU, fewer when the call cannot list that many (cell, group) blocks: at most one
   // per listed cell plus one per full group of pairs
   const int64_t np = (int64_t)a.nq * (a.max_nprobe > a.p0 ? a.max_nprobe - a.p0 : 0);
@@ -502,16 +600,19 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   if (blocks > np) blocks = np;
   if (blocks < 1) return TPQ_OK;
   blocks = (blocks + 7) / 8;
-  int dev = 0, n_cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
-    n_cus = 256;
   if (blocks > n_cus) blocks = n_cus;
-  if (a.ds == 1)
-    return launch_with_lds(cell_cand_kernel<1>, "cell_cand_kernel", dim3((unsigned)blocks), dim3(512),
-                           CellBook<1>::kBytes, st, a);
-  return launch_with_lds(cell_cand_kernel<2>, "cell_cand_kernel", dim3((unsigned)blocks), dim3(512),
-                         CellBook<2>::kBytes, st, a);
+  const dim3 grid((unsigned)blocks), wg(512);
+  if (a.norm) {
+    // the norms of the listed cells, once per call: cells dealt over at most one workgroup per CU
+    const dim3 norm_grid((unsigned)(a.n_cells < n_cus ? a.n_cells : n_cus));
+    const int rc = a.ds == 1 ? launch_with_lds(cell_norm_kernel<1>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 4, st, a)
+                             : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
+    if (rc) return rc;
+    return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, true>, "cell_cand_kernel", grid, wg, CellBook<1>::kBytes, st, a)
+                     : launch_with_lds(cell_cand_kernel<2, true>, "cell_cand_kernel", grid, wg, CellBook<2>::kBytes, st, a);
+  }
+  return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, false>, "cell_cand_kernel", grid, wg, CellBook<1>::kBytes, st, a)
+                   : launch_with_lds(cell_cand_kernel<2, false>, "cell_cand_kernel", grid, wg, CellBook<2>::kBytes, st, a);
 }
 
 }  // namespace tpq
@@ -550,7 +651,7 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
   a.p0 = first_probe; a.k = 0; a.chunks = capacity / 64; a.epoch = 1; a.rel = cell_delta_rel(ds);
   a.thr_in = threshold;
   a.keys = out_keys; a.idx = out_addr; a.flags = out_flags; a.ws_delta = out_delta;
-  cell_fill_extras(a, workspace);
+  cell_fill_extras(a, workspace, workspace_bytes);  // (with room behind the extras: the slot norms, once per call)
   a.cnt = out_count;
   return launch_cell_candidates(a, reinterpret_cast<hipStream_t>(stream));
 }
@@ -558,4 +659,10 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
 extern "C" size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe) {
   if (nq <= 0 || max_nprobe < 1 || n_cells < 1 || first_probe < 0) return 0;
   return cell_extra_bytes(nq, max_nprobe, n_cells, first_probe);
+}
+
+extern "C" size_t tpq_ivfpq_cell_candidates_norms_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe,
+                                                                  int64_t n_slots) {
+  if (nq <= 0 || max_nprobe < 1 || n_cells < 1 || first_probe < 0 || n_slots < 0) return 0;
+  return cell_extra_bytes(nq, max_nprobe, n_cells, first_probe) + cell_norm_bytes(n_slots);
 }

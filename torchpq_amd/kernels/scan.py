@@ -126,19 +126,28 @@ class IVFPQTopkHip:
         a large batch of more than one round of workgroup slots whose workspace has room for the order)"""
         return None if self.last_call is None else self.ordered(self.last_workspace_bytes)
 
+    def _cell_query(self, name, workspace_bytes, n_cells, n_slots):
+        if self.last_call is None:
+            return None
+        c = self.last_call
+        code = getattr(load(), name)(int(c["n_query"]), int(c["k"]), int(c["n_split"]), self.m, int(c["ds"]),
+                                     int(c["n_probe"]), int(c["slots_hint"] or 0), int(bool(c["has_lut"])),
+                                     int(bool(c["packed"]) and self.m in PACKED_M), int(c["n_split"] > 1),
+                                     int(bool(c.get("residual", False))), int(n_cells), int(n_slots),
+                                     int(workspace_bytes))
+        return code == 1
+
     def cell_major(self, workspace_bytes, n_cells, n_slots):
         """diagnostics: whether the last topk_fused call, handed `workspace_bytes` of workspace and the probed cells of
         an index of `n_cells` cells over `n_slots` slots, takes the cell-major form of the large-batch route
         (tpq_ivfpq_scan_cell_major: the library's own rule, nothing is launched)"""
-        if self.last_call is None:
-            return None
-        c = self.last_call
-        code = load().tpq_ivfpq_scan_cell_major(int(c["n_query"]), int(c["k"]), int(c["n_split"]), self.m, int(c["ds"]),
-                                                 int(c["n_probe"]), int(c["slots_hint"] or 0), int(bool(c["has_lut"])),
-                                                 int(bool(c["packed"]) and self.m in PACKED_M), int(c["n_split"] > 1),
-                                                 int(bool(c.get("residual", False))), int(n_cells), int(n_slots),
-                                                 int(workspace_bytes))
-        return code == 1
+        return self._cell_query("tpq_ivfpq_scan_cell_major", workspace_bytes, n_cells, n_slots)
+
+    def cell_norms(self, workspace_bytes, n_cells, n_slots):
+        """diagnostics: whether such a call takes the form AND its candidate kernel reads the slot norms of an array
+        computed once per call -- the workspace has room for it behind the lists and inversion arrays in use -- and does
+        not form them in every block (tpq_ivfpq_scan_cell_norms: the library's own rule, nothing is launched)"""
+        return self._cell_query("tpq_ivfpq_scan_cell_norms", workspace_bytes, n_cells, n_slots)
 
     def last_cell_major(self):
         """diagnostics: whether the last topk / topk_fused call ran the cell-major form (csrc/scan_cells.hip): it handed
@@ -148,6 +157,15 @@ class IVFPQTopkHip:
         if self._last_cells is None:
             return False
         return self.cell_major(self.last_workspace_bytes, *self._last_cells)
+
+    def last_cell_norms(self):
+        """diagnostics: whether the last topk / topk_fused call ran the cell-major form with per-call slot norms
+        (cell_norm_kernel, csrc/scan_cells.hip); False where last_cell_major() is"""
+        if self.last_call is None:
+            return None
+        if self._last_cells is None:
+            return False
+        return self.cell_norms(self.last_workspace_bytes, *self._last_cells)
 
     def _n_split(self, n_query, device, slots_hint=None):
         """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
@@ -383,9 +401,11 @@ class CellCandidatesHip:
     delta_q; m = 64, sub-vectors of 1 or 2 components."""
 
     def __call__(self, data, query, codebook, cells, n_cells, cell_start, cell_size, n_probe_list, threshold,
-                 first_probe=0, capacity=1024, is_empty=None, distance="euclidean"):
+                 first_probe=0, capacity=1024, is_empty=None, distance="euclidean", slot_norms=True):
         """-> (count i32 [nq], values f32 [nq, capacity], address i64 [nq, capacity] (-1 past the count), band f32 [nq]
-        = 2 delta_q, flags i32 [nq])"""
+        = 2 delta_q, flags i32 [nq]).  slot_norms: hand over the workspace with room for the per-call slot norms
+        (tpq_ivfpq_cell_candidates_norms_workspace_bytes); False: exactly tpq_ivfpq_cell_candidates_workspace_bytes, and
+        the candidate kernel forms the norms itself.  The same candidates with the same values either way."""
         m, ds, kk = codebook.shape
         n_data = data.shape[1]
         n_query, n_probe = cell_start.shape
@@ -402,7 +422,11 @@ class CellCandidatesHip:
         addr = torch.zeros(n_query, capacity, device=dev, dtype=torch.int32)
         band = torch.zeros(n_query, device=dev, dtype=torch.float32)
         flags = torch.zeros(n_query, device=dev, dtype=torch.int32)
-        ws_bytes = load().tpq_ivfpq_cell_candidates_workspace_bytes(n_query, n_probe, int(n_cells), int(first_probe))
+        if slot_norms:
+            ws_bytes = load().tpq_ivfpq_cell_candidates_norms_workspace_bytes(n_query, n_probe, int(n_cells),
+                                                                              int(first_probe), n_data)
+        else:
+            ws_bytes = load().tpq_ivfpq_cell_candidates_workspace_bytes(n_query, n_probe, int(n_cells), int(first_probe))
         ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
         call("tpq_ivfpq_cell_candidates", dev, ptr(data), ptr(query), ptr(codebook), ds, metric_code(distance),
              ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(cells), int(n_cells),
