@@ -33,21 +33,26 @@
 //                        LDS once -- already scaled and split into its two fp16 pieces, 128 KiB at ds = 2 -- and its waves
 //                        take blocks from a counter, independently: no barrier after the staging.  Per tile of 32 slots,
 //                        lane (row, half) reads the 8 code dwords of its half of every k-step from the reference layout
-//                        [16][n_slots][4] (coalesced over slots, one tile ahead) and gathers its A operand straight from
+//                        [16][n_slots][4] (coalesced over slots, one tile ahead, unconditionally: rows past the size
+//                        are clamped into the cell and masked afterwards) and gathers its A operand straight from
 //                        the codebook in LDS; |x'|^2 is cell_norm_kernel's, loaded with the codes (NORMS), or rides
 //                        along (an fma chain over the same pieces, the two half-waves added), and reaches the
-//                        accumulator's rows through 128 bytes of LDS per wave.  A lane's admitted rows of a tile take
-//                        consecutive entries of its query's list from ONE counter update (a returning atomic per row
-//                        was four or five dependent round trips per tile).
+//                        accumulator's rows through 128 bytes of LDS per wave.  A lane's admitted rows are staged in
+//                        its own segment of LDS and take consecutive entries of its query's list from ONE counter
+//                        update per flush -- at the end of the block, or when a segment is full (a returning atomic
+//                        per row was four or five dependent round trips per tile, one per lane and tile still one).
 //                        A probe listed twice in a row is skipped as the scan skips it (fetch_probes, scan_shared.h).
 //                        (Measured on the headline batch, 10 000 queries x 28 listed probes: sub-vectors gathered from
 //                        the fp32 codebook in global memory into a staged 128-slot tile, 2.66 ms; this form with the
 //                        queries read from [d][nq] per block, 1.06 ms; with the split copy, 0.91 ms; with the norms of a
 //                        tile read in four 16-byte LDS reads and the codes loaded a tile ahead, 0.81 ms (0.78 in the
 //                        later record, profiles/cell_norms_bench.json); with the norms of cell_norm_kernel, 0.68 +
-//                        0.03 ms; with one counter update per lane and tile, 0.53 + 0.03 ms.  Two 32-column query sets
-//                        per decode -- 64 queries per block, 252 registers -- ran 0.55 ms and are not built:
-//                        tools/experiments/cell_two_sets.patch.)
+//                        0.03 ms; with one counter update per lane and tile, 0.53 + 0.03 ms (0.55 in the later
+//                        record, profiles/cell_pipeline_bench.json); with the tile's loads unconditional, so that they
+//                        really run a tile ahead, 0.50 + 0.03 ms; with the admitted rows staged in LDS, 0.43 + 0.03 ms.
+//                        Two 32-column query sets per decode -- 64 queries per block, 252 registers -- ran 0.55 ms
+//                        and are not built: tools/experiments/cell_two_sets.patch; twelve waves per workgroup ran
+//                        0.40 ms with four registers of <2, true> spilled, and are not built either.)
 //
 // Arithmetic.  q' = s_q q = qh + ql + rq,  x' = s_x x = xh + xl + rx  (h = fp16(.), l = fp16(. - h); s_q, s_x powers of
 // two with max |q'_i|, max |s_x c| in [2^12, 2^13): no piece overflows, and the scaling is exact).  Per component
@@ -316,12 +321,21 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
   }
 }
 
+// A candidate workgroup's LDS: the split codebook, per wave the 32 row norms of its tile, and per wave a staging area for
+// admitted rows -- kDepth entries of 8 bytes per lane, entry-major ([entry][lane]: a wave's store of one entry level is
+// contiguous).  kDepth is what the CU's 160 KiB leave behind the ds = 2 book, for either ds: 7 at eight waves.
+constexpr int kCellWaves = 8;
+constexpr size_t kCellLdsBytes = 160 * 1024;
 template <int DS>
 struct CellBook {
   static constexpr int KS = 4 * DS;                            // MFMA k-steps of 16 components
   static constexpr size_t kBook = (size_t)64 * 256 * 4 * DS;   // the split codebook: [j][c] -> DS hi pieces, DS lo pieces
-  static constexpr int kWaves = 8;
-  static constexpr size_t kBytes = kBook + kWaves * 32 * 4;    // + per wave: |x|^2 of the tile's 32 rows (NaN: not live)
+  static constexpr int kWaves = kCellWaves;
+  static constexpr int kThreads = 64 * kWaves;
+  static constexpr size_t kNorms = (size_t)kWaves * 32 * 4;    // per wave: |x|^2 of the tile's 32 rows (NaN: not live)
+  static constexpr int kDepth = (int)((kCellLdsBytes - (size_t)64 * 256 * 8 - kNorms) / ((size_t)kWaves * 64 * 8));
+  static constexpr size_t kBytes = kBook + kNorms + (size_t)kWaves * 64 * kDepth * 8;
+  static_assert(kDepth >= 1 && kBytes <= kCellLdsBytes, "the staging area does not fit the CU's LDS");
 };
 
 __device__ __forceinline__ unsigned pack_f16x2(_Float16 lo, _Float16 hi) {
@@ -401,21 +415,40 @@ __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
 // pieces of 8 components -- straight from the codebook in LDS: no staged tile, no barrier.
 // NORMS: the norm of a row is cell_norm_kernel's (a.norm, loaded with the codes, NaN for a row that is not live) instead
 // of the chain over the gathered pieces; the same bits either way.
+//
+// The tile loop's pipeline.  The loads of tile i + 1 -- 8 code dwords and the norm (NORMS) or the tombstone byte -- are
+// issued at the head of tile i's body, unconditionally and straight-line: a row at or past the cell's size reads the
+// cell's last row (in range: the extent was checked, and a.norm is written for the whole of a listed cell), the last tile
+// prefetches that row again, and rv / the tombstone are applied to the loaded values as selects.  (A load under `rv ? :`
+// is a branch around the load to hipcc, and a full vmcnt(0) behind it: the loads were issued a tile ahead and waited for
+// at once.)  The loop head waits for tile i's own dwords -- the previous prefetch -- BEFORE the new loads go out, and no
+// wait on the new loads stands between their issue and the tile's last MFMA.  A block with nothing to read (extent
+// rejected) is skipped before any load.
+// Admitted rows do not go to the query's list from the loop: a returning atomic there is a second exposed round trip per
+// tile, and its vmcnt(0) drains the prefetch.  Lane (query column, half) appends (f2key(fast), ~address) to its private
+// segment of the wave's staging area.  The wave flushes at the end of its block, and before a tile whose rows some
+// lane's segment cannot take (one ballot, wave-uniform): a flush is ONE counter update per lane that holds entries --
+// its staged entries and, in the loop, the rows of the tile at hand, which are written from registers -- followed by
+// the capacity rule as before (entries at or beyond cap are not written, the query is flagged, cnt counts them all).
 template <int DS, bool NORMS>
-__global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
+__global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellArgs a) {
   using T = CellBook<DS>;
   constexpr int KS = T::KS;
+  constexpr int kDepth = T::kDepth;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* book = reinterpret_cast<unsigned*>(smem);  // DS = 2: [j][c] (h0 h1, l0 l1); DS = 1: [j][c] (h l)
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* x2w = reinterpret_cast<float*>(smem + T::kBook) + wave * 32;
+  uint2* stage = reinterpret_cast<uint2*>(smem + T::kBook + T::kNorms) + wave * (64 * kDepth) + lane;  // [entry][lane]
   int* work = reinterpret_cast<int*>(a.params) + 8;
   const int n_blocks = a.blk_off[a.n_cells];
   const int col = lane & 31, half = lane >> 5;
   const float sx = a.params[3];
   const float inv_sx = 1.f / sx;  // (a power of two: exact)
   const float inv_sx2 = inv_sx * inv_sx;
-  for (int i = tid; i < 64 * 256; i += 512) {  // entry (j, c)
+  // the tombstone bytes, or any readable bytes of one per slot when the index keeps none (the value is not used then)
+  const uint8_t* __restrict__ emp = a.is_empty ? a.is_empty : a.codes;
+  for (int i = tid; i < 64 * 256; i += T::kThreads) {  // entry (j, c)
     const int j = i >> 8, c = i & 255;
     _Float16 h[DS], l[DS];
 #pragma unroll
@@ -452,6 +485,7 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
     const int64_t st = a.cell_st[c];
     int sz = a.cell_sz[c];
     if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (an extent outside the storage is never read)
+    if (sz == 0) continue;
     // this lane's query: pieces of s_q q for the B operand, threshold and scales
     const bool qvalid = col < nqs;
     const int q = qvalid ? a.pairs[first + col] : 0;
@@ -468,27 +502,70 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
       ql[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 128 + 16 * s) : z);
     }
     // the code dwords of this lane's components: k-step s holds components [16 s + 8 half, + 8), i.e. sub-quantizers
-    // [(16 s + 8 half) / DS, + 8 / DS): one dword at ds = 2, two at ds = 1.  Loaded one tile ahead.
-    auto load_tile = [&](int r0, uint32_t (&w)[8], bool& live, float& nrm) {
-      const bool rv = r0 + col < sz;
-      const int64_t slot = st + (rv ? r0 + col : 0);
+    // [(16 s + 8 half) / DS, + 8 / DS): one dword at ds = 2, two at ds = 1; aux: the norm's bits (NORMS) or the tombstone
+    // byte.  Every load is unconditional: a row past the size reads the cell's last row (0 < sz, st + sz <= n_slots)
+    auto load_tile = [&](int r0, uint32_t (&w)[8], unsigned& aux) {
+      const int row = r0 + col < sz ? r0 + col : sz - 1;
+      const int64_t slot = st + row;
       const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(a.codes) + slot;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int gq = DS == 2 ? 2 * i + half : 4 * (i >> 1) + 2 * half + (i & 1);
-        w[i] = rv ? cw[(int64_t)gq * a.n_slots] : 0u;
+        w[i] = cw[(int64_t)gq * a.n_slots];
       }
       if constexpr (NORMS)
-        nrm = rv && half == 0 ? a.norm[slot] : __builtin_nanf("");
+        aux = __float_as_uint(a.norm[slot]);
       else
-        live = rv && !(a.is_empty && a.is_empty[slot]);
+        aux = emp[slot];
+    };
+    // a flush: one counter update for the lane's staged entries and the rows `pass` of the tile at r0
+    int fill = 0;
+    auto flush = [&](unsigned pass, const float (&fast)[16], int r0) {
+      const int total = fill + __builtin_popcount(pass);
+      if (total > 0) {
+        int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], total);
+        if (e + total > cap) a.flags[q] = a.epoch;
+        unsigned* __restrict__ qkeys = a.keys + (int64_t)q * cap;
+        unsigned* __restrict__ qidx = a.idx + (int64_t)q * cap;
+#pragma unroll
+        for (int i = 0; i < kDepth; ++i) {
+          if (i < fill) {
+            if (e < cap) {
+              const uint2 v = stage[i * 64];
+              qkeys[e] = v.x;
+              qidx[e] = v.y;
+            }
+            ++e;
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if ((pass >> r) & 1u) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (e < cap) {
+              qkeys[e] = f2key(fast[r]);
+              qidx[e] = ~(unsigned)(st + r0 + row);
+            }
+            ++e;
+          }
+        }
+      }
+      fill = 0;
     };
     uint32_t w[8], wn[8];
-    bool live = false, live_n = false;
-    float nrm = 0.f, nrm_n = 0.f;
-    if (sz > 0) load_tile(0, w, live, nrm);
+    unsigned aux = 0u, aux_n = 0u;
+    load_tile(0, w, aux);
     for (int r0 = 0; r0 < sz; r0 += 32) {
-      if (r0 + 32 < sz) load_tile(r0 + 32, wn, live_n, nrm_n);
+      load_tile(r0 + 32, wn, aux_n);  // (the last tile: the cell's last row again)
+      const bool rv = r0 + col < sz;
+      // (opaque: a load whose only use is a select is sunk under the select's condition, and waited for there)
+      asm volatile("" : "+v"(aux));
+      float nrm = 0.f;
+      bool live = false;
+      if constexpr (NORMS)
+        nrm = rv ? __uint_as_float(aux) : __builtin_nanf("");
+      else
+        live = rv & ((a.is_empty == nullptr) | (aux == 0u));
       f32x16 acc = zero_f32x16();
       float x2 = 0.f;
 #pragma unroll
@@ -552,29 +629,27 @@ __global__ __launch_bounds__(512) void cell_cand_kernel(CellArgs a) {
           pass |= (qvalid && xr[i] == xr[i] && fast[r] >= thr) ? (1u << r) : 0u;
         }
       }
-      if (pass != 0u) {
-        // one counter round trip per lane and tile, not one per row: the lane's rows take consecutive entries
-        const int n_pass = __builtin_popcount(pass);
-        int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], n_pass);
-        if (e + n_pass > cap) a.flags[q] = a.epoch;
+      // the lane's rows go to its segment; a tile that some lane's segment cannot take flushes the wave first, and
+      // takes its own rows along in the same counter update
+      if (__ballot(fill + __builtin_popcount(pass) > kDepth) != 0ull) {
+        flush(pass, fast, r0);
+      } else if (pass != 0u) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if ((pass >> r) & 1u) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (e < cap) {
-              a.keys[(int64_t)q * cap + e] = f2key(fast[r]);
-              a.idx[(int64_t)q * cap + e] = ~(unsigned)(st + r0 + row);
-            }
-            ++e;
+            stage[fill * 64] = make_uint2(f2key(fast[r]), ~(unsigned)(st + r0 + row));
+            ++fill;
           }
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
       for (int i = 0; i < 8; ++i) w[i] = wn[i];
-      live = live_n;
-      nrm = nrm_n;
+      aux = aux_n;
     }
+    const float none[16] = {};
+    flush(0u, none, 0);
   }
 }
 
@@ -599,20 +674,20 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   int64_t blocks = (int64_t)a.n_cells + np / kCellGroup;
   if (blocks > np) blocks = np;
   if (blocks < 1) return TPQ_OK;
-  blocks = (blocks + 7) / 8;
+  blocks = (blocks + kCellWaves - 1) / kCellWaves;
   if (blocks > n_cus) blocks = n_cus;
-  const dim3 grid((unsigned)blocks), wg(512);
+  const dim3 grid((unsigned)blocks), wg(512), cand_wg(64 * kCellWaves);
   if (a.norm) {
     // the norms of the listed cells, once per call: cells dealt over at most one workgroup per CU
     const dim3 norm_grid((unsigned)(a.n_cells < n_cus ? a.n_cells : n_cus));
     const int rc = a.ds == 1 ? launch_with_lds(cell_norm_kernel<1>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 4, st, a)
                              : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
     if (rc) return rc;
-    return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, true>, "cell_cand_kernel", grid, wg, CellBook<1>::kBytes, st, a)
-                     : launch_with_lds(cell_cand_kernel<2, true>, "cell_cand_kernel", grid, wg, CellBook<2>::kBytes, st, a);
+    return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, true>, "cell_cand_kernel", grid, cand_wg, CellBook<1>::kBytes, st, a)
+                     : launch_with_lds(cell_cand_kernel<2, true>, "cell_cand_kernel", grid, cand_wg, CellBook<2>::kBytes, st, a);
   }
-  return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, false>, "cell_cand_kernel", grid, wg, CellBook<1>::kBytes, st, a)
-                   : launch_with_lds(cell_cand_kernel<2, false>, "cell_cand_kernel", grid, wg, CellBook<2>::kBytes, st, a);
+  return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, false>, "cell_cand_kernel", grid, cand_wg, CellBook<1>::kBytes, st, a)
+                   : launch_with_lds(cell_cand_kernel<2, false>, "cell_cand_kernel", grid, cand_wg, CellBook<2>::kBytes, st, a);
 }
 
 }  // namespace tpq
