@@ -29,7 +29,12 @@ __global__ __launch_bounds__(256) void centroid_accum_kernel(const float* __rest
   const bool count_here = (blockIdx.y == 0);
   const float* __restrict__ drow = data + ((int64_t)b * d + e0) * n;
   const int64_t* __restrict__ lrow = labels + (int64_t)b * n;
-  if (ne == kCcDT && (n & 3) == 0) {
+  // 16-byte loads need 16-byte addresses: with n % 4 == 0 every row of data and labels starts a
+  // multiple of 16 bytes after its base, so the two bases decide (a contiguous view with a storage
+  // offset is not aligned); block-uniform, misaligned input takes the scalar loop
+  const bool aligned16 =
+      ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(labels)) & 15) == 0;
+  if (ne == kCcDT && (n & 3) == 0 && aligned16) {
     // full 16-dimension tile, 4 points per thread: 16 independent 16-byte loads in flight per
     // thread before the first LDS atomic (the scalar loop below is latency-bound: one 4-byte
     // load per ds_add)
