@@ -228,7 +228,10 @@ int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes, 
  * capacity: a multiple of 64; workspace: tpq_ivfpq_cell_candidates_workspace_bytes, or
  * tpq_ivfpq_cell_candidates_norms_workspace_bytes (that size + 4 * n_slots rounded up to 256): a workspace of at least
  * the larger size takes the slot norms from an array computed once per call, a smaller one forms them in every block;
- * the same candidates with the same keys either way. */
+ * the same candidates with the same keys either way.
+ * tpq_ivfpq_cell_fold_threshold (host only, launches nothing) is the fold step 4 applies to a euclidean query's
+ * admission threshold: the smallest float t2 with  a >= t2  <=>  fl(a - q2) >= threshold  for every float a (q2 = |q|^2,
+ * finite); -inf, +inf and NaN are returned as they are. */
 int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes, const float* query,
                                  const float* codebook, int ds, int metric, const uint8_t* is_empty,
                                  const int64_t* cell_start, const int64_t* cell_size,
@@ -252,6 +255,7 @@ int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const fl
                               const float* threshold, int64_t n_slots, int nq, int max_nprobe, int m, int capacity,
                               int32_t* out_count, uint32_t* out_keys, uint32_t* out_addr, float* out_delta,
                               int32_t* out_flags, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+float tpq_ivfpq_cell_fold_threshold(float threshold, float q2);
 
 /* ---------------------------------------------------------------------------
  * SURVEY 8(f)-3  residual-PQ list scan (pq_use_residual=True)

@@ -53,6 +53,7 @@ SIGNATURES = {
     "tpq_ivfpq_cell_candidates_norms_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
     "tpq_ivfpq_cell_candidates": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tpq_ivfpq_cell_fold_threshold": (_f, [_f, _f]),
     "tpq_ivfpq_scan_topk_residual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "tpq_residual_part1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

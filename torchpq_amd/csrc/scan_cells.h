@@ -40,7 +40,7 @@ struct CellArgs {
   float* ws_delta;               // [nq] <- 2 delta_q
   // behind the lists (cell_extra_bytes): every array rounded up to 256 bytes
   float* params;                 // [4] max |codebook|, sum_j max_c |c_jc|^2, 0 / 1: the codebook can be scaled
-  float* thr;                    // [nq] tau_q - delta_q
+  float* thr;                    // [nq] tau_q - delta_q; euclidean: folded over |q|^2 (cell_fold_threshold)
   float* qscale;                 // [nq] the query's power-of-two scale
   float* qnorm;                  // [nq] |q|^2
   int* cnt;                      // [nq] candidates admitted (beyond the capacity: counted, not stored)
@@ -64,6 +64,48 @@ inline size_t cell_extra_bytes(int nq, int max_nprobe, int n_cells, int p0) {
 }
 // the slot norms of a call (cell_norm_kernel): one fp32 per slot address
 inline size_t cell_norm_bytes(int64_t n_slots) { return cell_align((size_t)(n_slots > 0 ? n_slots : 0) * 4); }
+// The candidate kernel's folded threshold.  A row is admitted when fl(a - q2) >= thr (a = fl(2 dot - |x|^2), q2 = |q|^2
+// finite); rounding is monotone, so the rows admitted are those with a >= thr2 for ONE float thr2 = the smallest a that
+// passes, and the subtraction leaves the tile loop.  -inf stays -inf, +inf stays +inf, NaN stays NaN (nothing passes).
+// fl(thr + q2) is only where the search starts: where thr + q2 cancels (thr = -1 + 2^-24, q2 = 1) it is millions of
+// floats away from thr2, so the search doubles its step until it brackets thr2 and bisects -- two or three evaluations
+// in the common case.  Floats are walked by their order-preserving integer image (both zeros -> 0).
+__host__ __device__ inline int cell_float_ord(float f) {
+  const unsigned b = __builtin_bit_cast(unsigned, f);
+  return (b & 0x80000000u) ? (int)(0x80000000u - b) : (int)b;
+}
+__host__ __device__ inline float cell_ord_float(int o) {
+  return __builtin_bit_cast(float, o >= 0 ? (unsigned)o : 0x80000000u - (unsigned)o);
+}
+__host__ __device__ inline float cell_fold_threshold(float thr, float q2) {
+  constexpr long long kTop = 0x7f800000;  // the image of +inf
+  if (!(thr == thr) || thr == __builtin_inff() || thr == -__builtin_inff()) return thr;
+  auto pass = [&](long long o) { return (cell_ord_float((int)o) - q2) >= thr; };
+  const float t0 = thr + q2;
+  if (!(t0 == t0)) return t0;  // (q2 not finite: nothing passes)
+  long long lo, hi, step = 1;  // !pass(lo), pass(hi); -inf never passes a finite threshold, +inf always does
+  if (pass(cell_float_ord(t0))) {
+    hi = cell_float_ord(t0);
+    for (;; step *= 2) {
+      lo = hi - step > -kTop ? hi - step : -kTop;
+      if (lo == -kTop || !pass(lo)) break;
+      hi = lo;
+    }
+  } else {
+    lo = cell_float_ord(t0);
+    for (;; step *= 2) {
+      hi = lo + step < kTop ? lo + step : kTop;
+      if (hi == kTop || pass(hi)) break;
+      lo = hi;
+    }
+  }
+  while (hi - lo > 1) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (pass(mid)) hi = mid; else lo = mid;
+  }
+  return cell_ord_float((int)hi);
+}
+
 // points the extras of `a` into `at` (cell_extra_bytes of it); `room` bytes are the caller's from `at` on: the slot
 // norms follow the extras when they fit, else a.norm = nullptr
 void cell_fill_extras(CellArgs& a, void* at, size_t room);

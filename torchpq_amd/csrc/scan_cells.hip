@@ -12,7 +12,8 @@
 //   cell_prep_kernel     one block: the codebook's max |entry| (-> the power-of-two scale s_x) and X^2 = sum_j max_c
 //                        |c_jc|^2 >= |x|^2 of every decodable slot; zeroes the histogram.
 //   cell_seed_kernel     one wave per query: tau_q (the k-th seed, or the caller's threshold), the query's scale s_q and
-//                        |q|^2, delta_q, the admission threshold tau_q - delta_q and ws_delta = 2 delta_q; the seeds into the
+//                        |q|^2, delta_q, the admission threshold tau_q - delta_q (euclidean: folded over |q|^2, see `The
+//                        admission test`) and ws_delta = 2 delta_q; the seeds into the
 //                        first ceil(k / 64) chunks of the query's lists in the finish kernel's format (value image,
 //                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words; the histogram of the
 //                        query's listed probes.  A query that was flagged before, has a non-finite component, norm or
@@ -76,6 +77,38 @@
 // Every slot whose exact value is >= tau_q has fast >= tau_q - delta_q and is admitted; every admitted slot has an exact
 // value >= tau_q - 2 delta_q.  Rows past the cell's size and tombstones never pass.  A candidate beyond the capacity of
 // the query's lists is not written: the query is flagged for the exact kernel.
+//
+// The admission test.  `fast >= tau_q - delta_q` is not evaluated row by row.  With u = 1 / (s_q s_x), a power of two, and
+// thr = fl(tau_q - delta_q):
+//   euclidean      a = fma(S, 2u, -|x|^2) >= thr2,  thr2 = cell_fold_threshold(thr, |q|^2) (scan_cells.h), formed once per
+//                  query by the seed kernel: the smallest float with  a >= thr2  <=>  fl(a - |q|^2) >= thr  for every a
+//                  (rounding is monotone; -inf and +inf fold to themselves).  While S u is a normal number, S u and its
+//                  doubling are exact, a has the bits of fl(2 fl(S u) - |x|^2), and the rows admitted are exactly those
+//                  with fast >= thr.  A NaN norm (tombstone, row past the size) makes a NaN: no separate compare.
+//   inner product  fma(S, u, z) >= thr with z = 0 for a live row and NaN otherwise: fl(S u) >= thr, and NaN rejects.
+// Where S u is subnormal -- |S u| < 2^-126, possible only when the scales multiply to more than 2^78, i.e. the largest
+// components of query and codebook multiply to less than 2^-54 -- fl(S u) rounds and the fma does not: a is then the
+// rounding of the exact 2 S u - |x|^2, the old value that of a number up to 2^-149 away from it, and the two can differ
+// in the last bit.  The containment above is argued for the tested value: it is the line `the two subtractions` with
+// one rounding less before them, so exact >= tau_q still implies admitted; the stored key of an admitted row is
+// formed in the order given under Arithmetic and may then differ from the tested value by 2^-148 at most, against
+// delta_q >= 2^-17 B^2 >= 2^-97 (|q| >= 2^-40): the second statement (exact >= tau_q - 2 delta_q) keeps its slack of 1.25.
+// Only the rows that passed form `fast` (mul, add, two subtractions, the key image): the stored bits are what they were.
+//
+// Staging.  A row's compare leaves the answers of the 64 lanes in a scalar register pair; all 16 compares of a tile are
+// issued first, and the walk over the rows tests the pairs with scalar instructions: a row nobody admitted costs its fma
+// and compare and nothing else.  A row somebody admitted is staged under its mask as exec: one 8-byte LDS store into the
+// lane's segment, fill + 1.  Before it, if any admitting lane's segment is full (one scalar AND of the row's mask with
+// the ballot of fill >= depth), the wave flushes: one counter update per lane that holds entries, its entries copied
+// to the query's lists up to the capacity, the flag set beyond it -- the rule as before; the flush no longer carries
+// rows of the tile at hand in registers.
+// (Measured on the headline batch, profiles/cell_epilogue_bench.json: 427 us before; one-fma test, metric as a template
+// parameter and the mask walk, 366 us; the fold moved from the block prologue to the seed kernel and the compares
+// batched ahead of the walk with the staging blocks out of line, 340 us.  Not built: the codebook as two planes of
+// dwords -- hipcc pairs the two reads into ds_read2st64_b32, the operand moves stay and the half-rate dword reads cost
+// 30 us, tools/experiments/cell_planes.patch --; the gathers of the next k-step issued ahead of a k-step's products,
+// 335 us against 340 and one register over the budget without the slot norms; twelve waves per workgroup, which now fit
+// 168 registers without a spill: 321-331 us, 0.65 % of the step, under five times the step's run-to-run spread.)
 #include <cmath>
 
 #include "mfma_util.h"
@@ -222,7 +255,8 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
   const float B = sqrtf(q2) * 1.000001f + sqrtf(a.params[1]) * 1.000001f;
   const float delta = a.rel * (B * B);
   if (lane == 0) {
-    a.thr[q] = tau - delta;
+    // the candidate kernel's threshold: a row passes when fl(a - |q|^2) >= tau - delta, tested as a >= the fold
+    a.thr[q] = a.euclid ? cell_fold_threshold(tau - delta, q2) : tau - delta;
     a.ws_delta[q] = 2.f * delta;
     a.qscale[q] = pow2i(kCellScaleExp - eq);
     a.qnorm[q] = q2;
@@ -324,7 +358,10 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
 // A candidate workgroup's LDS: the split codebook, per wave the 32 row norms of its tile, and per wave a staging area for
 // admitted rows -- kDepth entries of 8 bytes per lane, entry-major ([entry][lane]: a wave's store of one entry level is
 // contiguous).  kDepth is what the CU's 160 KiB leave behind the ds = 2 book, for either ds: 7 at eight waves.
-constexpr int kCellWaves = 8;
+#ifndef TPQ_CELL_WAVES
+#define TPQ_CELL_WAVES 8  // (variant builds: the A/B of 12)
+#endif
+constexpr int kCellWaves = TPQ_CELL_WAVES;
 constexpr size_t kCellLdsBytes = 160 * 1024;
 template <int DS>
 struct CellBook {
@@ -426,11 +463,11 @@ __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
 // rejected) is skipped before any load.
 // Admitted rows do not go to the query's list from the loop: a returning atomic there is a second exposed round trip per
 // tile, and its vmcnt(0) drains the prefetch.  Lane (query column, half) appends (f2key(fast), ~address) to its private
-// segment of the wave's staging area.  The wave flushes at the end of its block, and before a tile whose rows some
-// lane's segment cannot take (one ballot, wave-uniform): a flush is ONE counter update per lane that holds entries --
-// its staged entries and, in the loop, the rows of the tile at hand, which are written from registers -- followed by
-// the capacity rule as before (entries at or beyond cap are not written, the query is flagged, cnt counts them all).
-template <int DS, bool NORMS>
+// segment of the wave's staging area.  The wave flushes at the end of its block, and before a ROW that some admitting
+// lane's segment cannot take (the row's mask AND one ballot, scalar): a flush is ONE counter update per lane that holds
+// entries, followed by the capacity rule as before (entries at or beyond cap are not written, the query is flagged, cnt
+// counts them all).  EUCLID: the metric, so that the tile loop selects nothing on it (the header: `The admission test`).
+template <int DS, bool NORMS, bool EUCLID>
 __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellArgs a) {
   using T = CellBook<DS>;
   constexpr int KS = T::KS;
@@ -490,9 +527,12 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
     const bool qvalid = col < nqs;
     const int q = qvalid ? a.pairs[first + col] : 0;
     const float sq = qvalid ? a.qscale[q] : 0.f;
-    const float thr = qvalid ? a.thr[q] : INFINITY;
+    const float thr2 = qvalid ? a.thr[q] : INFINITY;  // (the seed kernel's: folded over |q|^2 when euclidean)
     const float q2 = qvalid ? a.qnorm[q] : 0.f;
     const float unscale = qvalid ? (1.f / sq) * inv_sx : 0.f;
+    // the admission test of a row is ONE fma and ONE compare (see the header): test = fma(acc, um, -|x|^2) >= thr2.
+    // A lane without a query has um = 0 and thr2 = +inf: its test value is -|x|^2, 0 or NaN, and never passes
+    const float um = EUCLID ? 2.f * unscale : unscale;
     f16x8 qh[KS], ql[KS];
     const _Float16* __restrict__ qs = a.qsplit + (int64_t)q * kCellQSplit + 8 * half;
 #pragma unroll
@@ -518,36 +558,21 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
       else
         aux = emp[slot];
     };
-    // a flush: one counter update for the lane's staged entries and the rows `pass` of the tile at r0
+    // a flush: one counter update for the lane's staged entries; those at or beyond cap are counted and not written.
+    // (A loop, not unrolled: the flush stands in front of every row of the tile, and runs before few.)
     int fill = 0;
-    auto flush = [&](unsigned pass, const float (&fast)[16], int r0) {
-      const int total = fill + __builtin_popcount(pass);
-      if (total > 0) {
-        int64_t e = (int64_t)seed_entries + atomicAdd(&a.cnt[q], total);
-        if (e + total > cap) a.flags[q] = a.epoch;
-        unsigned* __restrict__ qkeys = a.keys + (int64_t)q * cap;
-        unsigned* __restrict__ qidx = a.idx + (int64_t)q * cap;
-#pragma unroll
-        for (int i = 0; i < kDepth; ++i) {
-          if (i < fill) {
-            if (e < cap) {
-              const uint2 v = stage[i * 64];
-              qkeys[e] = v.x;
-              qidx[e] = v.y;
-            }
-            ++e;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if ((pass >> r) & 1u) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (e < cap) {
-              qkeys[e] = f2key(fast[r]);
-              qidx[e] = ~(unsigned)(st + r0 + row);
-            }
-            ++e;
-          }
+    auto flush = [&]() {
+      if (fill > 0) {
+        const int64_t e0 = (int64_t)seed_entries + atomicAdd(&a.cnt[q], fill);
+        if (e0 + fill > cap) a.flags[q] = a.epoch;
+        unsigned* __restrict__ qkeys = a.keys + (int64_t)q * cap + e0;
+        unsigned* __restrict__ qidx = a.idx + (int64_t)q * cap + e0;
+        const int fits = e0 + fill <= cap ? fill : (e0 < cap ? (int)(cap - e0) : 0);
+#pragma unroll 1
+        for (int i = 0; i < fits; ++i) {
+          const uint2 v = stage[i * 64];
+          qkeys[i] = v.x;
+          qidx[i] = v.y;
         }
       }
       fill = 0;
@@ -606,39 +631,51 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), ql[s], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), qh[s], acc, 0, 0, 0);
       }
-      // (a row past the cell's size or a tombstone: NaN, which no comparison passes)
+      // (a row past the cell's size or a tombstone: NaN, which no comparison passes; the inner product's test needs
+      // only that: its rows carry 0 or NaN)
       if constexpr (NORMS) {
-        if (half == 0) x2w[col] = nrm;
+        if (half == 0) x2w[col] = EUCLID ? nrm : nrm * 0.f;
       } else {
         // |x'|^2 of the row: this lane's half of the components and the other half-wave's
         x2 += __shfl_xor(x2, 32, 64);
-        if (half == 0) x2w[col] = live ? x2 * inv_sx2 : __builtin_nanf("");
+        const float v = live ? x2 * inv_sx2 : __builtin_nanf("");
+        if (half == 0) x2w[col] = EUCLID ? v : v * 0.f;
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      // accumulator register 4 g + i holds row 8 g + 4 half + i of the tile: four 16-byte reads bring the 16 norms
-      float fast[16];
-      unsigned pass = 0u;
+      // accumulator register 4 g + i holds row 8 g + 4 half + i of the tile: four 16-byte reads bring the 16 norms.
+      // A row's compare leaves its 64 lanes' answers in a scalar register pair: whether anybody admitted the row is
+      // scalar work, and a row nobody admitted costs no vector instruction beyond its fma and compare
+      float xr[16];
+      bool adm[16];
+      unsigned long long any[16];  // (the compare's scalar register pair)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        const f32x4 xr = *reinterpret_cast<const f32x4*>(x2w + 8 * gq + 4 * half);
+        const f32x4 x4 = *reinterpret_cast<const f32x4*>(x2w + 8 * gq + 4 * half);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * gq + i;
-          const float dot = acc[r] * unscale;
-          fast[r] = a.euclid ? (2.f * dot - xr[i]) - q2 : dot;
-          pass |= (qvalid && xr[i] == xr[i] && fast[r] >= thr) ? (1u << r) : 0u;
+          xr[r] = x4[i];
+          adm[r] = fmaf(acc[r], um, -xr[r]) >= thr2;
+          any[r] = __ballot(adm[r]);
         }
       }
-      // the lane's rows go to its segment; a tile that some lane's segment cannot take flushes the wave first, and
-      // takes its own rows along in the same counter update
-      if (__ballot(fill + __builtin_popcount(pass) > kDepth) != 0ull) {
-        flush(pass, fast, r0);
-      } else if (pass != 0u) {
+      // (all 16 compares ahead of the walk: sunk to its rows, each is a compare, a wait for its scalar result and a
+      // taken branch, one after the other)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if ((pass >> r) & 1u) {
+      for (int r = 0; r < 16; ++r) asm volatile("" ::"s"(any[r]));
+      // an admitted row goes to its lanes' segments, under the compare's mask -- the key formed as ever, for these
+      // lanes only; a row that some admitting lane's segment cannot take flushes the wave first
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (__builtin_expect(any[r] != 0ull, 0)) {
+          if ((any[r] & __ballot(fill >= kDepth)) != 0ull) flush();
+          if (adm[r]) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            stage[fill * 64] = make_uint2(f2key(fast[r]), ~(unsigned)(st + r0 + row));
+            float s = acc[r];
+            asm volatile("" : "+v"(s));  // (opaque: the keys of all 16 rows are otherwise formed ahead of the walk)
+            const float dot = s * unscale;
+            const float fast = EUCLID ? (2.f * dot - xr[r]) - q2 : dot;
+            stage[fill * 64] = make_uint2(f2key(fast), ~(unsigned)(st + r0 + row));
             ++fill;
           }
         }
@@ -648,9 +685,15 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
       for (int i = 0; i < 8; ++i) w[i] = wn[i];
       aux = aux_n;
     }
-    const float none[16] = {};
-    flush(0u, none, 0);
+    flush();
   }
+}
+
+// the metric is the kernel's: no select on it in the tile loop
+template <int DS, bool NORMS>
+static int launch_cand(const CellArgs& a, dim3 grid, dim3 wg, hipStream_t st) {
+  return a.euclid ? launch_with_lds(cell_cand_kernel<DS, NORMS, true>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a)
+                  : launch_with_lds(cell_cand_kernel<DS, NORMS, false>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a);
 }
 
 int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
@@ -683,11 +726,9 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
     const int rc = a.ds == 1 ? launch_with_lds(cell_norm_kernel<1>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 4, st, a)
                              : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
     if (rc) return rc;
-    return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, true>, "cell_cand_kernel", grid, cand_wg, CellBook<1>::kBytes, st, a)
-                     : launch_with_lds(cell_cand_kernel<2, true>, "cell_cand_kernel", grid, cand_wg, CellBook<2>::kBytes, st, a);
+    return a.ds == 1 ? launch_cand<1, true>(a, grid, cand_wg, st) : launch_cand<2, true>(a, grid, cand_wg, st);
   }
-  return a.ds == 1 ? launch_with_lds(cell_cand_kernel<1, false>, "cell_cand_kernel", grid, cand_wg, CellBook<1>::kBytes, st, a)
-                   : launch_with_lds(cell_cand_kernel<2, false>, "cell_cand_kernel", grid, cand_wg, CellBook<2>::kBytes, st, a);
+  return a.ds == 1 ? launch_cand<1, false>(a, grid, cand_wg, st) : launch_cand<2, false>(a, grid, cand_wg, st);
 }
 
 }  // namespace tpq
@@ -730,6 +771,8 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
   a.cnt = out_count;
   return launch_cell_candidates(a, reinterpret_cast<hipStream_t>(stream));
 }
+
+extern "C" float tpq_ivfpq_cell_fold_threshold(float threshold, float q2) { return cell_fold_threshold(threshold, q2); }
 
 extern "C" size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe) {
   if (nq <= 0 || max_nprobe < 1 || n_cells < 1 || first_probe < 0) return 0;
