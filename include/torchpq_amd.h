@@ -814,6 +814,66 @@ int tpq_ivfpq_range_residual_fill(const uint8_t* codes, const float* part1, cons
                                   int nq, int max_nprobe, int m, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQIndex filtered search: the k best stored codes of the probed cells AMONG the slots a filter allows (no
+ * reference counterpart).  codes, the tables, is_empty, cell_start, cell_size, n_probe_list, n_slots, nq, max_nprobe
+ * and m are those of tpq_ivfpq_range_count / tpq_ivfpq_range_residual_count; the scan reads the reference layout,
+ * codes u8 [m/4][n_slots][4], whatever the index keeps for its unfiltered search.
+ *
+ * Filter     filter_bits u32 [n_filters][filter_stride]: bit (s & 31) of word (s >> 5) of row f says that slot
+ *            address s is allowed by filter f; filter_stride >= ceil(n_slots / 32); the bits of slots >= n_slots are
+ *            padding and are never looked at.  filter_of_query i32 [nq] names the row of every query, NULL: every
+ *            query uses row 0.  A value outside [0, n_filters) gives that query no candidate; neither array is then
+ *            read out of range.
+ * Candidates of a query: those of tpq_ivfpq_range_count -- its first n_probe_list[q] probes (clamped to
+ *            [0, max_nprobe]), a probe whose start equals the previous probe's start skipped, the slots inside
+ *            [start, start + size) and inside [0, n_slots) (a cell that leaves the storage is cut) that are not
+ *            tombstoned (is_empty) -- AND whose bit is set in the query's row.
+ * Value      that of tpq_ivfpq_range_count (plain PQ: v = 0.f, then v += lut[j][q][code_j] for j ascending, the
+ *            table given as `lut` or built from query, codebook, ds and metric) and of tpq_ivfpq_range_residual_count
+ *            (residual PQ: v = base_sims[q][p], then v += LUT_p[j][code_j], stored as v + 0.0f), bit for bit: a
+ *            filtered result, a range hit and an unfiltered top-k result of one slot carry the same bits.  A NaN value
+ *            never enters.
+ * Output     per query the k best candidates by (value descending, address ascending) -- a strict total order: the
+ *            result does not depend on the order the slots are met in, nor on n_split; out_vals f32 [nq][k], out_addr
+ *            i64 [nq][k], positions beyond the candidates (-inf, -1); out_ids i64 [nq][k] or NULL = address2id[out_addr]
+ *            (-1 at the pads), only together with address2id.
+ * The scan tests a slot's bit before it reads the slot's code: a 64-slot tile without an allowed live slot reads no
+ * code, the allowed slots of several tiles are valued together on full waves.
+ *   plain     one workgroup per (query, part), n_split parts, the parts' lists merged as in tpq_ivfpq_scan_topk;
+ *             workspace: tpq_ivfpq_scan_filtered_workspace_bytes(nq, k, n_split) bytes (0 when n_split == 1, or for
+ *             arguments out of range); too small: TPQ_ERR_WORKSPACE.
+ *   residual  one workgroup per query walks its probes, as tpq_ivfpq_scan_topk_residual; no workspace.
+ * m % 4 == 0, 1 <= k <= 1024, 1 <= n_split <= 1024, n_filters >= 1 and filter_stride >= ceil(n_slots / 32), else
+ * TPQ_ERR_INVALID_ARGUMENT; n_slots < 2^31 - 1 and m <= 148 -- the workgroup's LDS holds m KiB of table, 4 KiB of
+ * candidate queues, 4 KiB of pending slots, the probe table and the staged query when the table is built there, in
+ * 160 KiB -- else TPQ_ERR_UNSUPPORTED.  nq == 0 is TPQ_OK without a launch.  Every check comes before the first HIP
+ * call.  Deterministic, no global atomics.  The library allocates nothing.
+ *
+ * tpq_slot_filter_build ORs the bit of every address[i], i < n, that lies in [0, n_slots) into `bits` u32
+ * [>= ceil(n_slots / 32)], one filter row THE CALLER HAS ZEROED (or that holds an earlier set: the result is the
+ * union); other addresses -- the -1 tpq_get_address_by_id gives for an unknown id -- are ignored.  Global atomic OR:
+ * the result does not depend on the order.  n == 0 is TPQ_OK.
+ * ------------------------------------------------------------------------- */
+size_t tpq_ivfpq_scan_filtered_workspace_bytes(int nq, int k, int n_split);
+int tpq_ivfpq_scan_filtered_topk(const uint8_t* codes, const float* lut, const float* query, const float* codebook,
+                                 int ds, int metric, const uint8_t* is_empty, const int64_t* cell_start,
+                                 const int64_t* cell_size, const int64_t* n_probe_list, const uint32_t* filter_bits,
+                                 const int32_t* filter_of_query, int n_filters, int64_t filter_stride,
+                                 float* out_vals, int64_t* out_addr, const int64_t* address2id, int64_t* out_ids,
+                                 int64_t n_slots, int nq, int max_nprobe, int m, int k, int n_split, void* workspace,
+                                 size_t workspace_bytes, tpq_stream_t stream);
+int tpq_ivfpq_scan_filtered_residual_topk(const uint8_t* codes, const float* part1, const float* query,
+                                          const float* codebook, int ds, const float* part2, const float* full_lut,
+                                          const int64_t* cells, const float* base_sims, const uint8_t* is_empty,
+                                          const int64_t* cell_start, const int64_t* cell_size,
+                                          const int64_t* n_probe_list, const uint32_t* filter_bits,
+                                          const int32_t* filter_of_query, int n_filters, int64_t filter_stride,
+                                          float* out_vals, int64_t* out_addr, const int64_t* address2id,
+                                          int64_t* out_ids, int64_t n_slots, int nq, int max_nprobe, int m, int k,
+                                          tpq_stream_t stream);
+int tpq_slot_filter_build(const int64_t* address, int64_t n, uint32_t* bits, int64_t n_slots, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FlatIndex fused exact search: the k best stored vectors of every query without a [nq][n_slots] similarity
  * matrix -- a similarity GEMM on the fp32 matrix cores with a top-k epilogue (the semantics of the reference's
  * TopkBMMCuda, torchpq/kernels/TopkBMMCuda.py, which FlatIndex itself does not use).

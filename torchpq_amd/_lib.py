@@ -121,6 +121,12 @@ SIGNATURES = {
     "tpq_ivfpq_range_residual_segments": (_sz, [_i, _i]),
     "tpq_ivfpq_range_residual_count": (_i, [_vp] * 4 + [_i] + [_vp] * 10 + [_i64, _i, _i, _i, _vp]),
     "tpq_ivfpq_range_residual_fill": (_i, [_vp] * 4 + [_i] + [_vp] * 12 + [_i64, _i, _i, _i, _vp]),
+    "tpq_ivfpq_scan_filtered_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tpq_ivfpq_scan_filtered_topk": (_i, [_vp] * 4 + [_i, _i] + [_vp] * 6 + [_i, _i64] + [_vp] * 4
+                                     + [_i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tpq_ivfpq_scan_filtered_residual_topk": (_i, [_vp] * 4 + [_i] + [_vp] * 10 + [_i, _i64] + [_vp] * 4
+                                              + [_i64, _i, _i, _i, _i, _vp]),
+    "tpq_slot_filter_build": (_i, [_vp, _i64, _vp, _i64, _vp]),
     "tpq_flat_topk_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_flat_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_flat_range_segments": (_sz, [_i, _i]),

@@ -12,8 +12,9 @@ from .. import util
 from ..codec import PQCodec
 from ..container import CellContainer
 from ..fn import IVFPQTopk
-from ..kernels import PACKED_M, IVFPQRangeHip, ResidualPart1Hip, ResidualSlotTermsHip
+from ..kernels import PACKED_M, IVFPQFilteredTopkHip, IVFPQRangeHip, ResidualPart1Hip, ResidualSlotTermsHip
 from ._coarse import CoarseProbeMixin
+from ._filter import IdFilter, filtered_search_batches
 from ._range import range_search_batches
 
 
@@ -70,6 +71,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
                                 distance=distance, verbose=verbose)
         self._ivfpq_topk = IVFPQTopk(n_subvectors=n_subvectors, contiguous_size=self.contiguous_size)
         self._ivfpq_range = IVFPQRangeHip(m=n_subvectors)
+        self._ivfpq_filtered = IVFPQFilteredTopkHip(m=n_subvectors)
         self.to(device)
 
     # ---- knobs (reference :89-232) ---------------------------------------------------------------
@@ -368,3 +370,57 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
             self, x, threshold, lambda xb, thr, sims, cells, n_probe_list, extents: self.range_search_cells(
                 xb, cells, thr, base_sims=sims, n_probe_list=n_probe_list, return_address=True, _extents=extents),
             return_address, sort)
+
+    # ---- filtered search ---------------------------------------------------------------------------
+    def id_filter(self, ids):
+        """ids: an int64 tensor -- one set of allowed ids -- or a sequence of them, one filter row each -> IdFilter,
+        what search_filtered takes.  Ids the index does not hold are ignored; the filter follows later add / remove."""
+        return IdFilter(self, ids)
+
+    def search_cells_filtered(self, x, cells, flt, filter_of_query=None, base_sims=None, n_probe_list=None, k=1,
+                              return_address=False, _extents=None):
+        """The k best live codes of the given cells [n_query, n_probe] among the ids `flt` allows; (values, ids[,
+        address]).  `filter_of_query`: int32 [n_query], the row of `flt` every query uses (None: row 0).  The tables
+        are those search_cells would use; the codes are read in the container's own layout (`_scan_codes()`), never
+        the scan-layout copy.  (`_extents` as in search_cells.)"""
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        lists = dict(data=self._scan_codes(), cell_start=cell_start, cell_size=cell_size, n_probe_list=n_probe_list,
+                     k=k, filter_bits=flt.bits(self), filter_of_query=filter_of_query, is_empty=is_empty,
+                     address2id=self._address2id)
+        fused = self.use_fused_lut and self.d_subvector <= self.fused_lut_max_subvector
+        if self.pq_use_residual:
+            assert base_sims is not None, "base_sims is required when pq_use_residual is True"
+            if self.use_precomputed:
+                if self._precomputed_part2 is None:
+                    self.precompute_part2()
+                tables = dict(part2=self._part2_by_cell, cells=cells)
+                if fused:
+                    tables.update(query=x, codebook=self.pq_codec.codebook)
+                else:
+                    tables.update(part1=ResidualPart1Hip()(x, self.pq_codec.codebook))
+            else:
+                tables = dict(full=self.precomputed_adc_residual(x, cells))
+            vals, address, ids = self._ivfpq_filtered.residual(base_sims=base_sims, **tables, **lists)
+        elif fused:
+            vals, address, ids = self._ivfpq_filtered(query=x, codebook=self.pq_codec.codebook,
+                                                      distance=self.distance, slots_hint=slots_hint, **lists)
+        else:
+            vals, address, ids = self._ivfpq_filtered(precomputed=self.pq_codec.precompute_adc(x),
+                                                      slots_hint=slots_hint, **lists)
+        return (vals, ids, address) if return_address else (vals, ids)
+
+    def search_filtered(self, x, k, flt, filter_of_query=None):
+        """x [d_vector, n_query] f32, flt = index.id_filter(ids) -> (values f32 [n_query, k] descending, ids int64
+        [n_query, k]): the k best stored codes of the query's probed cells (`n_probe`, as in search) AMONG the ids the
+        filter allows, padded with (-inf, -1) where fewer exist.  `filter_of_query`: an int tensor [n_query] choosing
+        the filter's row per query (a filter made from a sequence of id sets); the default is row 0 for every query.
+        A result carries the value search returns for the same code; equal values come by ascending slot address."""
+        x = self._prepare(x)
+        assert 0 < k <= 1024
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        return filtered_search_batches(
+            self, x, flt, filter_of_query, lambda xb, rows, sims, cells, n_probe_list, extents:
+            self.search_cells_filtered(xb, cells, flt, filter_of_query=rows, base_sims=sims,
+                                       n_probe_list=n_probe_list, k=k, _extents=extents))

@@ -173,3 +173,15 @@ class IVFPQRIndex(IVFPQIndex):
         raise NotImplementedError(
             "IVFPQRIndex has no range search: the list scan's values are those of the first code, not the re-ranked "
             "values search returns, so a threshold in this index's value space cannot be applied to them")
+
+    # ---- filtered search -------------------------------------------------------------------------------
+    def search_cells_filtered(self, x, cells, flt, filter_of_query=None, base_sims=None, n_probe_list=None, k=1,
+                              return_address=False, _extents=None):
+        raise NotImplementedError(
+            "IVFPQRIndex has no filtered search: the filtered list scan returns the values of the first code, not the "
+            "re-ranked values search returns")
+
+    def search_filtered(self, x, k, flt, filter_of_query=None):
+        raise NotImplementedError(
+            "IVFPQRIndex has no filtered search: the filtered list scan returns the values of the first code, not the "
+            "re-ranked values search returns")

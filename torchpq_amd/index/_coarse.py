@@ -49,13 +49,16 @@ class CoarseProbeMixin:
         slots_hint = cells.shape[1] * self.capacity // max(self.n_cells, 1)
         return n_probe_list, cell_start, cell_size, slots_hint, self._is_empty if self._has_holes else None
 
-    def _search_batches(self, x, per_batch):
+    def _search_batches(self, x, per_batch, alongside=()):
         """search() over batches of `max_query_batch` prepared queries: per_batch(xb, sims, cells, n_probe_list,
-        extents) returns a tuple of [n_batch, k] tensors; the concatenations (a single batch's own tensors)"""
+        extents) returns a tuple of [n_batch, k] tensors; the concatenations (a single batch's own tensors).
+        `alongside`: per-query tensors [n_query, ...] (or None) that are cut as the queries are and handed to
+        per_batch behind xb -- a filtered search's row of every query"""
         out = []
         for q0 in range(0, max(x.shape[1], 1), self.max_query_batch):
             xb = x[:, q0:q0 + self.max_query_batch].contiguous()
-            out.append(per_batch(xb, *self._probe_with_extents(xb)))
+            cut = tuple(None if t is None else t[q0:q0 + self.max_query_batch].contiguous() for t in alongside)
+            out.append(per_batch(xb, *cut, *self._probe_with_extents(xb)))
         return out[0] if len(out) == 1 else tuple(torch.cat(t, 0) for t in zip(*out))
 
     @property

@@ -898,6 +898,125 @@ class IVFPQRangeHip:
         return _range_two_pass(n_query, device, threshold, passes)
 
 
+class SlotFilterBuildHip:
+    """One row of filter bits from slot addresses (tpq_slot_filter_build, csrc/scan_filtered.hip): bit s & 31 of word
+    s >> 5 for every address s in [0, n_slots); other addresses (-1: an unknown id) are ignored."""
+
+    def __call__(self, address, bits, n_slots):
+        """address: [n] int64; bits: a zeroed (or to be extended) row, [>= ceil(n_slots / 32)] int32; in place"""
+        assert address.dim() == 1 and address.dtype == torch.int64
+        assert bits.dim() == 1 and bits.dtype == torch.int32 and bits.numel() * 32 >= n_slots
+        address = address.contiguous()
+        require_gpu(address, bits)
+        if address.numel() and n_slots:
+            call("tpq_slot_filter_build", bits.device, ptr(address), address.numel(), ptr(bits), int(n_slots))
+        return bits
+
+
+class IVFPQFilteredTopkHip:
+    """Filtered top-k over the lists of IVFPQIndex (tpq_ivfpq_scan_filtered_topk / _residual_topk,
+    csrc/scan_filtered.hip): the k best candidates of IVFPQRangeHip whose slot is allowed by the query's row of filter
+    bits, by (value descending, address ascending), the value being that of the exact reference-layout scan; the
+    semantics are defined in include/torchpq_amd.h.  The scan reads CellContainer._storage itself: there is no
+    scan-layout route."""
+
+    def __init__(self, m=8):
+        assert m % 4 == 0
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
+
+    _n_split = IVFPQTopkHip._n_split
+    _check_lists = IVFPQRangeHip._check_lists
+    _check_fused = IVFPQRangeHip._check_fused
+
+    @staticmethod
+    def _check_filter(filter_bits, filter_of_query, n_data, n_query):
+        """filter_bits [n_filters, stride] int32, stride >= ceil(n_data / 32); filter_of_query [n_query] int32 or None"""
+        assert filter_bits.dim() == 2 and filter_bits.dtype == torch.int32 and filter_bits.shape[0] >= 1
+        assert filter_bits.shape[1] * 32 >= n_data
+        if filter_of_query is not None:
+            assert filter_of_query.shape == (n_query,) and filter_of_query.dtype == torch.int32
+            filter_of_query = filter_of_query.contiguous()
+        return filter_of_query
+
+    def __call__(self, data, cell_start, cell_size, n_probe_list, k, filter_bits, filter_of_query=None,
+                 precomputed=None, query=None, codebook=None, distance="euclidean", is_empty=None, address2id=None,
+                 n_split=None, slots_hint=None):
+        """Plain PQ.
+          data, cell_start, cell_size, n_probe_list, precomputed or (query, codebook, distance), is_empty: as
+          IVFPQRangeHip
+          filter_bits: [n_filters, stride] int32, bit s & 31 of word s >> 5 of a row: slot s is allowed
+          filter_of_query: [n_query] int32, the row of every query (outside [0, n_filters): no candidate); None: row 0
+          address2id: optional [n_data] int64; when given a third tensor (ids) is returned
+        returns (values [n_query, k] descending, address [n_query, k][, ids]); unfilled = (-inf, -1[, -1])
+        """
+        n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
+        filter_of_query = self._check_filter(filter_bits, filter_of_query, n_data, n_query)
+        ds = 0
+        if precomputed is not None:
+            assert precomputed.shape == (self.m, n_query, 256) and precomputed.dtype == torch.float32
+            precomputed, query, codebook = precomputed.contiguous(), None, None
+        else:
+            assert query is not None and codebook is not None
+            query, codebook, ds = self._check_fused(query, codebook, n_query)
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(data, precomputed, query, codebook, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
+                    filter_of_query, address2id)
+        device = data.device
+        values, address, ids = alloc_topk(n_query, k, device, address2id)
+        if n_query == 0:
+            return topk_result(values, address, ids)
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq_scan_filtered_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
+        call("tpq_ivfpq_scan_filtered_topk", device,
+             ptr(data), ptr(precomputed), ptr(query), ptr(codebook), ds, metric_code(distance), ptr(is_empty),
+             ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(filter_bits), ptr(filter_of_query),
+             filter_bits.shape[0], filter_bits.shape[1], ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data,
+             n_query, n_probe, self.m, k, n_split, ptr(ws), ws_bytes)
+        return topk_result(values, address, ids)
+
+    def residual(self, data, base_sims, cell_start, cell_size, n_probe_list, k, filter_bits, filter_of_query=None,
+                 part1=None, part2=None, cells=None, full=None, query=None, codebook=None, is_empty=None,
+                 address2id=None):
+        """Residual PQ: base_sims and the tables as IVFPQRangeHip.residual, everything else, and the result, as
+        __call__; one workgroup per query: there is no n_split"""
+        n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
+        filter_of_query = self._check_filter(filter_bits, filter_of_query, n_data, n_query)
+        assert base_sims.shape == (n_query, n_probe) and base_sims.dtype == torch.float32
+        base_sims = base_sims.contiguous()
+        ds = 0
+        if full is not None:
+            assert full.shape == (n_query, n_probe, self.m, 256) and full.dtype == torch.float32
+            full, part1, part2, cells, query, codebook = full.contiguous(), None, None, None, None, None
+        else:
+            assert part2 is not None and cells is not None
+            assert part2.shape[1:] == (self.m, 256) and part2.dtype == torch.float32
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+            part2, cells = part2.contiguous(), cells.contiguous()
+            if part1 is not None:
+                assert part1.shape == (n_query, self.m, 256) and part1.dtype == torch.float32
+                part1, query, codebook = part1.contiguous(), None, None
+            else:
+                assert query is not None and codebook is not None
+                query, codebook, ds = self._check_fused(query, codebook, n_query)
+        assert 0 < k <= 1024
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(data, part1, query, codebook, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
+                    n_probe_list, filter_bits, filter_of_query, address2id)
+        device = data.device
+        values, address, ids = alloc_topk(n_query, k, device, address2id)
+        if n_query:
+            call("tpq_ivfpq_scan_filtered_residual_topk", device,
+                 ptr(data), ptr(part1), ptr(query), ptr(codebook), ds, ptr(part2), ptr(full), ptr(cells),
+                 ptr(base_sims), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(filter_bits),
+                 ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1], ptr(values), ptr(address),
+                 ptr(address2id), ptr(ids), n_data, n_query, n_probe, self.m, k)
+        return topk_result(values, address, ids)
+
+
 # ---- what the range wrappers share --------------------------------------------------------------------------------
 def _checked_threshold(threshold, n_query):
     """a range search's threshold: a Python float, or one float32 per query (returned contiguous)"""
