@@ -71,6 +71,8 @@ const char* tpq_last_error(void);
  * the order of consume_data, ivfpq_topk.cu:662-679).  Ordering: value descending,
  * exact ties by ascending address.  1 <= k <= 1024, m % 4 == 0, m <= 156.
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed (or hold anything): flags are compared with a per-call epoch, every list, pool, count and
+ * order array a call reads was written by that call's own kernels. */
 size_t tpq_ivfpq_scan_workspace_bytes(int nq, int k, int n_split, int m);
 
 int tpq_ivfpq_scan_topk(const uint8_t* codes, const float* lut, const uint8_t* is_empty,
@@ -246,7 +248,9 @@ int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max
 int tpq_ivfpq_scan_cell_norms(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
                               int has_packed, int has_tickets, int residual, int n_cells, int64_t n_slots,
                               size_t workspace_bytes);
+/* The workspace need not be zeroed: cell_prep_kernel and cell_seed_kernel clear every counter and array the later stages read. */
 size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe);
+/* The workspace need not be zeroed: the slot norms behind the arrays above are written by cell_norm_kernel for every listed cell. */
 size_t tpq_ivfpq_cell_candidates_norms_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe,
                                                        int64_t n_slots);
 int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const float* codebook, int ds, int metric,
@@ -341,6 +345,7 @@ int tpq_coarse_select(const float* dots, const float* a2, const float* b2, float
  * query f32 [d][nq], centroids f32 [d][n_cells], cell_*_tbl i64 [n_cells]
  * -> topk_sims f32 [nq][n_probe] (descending), cells / cell_start / cell_size i64 [nq][n_probe],
  *    n_probe_list i64 [nq].   1 <= n_probe <= min(n_cells, 1024). */
+/* The workspace need not be zeroed: similarities and group maxima are written before the row select reads them. */
 size_t tpq_ivfpq_coarse_probe_workspace_bytes(int nq, int n_cells);
 int tpq_ivfpq_coarse_probe(const float* query, const float* centroids,
                            const int64_t* cell_start_tbl, const int64_t* cell_size_tbl,
@@ -364,6 +369,7 @@ int tpq_ivfpq_coarse_probe(const float* query, const float* centroids,
 #define TPQ_PROBE_ROUTE_AUTO 0
 #define TPQ_PROBE_ROUTE_FP32 1
 #define TPQ_PROBE_ROUTE_FP16 2
+/* The workspace need not be zeroed, on either route (the fp16 pass clears its own counters on the stream). */
 size_t tpq_ivfpq_coarse_probe_route_workspace_bytes(int d, int nq, int n_cells, int route);
 int tpq_ivfpq_coarse_probe_route(const float* query, const float* centroids,
                                  const int64_t* cell_start_tbl, const int64_t* cell_size_tbl,
@@ -375,6 +381,7 @@ int tpq_ivfpq_coarse_probe_route(const float* query, const float* centroids,
  * |C|^2) can be prepared once per codebook into a caller-owned block and handed to every call (`prepared`; NULL: it is
  * prepared into the workspace per call, ~0.1 ms at 16 384 cells).  tpq_ivfpq_coarse_probe_prepared_bytes is 0 for shapes
  * without the fp16 pass.  The block is only read by the probe calls. */
+/* The prepared block need not be zeroed: tpq_ivfpq_coarse_probe_prepare clears its header on the stream and writes the rest. */
 size_t tpq_ivfpq_coarse_probe_prepared_bytes(int d, int n_cells);
 int tpq_ivfpq_coarse_probe_prepare(const float* centroids, int d, int n_cells, void* prepared,
                                    size_t prepared_bytes, tpq_stream_t stream);
@@ -455,12 +462,14 @@ int tpq_max_sim_split(const float* A, const float* B, float* vals, int64_t* inds
 #define TPQ_ASSIGN_ROUTE_AUTO 0
 #define TPQ_ASSIGN_ROUTE_CASCADE 1
 int tpq_coarse_assign_supported(int d, int64_t m, int n);
+/* The workspace need not be zeroed: every counter and flag of the route taken is cleared on the stream by the call. */
 size_t tpq_coarse_assign_workspace_bytes(int d, int64_t m, int n);
 /* diagnostics: byte offset inside the workspace of the int32 count of points the last call
  * re-checked exactly (d > 128: points that got an exact step on their candidates) */
 size_t tpq_coarse_assign_count_offset(int d, int64_t m, int n);
 int tpq_coarse_assign(const float* A, const float* B, float* vals, int64_t* inds, int d, int64_t m, int n,
                       int metric, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+/* The workspace need not be zeroed: every counter and flag of the route taken is cleared on the stream by the call. */
 size_t tpq_coarse_assign_route_workspace_bytes(int d, int64_t m, int n, int route);
 int tpq_coarse_assign_route(const float* A, const float* B, float* vals, int64_t* inds, int d, int64_t m, int n,
                             int metric, int route, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
@@ -473,6 +482,7 @@ int tpq_coarse_assign_route(const float* A, const float* B, float* vals, int64_t
  * resident in LDS and the points streamed (the PQ-codebook training shape, configs[4]).
  * workspace: tpq_max_sim_select_workspace_bytes(l, d, m, n) (dominated by the l x m int32 lists). */
 int tpq_max_sim_select_supported(int l, int d, int64_t m, int n);
+/* The workspace need not be zeroed, and may be the one an earlier call used: maxima, counts and means are cleared by the call. */
 size_t tpq_max_sim_select_workspace_bytes(int l, int d, int64_t m, int n);
 int tpq_max_sim_select(const float* A, const float* B, float* vals, int64_t* inds, int l, int d, int64_t m,
                        int n, int metric, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
@@ -495,9 +505,11 @@ int tpq_max_sim_select(const float* A, const float* B, float* vals, int64_t* ind
  *   fp16 range is handled entirely by the exact path (same results, slower).
  * Shapes: d <= 64, n <= 256, slices below 2 GiB (tpq_lloyd_supported); euclidean only. */
 int tpq_lloyd_supported(int l, int d, int64_t m, int n);
+/* The prepared block need not be zeroed: tpq_lloyd_prepare clears means, scales and flags on the stream and writes the rest. */
 size_t tpq_lloyd_prepared_bytes(int l, int d, int64_t m);
 int tpq_lloyd_prepare(const float* data, const float* centroids0, void* prepared, size_t prepared_bytes,
                       int l, int d, int64_t m, int n, tpq_stream_t stream);
+/* The workspace need not be zeroed, and serves step after step: maxima, counts, flags and the sums are cleared by every call. */
 size_t tpq_lloyd_step_workspace_bytes(int l, int d, int64_t m, int n);
 /* diagnostics: byte offset inside the workspace of the int32 [l] counts of points left undecided by
  * level 1 (the one-product coarse pass) / level 2 (the three-product pass; = re-checked exactly) */
@@ -516,6 +528,7 @@ int tpq_lloyd_step(const float* data, const void* prepared, const float* centroi
  * through 0 * x (up to 256 centroids turn NaN in that dimension); the scalar kernels used for the
  * other shapes, and the reference, confine it to the point's own cluster.  Finite inputs are
  * unaffected; callers that may hold NaN / Inf must sanitise the data first. */
+/* The workspace need not be zeroed: the call clears the sums and counts on the stream. */
 size_t tpq_compute_centroids_workspace_bytes(int l, int d, int k);
 int tpq_compute_centroids(const float* data, const int64_t* labels, float* centroids, int l, int d,
                           int64_t n, int k, void* workspace, size_t workspace_bytes,
@@ -531,6 +544,7 @@ int tpq_compute_centroids(const float* data, const int64_t* labels, float* centr
  * tpq_get_cell_by_address replaces GetDivByAddressV2Cuda torchpq/kernels/cuda/get_div_by_address_v2.cu:9-95
  *   cell whose [start, start+capacity) contains the address, else -1 (cells ordered by start).
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed: keys and positions are written for all n labels before the sort reads them. */
 size_t tpq_get_ioa_workspace_bytes(int64_t n);
 int tpq_get_ioa(const int64_t* labels, int64_t* ioa, int64_t n, int64_t n_cells, void* workspace,
                 size_t workspace_bytes, tpq_stream_t stream);
@@ -621,6 +635,7 @@ int tpq_ivfpqr_rerank(const uint8_t* storage, int64_t capacity, int m, int m_r, 
  * the CU count) and a second launch merges their lists through the caller's workspace of
  * tpq_ivfflat_scan_workspace_bytes(nq, k, n_split) bytes (0 when n_split == 1).  The library allocates nothing.
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed: every workgroup writes its whole list (pads included) before the merge reads it. */
 size_t tpq_ivfflat_scan_workspace_bytes(int nq, int k, int n_split);
 int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_t* is_empty,
                           const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
@@ -656,6 +671,7 @@ int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_
  * or a d / max_nprobe whose query and probe table do not fit the LDS next to the table); nothing is launched.
  * Workspace: tpq_ivfpq4_scan_workspace_bytes(nq, k, n_split) bytes (0 when n_split == 1).  The library allocates nothing.
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed: every workgroup writes its whole list (pads included) before the merge reads it. */
 size_t tpq_ivfpq4_scan_workspace_bytes(int nq, int k, int n_split);
 int tpq_ivfpq4_scan_topk(const uint8_t* codes, const float* query, const float* codebook, const uint8_t* is_empty,
                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
@@ -854,6 +870,7 @@ int tpq_ivfpq_range_residual_fill(const uint8_t* codes, const float* part1, cons
  * union); other addresses -- the -1 tpq_get_address_by_id gives for an unknown id -- are ignored.  Global atomic OR:
  * the result does not depend on the order.  n == 0 is TPQ_OK.
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed: every workgroup writes its whole list (pads included) before the merge reads it. */
 size_t tpq_ivfpq_scan_filtered_workspace_bytes(int nq, int k, int n_split);
 int tpq_ivfpq_scan_filtered_topk(const uint8_t* codes, const float* lut, const float* query, const float* codebook,
                                  int ds, int metric, const uint8_t* is_empty, const int64_t* cell_start,
@@ -904,6 +921,7 @@ int tpq_slot_filter_build(const int64_t* address, int64_t n, uint32_t* bits, int
  * exists anywhere (0 for nq <= 0 or arguments out of range); too small: TPQ_ERR_WORKSPACE.  Two launches (tiles,
  * then a merge that also gathers the ids), no global atomics, deterministic.  The library allocates nothing.
  * ------------------------------------------------------------------------- */
+/* The workspace need not be zeroed: a list that took no candidate is written as pads before the merge reads it. */
 size_t tpq_flat_topk_workspace_bytes(int nq, int k, int n_parts);
 int tpq_flat_topk(const float* vectors, const float* query, const int64_t* address2id,
                   float* out_vals, int64_t* out_addr, int64_t* out_ids,
