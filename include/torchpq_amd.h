@@ -617,7 +617,13 @@ int tpq_ivfpqr_rerank(const uint8_t* storage, int64_t capacity, int m, int m_r, 
  * vectors      f32 [d][n_slots]     dimension-major, slot-contiguous: CellContainer._storage of code_size = 4 d
  *                                   (u8 [d][n_slots][4]) read as fp32 -- row i holds the four bytes of component i
  * query        f32 [d][nq]          (pre-normalised by the host for TPQ_METRIC_INNER)
- * is_empty     u8  [n_slots] or NULL (1 = tombstone)
+ * is_empty     u8  [n_slots] or NULL  a mask: any set of slots the caller wants skipped (non-zero = skip), one for
+ *                                   the whole call -- the container's tombstones, or those OR-ed with the
+ *                                   complement of a filter (IVFFlatIndex.search_filtered).  The byte of a slot is
+ *                                   read before any of its 4 d bytes of vector: a 64-slot tile without a live slot
+ *                                   is not read, a tile with a few live slots is not read either -- its live slots
+ *                                   are gathered with those of other such tiles, 64 at a time -- and in any other
+ *                                   tile only the live slots' vectors are.  NULL: no slot is skipped, no mask read
  * cell_start / cell_size i64 [nq][max_nprobe]; n_probe_list i64 [nq], clamped to [0, max_nprobe]; a probe whose
  *              start equals the previous probe's start is skipped, as in tpq_ivfpq_scan_topk
  * out_vals f32 / out_addr i64 [nq][k]

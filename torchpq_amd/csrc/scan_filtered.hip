@@ -25,8 +25,6 @@
 namespace tpq {
 namespace filtered {
 
-constexpr int kPendingPerWave = 128;  // at most 63 left over + the 64 of one tile
-constexpr size_t kPendingBytes = (size_t)kScanWaves * kPendingPerWave * 4;
 constexpr int kMaxM = 148;      // 148 KiB + 4 KiB + 4 KiB = 156 KiB: 4 KiB left for the probe table and the query
 constexpr int kTilesAhead = 4;  // tiles whose filter words (then tombstone bytes) are loaded together
 constexpr int kRowGroup = 4;    // row loads in flight per lane, as scan_ref_kernel's group
@@ -87,28 +85,6 @@ __device__ __forceinline__ Member member(const uint32_t* __restrict__ row, int s
   if (ok) ok = ((row[s64 >> 5] >> (unsigned)(s64 & 31)) & 1u) != 0;
   return Member{(int)s64, ok};
 }
-
-// the wave's pending slots, in LDS words of its own
-struct Pending {
-  int* at;
-  int n;  // wave-uniform, < 64 between tiles
-  __device__ __forceinline__ void append(bool ok, int s) {
-    const unsigned long long mask = __ballot(ok);
-    if (mask == 0ull) return;
-    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-    if (ok) at[n + rank] = s;
-    n += __popcll(mask);
-  }
-  // the last `count` (<= 64) pending slots, one per lane below `count`
-  __device__ __forceinline__ int take(int count) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    n -= count;
-    const int lane = lane_id();
-    const int s = lane < count ? at[n + lane] : 0;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    return s;
-  }
-};
 
 // `count` pending slots are valued, one per lane, and go through the admission step
 template <int R, bool RESIDUAL>
@@ -307,7 +283,7 @@ extern "C" int tpq_ivfpq_scan_filtered_topk(const uint8_t* codes, const float* l
   }
   const int R = list_regs(k);
   const size_t lds = list_scan_lds_bytes(list_region0<size_t>((size_t)m * 1024, R), max_nprobe,
-                                         filtered::kPendingBytes + (lut ? 0 : (size_t)m * ds * 4));
+                                         kPendingBytes + (lut ? 0 : (size_t)m * ds * 4));
   if (int rc = check_lds(what, lds)) return rc;
   ScanArgs a = scan_args(codes, nullptr, lut, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
                          address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
@@ -348,7 +324,7 @@ extern "C" int tpq_ivfpq_scan_filtered_residual_topk(
   if (build_part1) TPQ_REQUIRE(ds >= 1 && ds <= 1024, "%s: bad sub-vector length %d", what, ds);
   const int R = list_regs(k);
   const size_t lds = list_scan_lds_bytes(list_region0<size_t>((size_t)m * 1024, R), max_nprobe,
-                                         filtered::kPendingBytes + (build_part1 ? (size_t)m * ds * 4 : 0));
+                                         kPendingBytes + (build_part1 ? (size_t)m * ds * 4 : 0));
   if (int rc = check_lds(what, lds)) return rc;
   ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
                          address2id, out_ids, n_slots, nq, max_nprobe, m, k, 1);

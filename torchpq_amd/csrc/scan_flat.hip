@@ -29,8 +29,61 @@ struct FlatArgs {
 
 __host__ __device__ constexpr size_t query_bytes(int d) { return align16((size_t)d * 4); }
 
-// LDS: [query d floats | the finisher's merge lists, which start once the scan is over][queues][probe table][threshold]
+// the value of scan_flat_kernel: `col` is component 0 of the slot, rows are `stride` floats apart; GROUPS groups of
+// kFlatUnroll rows per trip (the order of the sum is the same whatever GROUPS is)
+template <int METRIC, int GROUPS = 2>
+__device__ __forceinline__ float slot_value(const float* __restrict__ col, const float* xq, int d, int64_t stride) {
+  float v = 0.f;
+  int i = 0;
+  // two groups of kFlatUnroll rows per trip is what the compiler makes of the unmasked scan_flat_kernel's loop on its
+  // own; left alone it unrolled the inner-product fill kernel further, to 78 VGPRs (44 / 48 with this,
+  // tools/kernel_regs.py).  The masked scan takes one group: 61 - 71 VGPRs, seven waves per SIMD, against 73 - 81.
+#pragma unroll GROUPS
+  for (; i + kFlatUnroll <= d; i += kFlatUnroll) {
+    float x[kFlatUnroll];
+#pragma unroll
+    for (int u = 0; u < kFlatUnroll; ++u) x[u] = col[(int64_t)u * stride];
+    col += (int64_t)kFlatUnroll * stride;
+#pragma unroll
+    for (int u = 0; u < kFlatUnroll; ++u) v = metric_step<METRIC>(v, xq[i + u], x[u]);
+  }
+  for (; i < d; ++i) {
+    v = metric_step<METRIC>(v, xq[i], *col);
+    col += stride;
+  }
+  return v;
+}
+
+// ---- the masked scan: is_empty != nullptr -----------------------------------------------------------------------------
+// The mask is any set of slots to skip -- the container's tombstones, or those OR-ed with a filter's complement -- so
+// it may be dense.  A lane reads the mask byte of its slot BEFORE any row of the vector, kMaskTilesAhead tiles' bytes in
+// flight together, and the wave ballots:
+//   no live slot                 the tile reads no vector
+//   kCompactBelow live or more   the tile is valued in place, as the unmasked scan values it; its dead lanes load nothing
+//   fewer                        the live slots are appended to the wave's pending list (Pending, scan_list.h); whenever
+//                                64 are pending the wave takes 64 and every lane values one slot; the rest is drained
+//                                after the wave's last tile
+// Keys are (value, address): the order in which slots reach the selector does not change the result.
+// kCompactBelow is measured: compacting every partial tile cost 14 % at a mask that is 99 % live and 17 %
+// at 50 %, where nearly every 128-byte line of a tile holds a live slot anyway; compacting none cost 64 % at 0.1 %,
+// where a tile that is not empty holds one live slot and a wave would run its d row loads for that lane alone.
+constexpr int kMaskTilesAhead = 4;  // tiles whose mask bytes are loaded together
+constexpr int kCompactBelow = 4;    // a tile with fewer live slots than this is compacted
+
+// `count` pending slots are valued, one per lane, and go through the admission step
 template <int R, int METRIC>
+__device__ __forceinline__ void value_pending(const FlatArgs& f, const float* xq, int64_t stride, Pending& pend,
+                                              int count, WaveSelector<R>& sel, unsigned* tau_key) {
+  const int s = pend.take(count);
+  const bool live = lane_id() < count;
+  float v = 0.f;
+  if (live) v = slot_value<METRIC, 1>(f.vectors + s, xq, f.d, stride);
+  admit(sel, tau_key, live, v, s);
+}
+
+// LDS: [query d floats | the finisher's merge lists, which start once the scan is over][queues][probe table][threshold]
+// and, MASKED, the pending lists (8 waves x 128 slots = 4 KiB) behind them
+template <int R, int METRIC, bool MASKED>
 __global__ __launch_bounds__(kScanThreads) void scan_flat_kernel(ScanArgs a, FlatArgs f, size_t region0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* xq = reinterpret_cast<float*>(smem);
@@ -54,33 +107,84 @@ __global__ __launch_bounds__(kScanThreads) void scan_flat_kernel(ScanArgs a, Fla
   const int64_t stride = a.n_slots;
 
   int p = 0;
-  for (int T = t.begin + wave; T < t.end; T += kScanWaves) {
-    p = probe_of(lds.tab, p, T);
-    const Tile tile = tile_at(lds.tab, p, T, lane);
-    const int s = tile.slot();
-    const bool valid = tile.in_cell() && s >= 0 && (int64_t)s < a.n_slots;  // (a cell that leaves the storage is cut)
-    float v = 0.f;
-    bool live = valid;
-    if (valid) {
-      if (a.is_empty) live = (a.is_empty[s] == 0);
-      // (the loop of slot_value below, written out: with that function's `#pragma unroll 2` this kernel compiles to
-      // other code)
-      const float* __restrict__ col = f.vectors + s;
-      int i = 0;
-      for (; i + kFlatUnroll <= d; i += kFlatUnroll) {
-        float x[kFlatUnroll];
+  if constexpr (MASKED) {
+    Pending pend{reinterpret_cast<int*>(lds.tail) + wave * kPendingPerWave, 0};
+    for (int T0 = t.begin + wave; T0 < t.end; T0 += kScanWaves * kMaskTilesAhead) {
+      // a tile's first slot and how many of its lanes lie inside the cell: the same for every lane, so kept as scalars
+      int first[kMaskTilesAhead], inside[kMaskTilesAhead];
 #pragma unroll
-        for (int u = 0; u < kFlatUnroll; ++u) x[u] = col[(int64_t)u * stride];
-        col += (int64_t)kFlatUnroll * stride;
-#pragma unroll
-        for (int u = 0; u < kFlatUnroll; ++u) v = metric_step<METRIC>(v, xq[i + u], x[u]);
+      for (int u = 0; u < kMaskTilesAhead; ++u) {
+        const int T = T0 + u * kScanWaves;
+        first[u] = inside[u] = 0;
+        if (T < t.end) {  // (uniform)
+          p = probe_of(lds.tab, p, T);
+          const Tile tile = tile_at(lds.tab, p, T, 0);
+          first[u] = __builtin_amdgcn_readfirstlane(tile.slot());
+          inside[u] = __builtin_amdgcn_readfirstlane(tile.size - tile.off);
+        }
       }
-      for (; i < d; ++i) {
-        v = metric_step<METRIC>(v, xq[i], *col);
-        col += stride;
+      unsigned long long live_mask[kMaskTilesAhead], valid_mask[kMaskTilesAhead];  // (uniform)
+      {
+        uint8_t dead[kMaskTilesAhead];
+#pragma unroll
+        for (int u = 0; u < kMaskTilesAhead; ++u) {
+          const int s = first[u] + lane;
+          const bool valid = lane < inside[u] && s >= 0 && (int64_t)s < a.n_slots;  // (a cell that leaves the storage is cut)
+          valid_mask[u] = __ballot(valid);
+          dead[u] = valid ? a.is_empty[s] : (uint8_t)1;
+        }
+#pragma unroll
+        for (int u = 0; u < kMaskTilesAhead; ++u) live_mask[u] = __ballot(dead[u] == 0);
+      }
+#pragma unroll
+      for (int u = 0; u < kMaskTilesAhead; ++u) {
+        if (live_mask[u] == 0ull) continue;  // no vector is read
+        int s = first[u] + lane;
+        bool live = (live_mask[u] >> lane) & 1ull;
+        if (live_mask[u] != valid_mask[u] && __popcll(live_mask[u]) < kCompactBelow) {  // a sparse tile: its live slots wait until 64 are pending
+          pend.append(live, s);
+          if (pend.n < 64) continue;
+          s = pend.take(64);
+          live = true;
+        }
+        // a tile is valued in place, as the unmasked scan values it; 64 pending slots one per lane
+        float v = 0.f;
+        if (live) v = slot_value<METRIC, 1>(f.vectors + s, xq, d, stride);
+        admit(sel, lds.tau_key, live, v, s);
       }
     }
-    admit(sel, lds.tau_key, live, v, s);
+    if (pend.n > 0) value_pending<R, METRIC>(f, xq, stride, pend, pend.n, sel, lds.tau_key);
+  } else {
+    for (int T = t.begin + wave; T < t.end; T += kScanWaves) {
+      p = probe_of(lds.tab, p, T);
+      const Tile tile = tile_at(lds.tab, p, T, lane);
+      const int s = tile.slot();
+      const bool valid = tile.in_cell() && s >= 0 && (int64_t)s < a.n_slots;  // (a cell that leaves the storage is cut)
+      float v = 0.f;
+      bool live = valid;
+      if (valid) {
+        // (never taken: a call with a mask runs the MASKED form.  The test stays so that this form compiles to the
+        // instructions it had before there was another)
+        if (a.is_empty) live = (a.is_empty[s] == 0);
+        // (the loop of slot_value above, written out: with that function's `#pragma unroll 2` this kernel compiles to
+        // other code)
+        const float* __restrict__ col = f.vectors + s;
+        int i = 0;
+        for (; i + kFlatUnroll <= d; i += kFlatUnroll) {
+          float x[kFlatUnroll];
+#pragma unroll
+          for (int u = 0; u < kFlatUnroll; ++u) x[u] = col[(int64_t)u * stride];
+          col += (int64_t)kFlatUnroll * stride;
+#pragma unroll
+          for (int u = 0; u < kFlatUnroll; ++u) v = metric_step<METRIC>(v, xq[i + u], x[u]);
+        }
+        for (; i < d; ++i) {
+          v = metric_step<METRIC>(v, xq[i], *col);
+          col += stride;
+        }
+      }
+      admit(sel, lds.tau_key, live, v, s);
+    }
   }
   sel.flush();
   finish_list_scan<R>(a, q, part, sel.top, smem);
@@ -91,7 +195,10 @@ static int dispatch(const ScanArgs& a, const FlatArgs& f, int R, hipStream_t st)
   return with_list_regs(R, [&](auto r_c) {
     constexpr int RC = decltype(r_c)::value;
     const size_t region0 = list_region0(query_bytes(f.d), RC);
-    return launch_list_scan(scan_flat_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_flat_kernel", a,
+    if (a.is_empty)
+      return launch_list_scan(scan_flat_kernel<RC, METRIC, true>, scan_merge_kernel<RC>, "scan_flat_kernel (masked)", a,
+                              list_scan_lds_bytes(region0, a.max_nprobe, kPendingBytes), st, f, region0);
+    return launch_list_scan(scan_flat_kernel<RC, METRIC, false>, scan_merge_kernel<RC>, "scan_flat_kernel", a,
                             list_scan_lds_bytes(region0, a.max_nprobe, 0), st, f, region0);
   });
 }
@@ -105,29 +212,6 @@ static int dispatch(const ScanArgs& a, const FlatArgs& f, int R, hipStream_t st)
 // segments in (query, part, wave) order are tile-ascending whatever n_split is.  LDS: the query and the probe table.
 
 static size_t range_lds_bytes(int d, int max_nprobe) { return query_bytes(d) + probe_table_bytes(max_nprobe); }
-
-// the value of scan_flat_kernel: `col` is component 0 of the slot, rows are `stride` floats apart
-template <int METRIC>
-__device__ __forceinline__ float slot_value(const float* __restrict__ col, const float* xq, int d, int64_t stride) {
-  float v = 0.f;
-  int i = 0;
-  // two groups of kFlatUnroll rows per trip, which is what the compiler makes of scan_flat_kernel's loop on its own;
-  // left alone it unrolled the inner-product fill kernel further, to 78 VGPRs (44 / 48 with this, tools/kernel_regs.py)
-#pragma unroll 2
-  for (; i + kFlatUnroll <= d; i += kFlatUnroll) {
-    float x[kFlatUnroll];
-#pragma unroll
-    for (int u = 0; u < kFlatUnroll; ++u) x[u] = col[(int64_t)u * stride];
-    col += (int64_t)kFlatUnroll * stride;
-#pragma unroll
-    for (int u = 0; u < kFlatUnroll; ++u) v = metric_step<METRIC>(v, xq[i + u], x[u]);
-  }
-  for (; i < d; ++i) {
-    v = metric_step<METRIC>(v, xq[i], *col);
-    col += stride;
-  }
-  return v;
-}
 
 // One pass of one (query, part).  A NaN value and a NaN threshold fail `v >= thr`.
 template <int METRIC, bool FILL>

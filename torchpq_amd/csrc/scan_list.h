@@ -119,6 +119,35 @@ __device__ __forceinline__ void admit(WaveSelector<R>& sel, unsigned* tau_key, b
   admit(sel, tau_key, live, v, s, v);
 }
 
+// ---- pending slots -------------------------------------------------------------------------------------------------
+// The kernels that test a slot before they read it (scan_filtered.hip, the masked scan of scan_flat.hip) compact the
+// slots that pass into a list the wave owns in LDS -- kPendingBytes behind the frame, at ListLds::tail -- and value 64
+// of them at a time, one per lane.
+constexpr int kPendingPerWave = 128;  // at most 63 left over + the 64 of one tile
+constexpr size_t kPendingBytes = (size_t)kScanWaves * kPendingPerWave * 4;
+
+// the wave's pending slots, in LDS words of its own
+struct Pending {
+  int* at;
+  int n;  // wave-uniform, < 64 between tiles
+  __device__ __forceinline__ void append(bool ok, int s) {
+    const unsigned long long mask = __ballot(ok);
+    if (mask == 0ull) return;
+    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+    if (ok) at[n + rank] = s;
+    n += __popcll(mask);
+  }
+  // the last `count` (<= 64) pending slots, one per lane below `count`
+  __device__ __forceinline__ int take(int count) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    n -= count;
+    const int lane = lane_id();
+    const int s = lane < count ? at[n + lane] : 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    return s;
+  }
+};
+
 // ---- values --------------------------------------------------------------------------------------------------------
 // one dimension of a value: -(q - x)^2 or q x added to acc, each operation rounded on its own
 template <int METRIC>

@@ -7,12 +7,17 @@ layout FlatIndex uses, fully coalesced for the list scan (tpq_ivfflat_scan_topk,
 it in place.  add / expand / remove / tombstones / `_address2id` / state_dict are the container's.
 
 The coarse step is IVFPQIndex's (index/_coarse.py).
+
+Filtered search (search_filtered, range_search_filtered) hands the scan a filter row as its skip mask: IdFilter.masks()
+is the row's complement OR-ed with the tombstones, and the masked form of the scan reads a slot's mask byte before any
+of its 4 d bytes of vector, so a tile without an allowed slot costs 64 bytes, not 256 d.
 """
 import torch
 
 from ..container import CellContainer
 from ..kernels import IVFFlatRangeHip, IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
+from ._filter import IdFilter, checked_filter_rows, filtered_search_batches, queries_by_row
 from ._range import range_search_batches
 
 
@@ -118,17 +123,122 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
             _extents=extents))
         return (vals, ids, address) if return_address else (vals, ids)
 
+    # ---- filtered search -------------------------------------------------------------------------------
+    def id_filter(self, ids):
+        """ids: an int64 tensor -- one set of allowed ids -- or a sequence of them, one filter row each -> IdFilter,
+        what search_filtered and range_search_filtered take.  Ids the index does not hold are ignored; the filter
+        follows later add / remove."""
+        return IdFilter(self, ids)
+
+    def search_cells_filtered(self, x, cells, flt, filter_of_query=None, n_probe_list=None, k=1,
+                              return_address=False, _extents=None):
+        """The k best live vectors of the given cells [n_query, n_probe] among the ids `flt` allows; (values, ids[,
+        address]), (-inf, -1) where fewer exist.  `filter_of_query`: an int tensor [n_query], the row of `flt` every
+        query uses (None: row 0); a row outside [0, n_filters) allows nothing.  The scan takes one mask per launch:
+        the queries are grouped by row and every group is one launch with its row of `flt.masks()`, so a batch with
+        many distinct rows pays one launch per row.  When `filter_of_query` is given and the filter has more than one
+        row, the rows are read back to form the groups -- one host synchronisation per call; with one row, or without
+        `filter_of_query`, there is none.  (`_extents` as in search_cells.)"""
+        assert isinstance(flt, IdFilter), "flt is what index.id_filter(ids) returns"
+        n_probe_list, cell_start, cell_size, slots_hint, _ = self._scan_preamble(x, cells, n_probe_list, _extents)
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        masks = flt.masks(self)
+        n_query = x.shape[1]
+        scan = lambda row, xg, cs, sz, npl: self._flat_topk(
+            self._vectors(), xg, cs, sz, npl, k, is_empty=masks[row], distance=self.distance, slots_hint=slots_hint)
+        if filter_of_query is None or flt.n_filters == 1:
+            vals, address = scan(0, x, cell_start, cell_size, n_probe_list)
+            if filter_of_query is not None:      # a row other than 0 allows nothing
+                other = (filter_of_query != 0)[:, None]
+                vals = vals.masked_fill(other, float("-inf"))
+                address = address.masked_fill(other, -1)
+        else:
+            vals = torch.full((n_query, k), float("-inf"), device=self.device, dtype=torch.float32)
+            address = torch.full((n_query, k), -1, device=self.device, dtype=torch.int64)
+            for row, queries in queries_by_row(filter_of_query, n_query, flt.n_filters, self.device):
+                if queries is None:
+                    vals, address = scan(row, x, cell_start, cell_size, n_probe_list)
+                else:
+                    v, a = scan(row, x[:, queries], cell_start[queries], cell_size[queries], n_probe_list[queries])
+                    vals[queries] = v
+                    address[queries] = a
+        ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)
+        return (vals, ids, address) if return_address else (vals, ids)
+
+    def search_filtered(self, x, k, flt, filter_of_query=None):
+        """x [d_vector, n_query] f32, flt = index.id_filter(ids) -> (values f32 [n_query, k] descending, ids int64
+        [n_query, k]): the k best stored vectors of the query's probed cells (`n_probe`, as in search) AMONG the ids the
+        filter allows, padded with (-inf, -1) where fewer exist.  `filter_of_query`: an int tensor [n_query] choosing
+        the filter's row per query (a filter made from a sequence of id sets); the default is row 0 for every query.
+        A result carries the value search returns for the same vector; equal values come by ascending slot address.
+        One launch per distinct row of a batch, and one host synchronisation per batch of `max_query_batch` queries
+        when rows are given and the filter has more than one (search_cells_filtered)."""
+        x = self._prepare(x)
+        assert 0 < k <= 1024
+        assert self.vq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        return filtered_search_batches(
+            self, x, flt, filter_of_query, lambda xb, rows, sims, cells, n_probe_list, extents:
+            self.search_cells_filtered(xb, cells, flt, filter_of_query=rows, n_probe_list=n_probe_list, k=k,
+                                       _extents=extents))
+
     # ---- range search ----------------------------------------------------------------------------------
     def range_search_cells(self, x, cells, threshold, n_probe_list=None, return_address=False, _extents=None):
         """Every live vector of the given cells [n_query, n_probe] whose value is >= `threshold` (a float, or f32
         [n_query]); (lims, values, ids[, address]) in scan order, see range_search.  (`_extents` as in search_cells.)"""
+        return self._range_cells(x, cells, threshold, n_probe_list, return_address, _extents, None, None)
+
+    def range_search_cells_filtered(self, x, cells, threshold, flt, filter_of_query=None, n_probe_list=None,
+                                    return_address=False, _extents=None):
+        """range_search_cells among the ids `flt` allows; `filter_of_query` chooses the filter's row per query, as in
+        search_cells_filtered: one pair of passes per distinct row, the segments put back in query order."""
+        assert isinstance(flt, IdFilter), "flt is what index.id_filter(ids) returns"
+        return self._range_cells(x, cells, threshold, n_probe_list, return_address, _extents, flt, filter_of_query)
+
+    def _range_cells(self, x, cells, threshold, n_probe_list, return_address, extents, flt, filter_of_query):
         n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
-                                                                                        _extents)
-        lims, vals, address = self._flat_range(
-            self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, threshold,
-            is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
+                                                                                        extents)
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        scan = lambda mask, xg, cs, sz, npl, thr: self._flat_range(
+            self._vectors(), xg, cs, sz, npl, thr, is_empty=mask, distance=self.distance, slots_hint=slots_hint)
+        if flt is None:
+            lims, vals, address = scan(is_empty, x, cell_start, cell_size, n_probe_list, threshold)
+        else:
+            lims, vals, address = self._range_by_row(scan, flt.masks(self), x, cell_start, cell_size, n_probe_list,
+                                                     threshold, filter_of_query)
         ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)
         return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+
+    def _range_by_row(self, scan, masks, x, cell_start, cell_size, n_probe_list, threshold, filter_of_query):
+        """the filtered range search of one batch: a scan per distinct filter row over the queries that use it, the
+        segments put back in query order -> (lims, values, address)"""
+        n_query = x.shape[1]
+        groups = queries_by_row(filter_of_query, n_query, masks.shape[0], self.device)
+        if len(groups) == 1 and groups[0][1] is None:
+            return scan(masks[groups[0][0]], x, cell_start, cell_size, n_probe_list, threshold)
+        counts = torch.zeros(n_query, device=self.device, dtype=torch.int64)
+        parts = []
+        for row, queries in groups:
+            thr = threshold[queries] if torch.is_tensor(threshold) else threshold
+            lg, vg, ag = scan(masks[row], x[:, queries], cell_start[queries], cell_size[queries],
+                              n_probe_list[queries], thr)
+            counts[queries] = lg.diff()
+            parts.append((queries, lg, vg, ag))
+        lims = torch.zeros(n_query + 1, device=self.device, dtype=torch.int64)
+        lims[1:] = counts.cumsum(0)
+        total = sum(vg.numel() for _, _, vg, _ in parts)
+        vals = torch.empty(total, device=self.device, dtype=torch.float32)
+        address = torch.empty(total, device=self.device, dtype=torch.int64)
+        for queries, lg, vg, ag in parts:
+            if not vg.numel():
+                continue
+            # hit i of the group belongs to its query j: it goes where that query's segment starts, plus i - lg[j]
+            j = torch.repeat_interleave(torch.arange(queries.numel(), device=self.device), lg.diff(),
+                                        output_size=vg.numel())
+            dest = lims[queries][j] + torch.arange(vg.numel(), device=self.device) - lg[j]
+            vals[dest] = vg
+            address[dest] = ag
+        return lims, vals, address
 
     def range_search(self, x, threshold, return_address=False, sort=False):
         """x [d_vector, n_query] f32, threshold a float or f32 [n_query] -> (lims int64 [n_query + 1], values f32
@@ -145,3 +255,17 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         return range_search_batches(
             self, x, threshold, lambda xb, thr, sims, cells, n_probe_list, extents: self.range_search_cells(
                 xb, cells, thr, n_probe_list, return_address=True, _extents=extents), return_address, sort)
+
+    def range_search_filtered(self, x, threshold, flt, filter_of_query=None, return_address=False, sort=False):
+        """range_search among the ids a filter allows: flt = index.id_filter(ids), `filter_of_query` (an int tensor
+        [n_query]) chooses its row per query as in search_filtered (default: row 0; a row outside [0, n_filters) has
+        no hit).  The same values, order and outputs as range_search.  One pair of passes, and one synchronisation, per
+        distinct row of a batch of `max_query_batch` queries."""
+        x = self._prepare(x)
+        assert self.vq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        rows = checked_filter_rows(self, x, flt, filter_of_query)
+        return range_search_batches(
+            self, x, threshold, lambda xb, thr, rows_b, sims, cells, n_probe_list, extents:
+            self.range_search_cells_filtered(xb, cells, thr, flt, rows_b, n_probe_list, return_address=True,
+                                             _extents=extents), return_address, sort, alongside=(rows,))

@@ -17,11 +17,13 @@ def sort_range_hits(lims, vals, ids, address):
     return vals[order], ids[order], address[order]
 
 
-def range_search_batches(index, x, threshold, per_batch, return_address, sort):
+def range_search_batches(index, x, threshold, per_batch, return_address, sort, alongside=()):
     """range_search() of an IVF index (a CoarseProbeMixin) over batches of `max_query_batch` prepared queries: the
     coarse step per batch, then per_batch(xb, thr, sims, cells, n_probe_list, extents) -- the index's
     range_search_cells -- which returns (lims, values, ids, address); a later batch's lims offset by the hits of the
-    earlier ones, the concatenation (or the empty result), the sort -> (lims, values, ids[, address])"""
+    earlier ones, the concatenation (or the empty result), the sort -> (lims, values, ids[, address]).
+    `alongside`: per-query tensors [n_query, ...] (or None), cut as the queries are and handed to per_batch behind thr
+    (CoarseProbeMixin._search_batches does the same)"""
     n_query = x.shape[1]
     if torch.is_tensor(threshold):
         assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
@@ -31,7 +33,8 @@ def range_search_batches(index, x, threshold, per_batch, return_address, sort):
     for q0 in range(0, n_query, index.max_query_batch):
         xb = x[:, q0:q0 + index.max_query_batch].contiguous()
         thr = threshold[q0:q0 + index.max_query_batch] if torch.is_tensor(threshold) else threshold
-        lb, vb, ib, ab = per_batch(xb, thr, *index._probe_with_extents(xb))
+        cut = tuple(None if t is None else t[q0:q0 + index.max_query_batch].contiguous() for t in alongside)
+        lb, vb, ib, ab = per_batch(xb, thr, *cut, *index._probe_with_extents(xb))
         lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
         vals.append(vb)
         ids.append(ib)
