@@ -13,6 +13,15 @@ constexpr int kCellP0 = TPQ_CELL_P0;
 constexpr int kCellMinRereads = 96;
 constexpr int kCellQSplit = 256;  // halfs per query of the split copy: [hi, lo][128 components]
 constexpr int kCellGroup = 32;   // queries per candidate block: the 32 MFMA columns of a wave
+// the inversion counts and scatters per workgroup, over a slice of this many consecutive queries, in an LDS histogram of
+// one int per cell (profiles/cell_inversion_bench.json)
+#ifndef TPQ_CELL_SLICE
+#define TPQ_CELL_SLICE 128  // (variant builds: the A/B of 128, 256 and 512)
+#endif
+constexpr int kCellSlice = TPQ_CELL_SLICE;
+// cells the LDS histogram takes: 64 KiB, two workgroups per CU.  Beyond it the inversion issues one global atomic per
+// listed pair (a slice's pairs hardly share a cell there, and every workgroup would walk the whole histogram twice)
+constexpr int kCellLdsCells = 16384;
 
 struct CellArgs {
   const uint8_t* codes;          // reference layout [16][n_slots][4]

@@ -15,15 +15,28 @@
 //                        |q|^2, delta_q, the admission threshold tau_q - delta_q (euclidean: folded over |q|^2, see `The
 //                        admission test`) and ws_delta = 2 delta_q; the seeds into the
 //                        first ceil(k / 64) chunks of the query's lists in the finish kernel's format (value image,
-//                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words; the histogram of the
-//                        query's listed probes.  A query that was flagged before, has a non-finite component, norm or
+//                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words.
+//                        A query that was flagged before, has a non-finite component, norm or
 //                        threshold (NaN, +inf), cannot be scaled or lists a cell outside [0, n_cells) is flagged and takes
 //                        no further part (tau = -inf is a threshold like any other: everything is admitted, and what
 //                        does not fit flags the query below).
+//   cell_count_kernel    the histogram of the listed (query, probe) pairs.  One workgroup per slice of kCellSlice
+//                        consecutive queries: the slice's pairs, flattened over the threads (the rows of cells, cell_start
+//                        and cell_size read coalesced), are counted with LDS atomics in a histogram of n_cells ints, and
+//                        every cell the slice lists takes ONE global atomic with the slice's count.  (One global atomic
+//                        per pair, from one wave per query, put ~270 atomics on each of the headline's 1 024 addresses
+//                        and several times that on a popular cell; same-address atomics execute one after the other.
+//                        Measured there, profiles/cell_inversion_bench.json: the seed kernel with that loop 89 us, without
+//                        it 22; the scatter 81 us; count + scatter now 8 + 12 us at 128 queries per slice, the shortest
+//                        of the three lengths measured -- 128, 256 and 512.)
 //   cell_scan_kernel     one block: exclusive prefixes of the histogram (pairs) and of ceil(pairs / 32) (blocks).
-//   cell_scatter_kernel  one wave per query: pairs[cursor[cell]++] = q; the pair that takes a cell's first position
+//   cell_scatter_kernel  the same slices and the same LDS count; one RETURNING global atomic per listed cell reserves the
+//                        slice's consecutive positions in the cell's range and leaves the first in LDS, and a second walk
+//                        places the pairs: pairs[lds_cursor[cell]++] = q; the pair that takes a cell's first position
 //                        writes the cell's extent.  The order inside a cell varies from run to run; nothing downstream
 //                        depends on it.
+//   cell_count_wide_kernel, cell_scatter_wide_kernel   n_cells > kCellLdsCells: one wave per query, one global atomic
+//                        per pair -- the form both stages had before; a slice's pairs hardly share a cell there.
 //   cell_norm_kernel     when the workspace has room for an fp32 per slot behind the other arrays (CellArgs::norm):
 //                        |x'|^2 / s_x^2 of every slot of a listed cell, NaN for a tombstone, once per call -- the bits
 //                        the candidate kernel's own chain forms in every (cell, block).  A thread per slot over a
@@ -291,6 +304,48 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
     if (t < seed_chunks) a.keys[base + e] = key.hi;
     a.idx[base + e] = key.lo;
   }
+}
+
+// The inversion's walk: the listed pairs of the slice of kCellSlice consecutive queries from q0, flattened over the
+// workgroup -- pair i is (q0 + i / np, p0 + i % np), so the rows of cells, cell_start and cell_size are read coalesced.
+// A query the seed kernel flagged lists nothing; every other query's cells lie in [0, n_cells) (the seed kernel's check).
+constexpr int kCellSliceThreads = 1024;
+template <class F>
+__device__ __forceinline__ void for_slice_pairs(const CellArgs& a, int q0, F&& f) {
+  const int np = a.max_nprobe - a.p0;  // (> 0: the launch)
+  const int nqs = a.nq - q0 < kCellSlice ? a.nq - q0 : kCellSlice;
+  for (int i = (int)threadIdx.x; i < nqs * np; i += kCellSliceThreads) {
+    const int dq = i / np;
+    const int q = q0 + dq, p = a.p0 + (i - dq * np);
+    if (p >= cell_n_probe(a, q) || a.flags[q] == a.epoch) continue;
+    const ListedProbe lp = listed_probe(a, q, p);
+    if (lp.listed) f(q, p, lp.cell);
+  }
+}
+// the slice's pairs per cell, in the workgroup's LDS histogram (n_cells ints, n_cells <= kCellLdsCells)
+__device__ __forceinline__ void count_slice(const CellArgs& a, int q0, int* cell_h) {
+  for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) cell_h[c] = 0;
+  __syncthreads();
+  for_slice_pairs(a, q0, [&](int, int, int c) { atomicAdd(&cell_h[c], 1); });
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kCellSliceThreads) void cell_count_kernel(CellArgs a) {
+  extern __shared__ int cell_h[];
+  count_slice(a, (int)blockIdx.x * kCellSlice, cell_h);
+  for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) {
+    const int h = cell_h[c];
+    if (h) atomicAdd(&a.hist[c], h);
+  }
+}
+
+// n_cells > kCellLdsCells: one wave per query, one global atomic per listed pair
+__global__ __launch_bounds__(256) void cell_count_wide_kernel(CellArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (q >= a.nq) return;
+  if (a.flags[q] == a.epoch) return;
+  const int n_probe = cell_n_probe(a, q);
   for (int p = a.p0 + lane; p < n_probe; p += 64) {
     const ListedProbe lp = listed_probe(a, q, p);
     if (lp.listed) atomicAdd(&a.hist[lp.cell], 1);
@@ -336,7 +391,30 @@ __global__ __launch_bounds__(1024) void cell_scan_kernel(CellArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
+// the pair that takes a cell's first position writes the cell's extent (every query lists it with the same)
+__device__ __forceinline__ void place_pair(const CellArgs& a, int q, int p, int c, int pos) {
+  a.pairs[pos] = q;
+  if (pos == a.cell_off[c]) {
+    const int64_t o = (int64_t)q * a.max_nprobe + p;
+    a.cell_st[c] = (int)a.cell_start[o];
+    a.cell_sz[c] = (int)a.cell_size[o];
+  }
+}
+
+__global__ __launch_bounds__(kCellSliceThreads) void cell_scatter_kernel(CellArgs a) {
+  extern __shared__ int cell_h[];
+  const int q0 = (int)blockIdx.x * kCellSlice;
+  count_slice(a, q0, cell_h);
+  // one returning atomic per cell the slice lists: its h consecutive positions, the first of them left in LDS
+  for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) {
+    const int h = cell_h[c];
+    if (h) cell_h[c] = atomicAdd(&a.hist[c], h);
+  }
+  __syncthreads();
+  for_slice_pairs(a, q0, [&](int q, int p, int c) { place_pair(a, q, p, c, atomicAdd(&cell_h[c], 1)); });
+}
+
+__global__ __launch_bounds__(256) void cell_scatter_wide_kernel(CellArgs a) {
   const int lane = (int)(threadIdx.x & 63);
   const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (q >= a.nq) return;
@@ -344,14 +422,7 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(CellArgs a) {
   const int n_probe = cell_n_probe(a, q);
   for (int p = a.p0 + lane; p < n_probe; p += 64) {
     const ListedProbe lp = listed_probe(a, q, p);
-    if (!lp.listed) continue;
-    const int pos = atomicAdd(&a.hist[lp.cell], 1);
-    a.pairs[pos] = q;
-    if (pos == a.cell_off[lp.cell]) {  // the cell's first pair writes its extent (every query lists it with the same)
-      const int64_t o = (int64_t)q * a.max_nprobe + p;
-      a.cell_st[lp.cell] = (int)a.cell_start[o];
-      a.cell_sz[lp.cell] = (int)a.cell_size[o];
-    }
+    if (lp.listed) place_pair(a, q, p, lp.cell, atomicAdd(&a.hist[lp.cell], 1));
   }
 }
 
@@ -703,10 +774,26 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   const dim3 per_query((unsigned)((a.nq + 3) / 4));
   hipLaunchKernelGGL(cell_seed_kernel, per_query, dim3(256), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_seed_kernel");
+  // the inversion: a workgroup per slice of kCellSlice queries over an LDS histogram, while one fits
+  const bool lds_hist = a.n_cells <= kCellLdsCells;
+  const dim3 per_slice((unsigned)((a.nq + kCellSlice - 1) / kCellSlice)), slice_wg(kCellSliceThreads);
+  const size_t hist_lds = (size_t)a.n_cells * sizeof(int);  // (<= 64 KiB: no attribute to raise)
+  if (lds_hist) {
+    hipLaunchKernelGGL(cell_count_kernel, per_slice, slice_wg, hist_lds, st, a);
+    TPQ_LAUNCH_CHECK("cell_count_kernel");
+  } else {
+    hipLaunchKernelGGL(cell_count_wide_kernel, per_query, dim3(256), 0, st, a);
+    TPQ_LAUNCH_CHECK("cell_count_wide_kernel");
+  }
   hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_scan_kernel");
-  hipLaunchKernelGGL(cell_scatter_kernel, per_query, dim3(256), 0, st, a);
-  TPQ_LAUNCH_CHECK("cell_scatter_kernel");
+  if (lds_hist) {
+    hipLaunchKernelGGL(cell_scatter_kernel, per_slice, slice_wg, hist_lds, st, a);
+    TPQ_LAUNCH_CHECK("cell_scatter_kernel");
+  } else {
+    hipLaunchKernelGGL(cell_scatter_wide_kernel, per_query, dim3(256), 0, st, a);
+    TPQ_LAUNCH_CHECK("cell_scatter_wide_kernel");
+  }
   int dev = 0, n_cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
