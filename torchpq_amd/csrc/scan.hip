@@ -105,7 +105,7 @@ struct PackedUnit {
   int (*pool)(const ScanArgs& a, int RL, hipStream_t st);
   int (*dump)(const ScanArgs& a, int RL, int Rf, int mode, hipStream_t st);
   int (*dump_occupancy)(int mode);
-  int (*finish)(const ScanArgs& a, int chunks, int Rf, hipStream_t st);
+  int (*finish)(const ScanArgs& a, int chunks, int Rf, int seed_chunks, const int* cnt, hipStream_t st);
 };
 static const PackedUnit* packed_unit(int m) {
 #define TPQ_UNIT(M) \
@@ -467,9 +467,10 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   cell_fill_extras(c, reinterpret_cast<char*>(workspace) + cm_lists, workspace_bytes - cm_lists);
   rc = launch_cell_candidates(c, st);
   if (rc) return rc;
-  // 5. the finish kernel over the filled chunks: F_k, the cut at F_k - 2 delta_q, the survivors -- seeds included --
-  //    evaluated exactly
-  return u.finish(a, chunks, p.Rf, st);
+  // 5. the finish kernel over the chunks that were filled (the seed chunks and ceil(cnt[q] / 64) behind them): F_k, the
+  //    cut at F_k - 2 delta_q, the survivors among the candidates evaluated exactly; those among the seeds keep the
+  //    values stage 1 gave them (scan_finish.h)
+  return u.finish(a, chunks, p.Rf, (a.k + 63) / 64, c.cnt, st);
 }
 
 extern "C" int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,

@@ -103,16 +103,82 @@ __global__ __launch_bounds__(512) void scan_merge_refine_kernel(ScanArgs a) {
 // arguments), and a second SOURCE of the exact entries -- FROM_LUT: the caller's materialised table [m][nq][256]
 // (tpq_adc_lut's output, the reference boundary: IVFPQTopkCuda.topk(precomputed=...), kernels/IVFPQTopkCuda.py:81-142),
 // gathered per survivor (m independent loads per lane, ascending-j adds); nothing is staged in LDS then.
+//
+// The deal.  Workgroup b of G takes the CONTIGUOUS queries [b nq / G, (b + 1) nq / G): every workgroup's share is within
+// one query of nq / G (queries strided over the grid's waves left the first nq mod 16 G waves a whole query more than the
+// others: at 10 000 queries on 256 CUs, 48 queries on each of 113 CUs against 32 on the rest), and the 16 queries a
+// workgroup holds at one time share the cache lines of query[d][nq].  Its waves draw the queries of that range from a
+// counter in LDS, one atomic per query (kFinishDraw), so that a wave with a long query does not hold back its SIMD's
+// share; where the codebook and the queues leave the CU no LDS for the counter -- RM = 8 beside a codebook -- wave w takes
+// every kFinishWaves-th query of the range (10 000 queries at k = 300: 352 -> 322 us).  RM = 16 beside a codebook keeps
+// the strided deal: its eight waves per workgroup take 4 or 5 queries each either way, so the ranges have nothing to
+// give there.  (That instantiation runs 2 % slower than it did, under either deal -- 10 000 queries at k = 500: 757 ->
+// 774 us strided, 774 -> 792 with the ranges on another machine; 83 -> 97 registers around sixteen-register exact rounds.
+// The cause was not found.)
+//
+// The cell-major form's stage 5 (scan.hip) hands over two more numbers; both are 0 / null everywhere else.
+//  * seed_chunks: the query's first seed_chunks chunks hold the exact top-k of its first probes, written by THIS kernel
+//    in the form's stage 1 and copied there as make_key(value, address) (cell_seed_kernel).  Their survivors are not
+//    queued and not evaluated again: they are inserted as Key{hi, ~address} straight from the registers.  The bits are
+//    those the evaluation would return: stage 1 ran the same chain of this same kernel over the same codebook and query
+//    (the codes, the un-permute, the ascending-j adds), `v + 0.0f` was applied before that value was written, key2f(f2key(v))
+//    == v for every such v, and the exact list orders by (value desc, address asc) whatever the order of the inserts -- a
+//    strict total order.  n_c, and with it the `lost` rule, counts seeds and candidates together as before: the same
+//    queries are flagged.
+//  * cnt[q]: the entries appended behind the seed chunks (the candidate kernel's counter; a count beyond the capacity
+//    flags the query, which is then skipped here).  Only T_q = seed_chunks + ceil(min(cnt, capacity) / 64) chunks hold
+//    anything; the loads, the ballots of the F_k search and the survivor walk stop there (finish_fk_upto: the search,
+//    unrolled for 2, 4, 6, 8, 12 or 16 chunks -- steps of two up to the 8 chunks 99 % of the headline's queries stay
+//    within, mean 4.6; a chunk of a step is a compare, a popcount and an add, and ONE 32-step loop whose chunk walk breaks
+//    at T_q puts a scalar compare and a branch beside each: that form measured 101 us against 92).  The tail of the last chunk is pad: the seed kernel writes ~kPadIdx into
+//    every idx chunk, and `hi` is zeroed under a pad index below.
+// (Measured on the headline batch -- 10 000 queries, k = 100, stage 1 at 4 chunks / stage 5 at 16 --, us per launch,
+// profiles/finish_deal_bench.json: strided deal 114.3 / 146.8; ranges 108.7 / 138.5, the same with and without the
+// counter; seeds kept 119.6 and filled chunks only 114.0 on stage 5, both 92 -- and 103 with the ranges dealt statically:
+// a query then costs one or two exact rounds over 3 to 13 chunks, and the counter evens that out.  48 % of a query's 105
+// survivors are seeds; 23 % of the queries keep more than 64 among their candidates and run a second round.)
 constexpr int finish_waves(int RM) { return RM <= 8 ? 16 : 8; }
 // registers of the finish kernel's exact list.  Round 6: 16 (eight waves per workgroup: 128 KiB of codebook + 32 KiB of
 // survivor queues) -- k in (440, 504] on long cells, whose band holds more than the 512 candidates of RM = 8
 constexpr int kDumpMaxR = 16;
+// the waves draw their queries from a counter in LDS (16 bytes behind the queues)
+constexpr bool finish_draws(int RM, bool from_lut) { return from_lut || RM < 8; }
 static size_t finish_lds_bytes(int m, int ds, int RM, bool from_lut) {
-  return (from_lut ? 0 : (size_t)m * ds * 1024) + (size_t)finish_waves(RM) * RM * 64 * 4;
+  return (from_lut ? 0 : (size_t)m * ds * 1024) + (size_t)finish_waves(RM) * RM * 64 * 4 +
+         (finish_draws(RM, from_lut) ? 16 : 0);
+}
+// F_k over the first N chunks: the largest key image t with at least k entries >= t (0 while fewer than k entries exist)
+template <int N, int NCH>
+__device__ __forceinline__ unsigned finish_fk(const unsigned (&hi)[NCH], int k) {
+  unsigned fk = 0u;
+#pragma unroll 1
+  for (int bit = 31; bit >= 0; --bit) {
+    const unsigned t = fk | (1u << bit);
+    int n = 0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) n += __popcll(__ballot(hi[c] >= t));
+    fk = n >= k ? t : fk;
+  }
+  return fk;
+}
+// ... over the T chunks in use (wave-uniform; the chunks behind them hold 0 and count for nothing)
+template <int N, int NCH>
+__device__ __forceinline__ unsigned finish_fk_upto(const unsigned (&hi)[NCH], int T, int k) {
+  if constexpr (N >= NCH) {
+    return finish_fk<NCH, NCH>(hi, k);
+  } else {
+    if (T <= N) return finish_fk<N, NCH>(hi, k);
+    return finish_fk_upto<(N < 8 ? N + 2 : N + 4), NCH>(hi, T, k);
+  }
 }
 template <int RM, int M, int DS, int NCH, bool FROM_LUT = false>
-__global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kernel(ScanArgs a, int nw_scan, int RL) {
+__global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kernel(ScanArgs a, int nw_scan, int RL,
+                                                                                   int seed_chunks,
+                                                                                   const int* __restrict__ cnt) {
   constexpr int kFinishWaves = finish_waves(RM);
+  constexpr bool kFinishDraw = finish_draws(RM, FROM_LUT);
+  constexpr bool kFinishRanges = kFinishDraw || RM <= 8;
+  constexpr int kSeedMax = RM < NCH ? RM : NCH;  // (seeds are a top-k: k <= 64 RM)
   using L = scan_layout::Layout<M>;
   constexpr int G = M / 4;  // code dwords per slot
   static_assert(DS == 0 || M * DS <= 128, "the query rides in two registers per lane");
@@ -125,17 +191,35 @@ __global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kerne
     float4* dst = reinterpret_cast<float4*>(cb);
     for (int i = threadIdx.x; i < M * ds * 64; i += kFinishWaves * 64) dst[i] = src[i];
   }
-  int* qi = reinterpret_cast<int*>(cb + (FROM_LUT ? 0 : M * ds * 256)) + wave * (RM * 64);  // the wave's survivors (addresses)
+  int* queues = reinterpret_cast<int*>(cb + (FROM_LUT ? 0 : M * ds * 256));
+  int* qi = queues + wave * (RM * 64);           // the wave's survivors (addresses)
+  int* next = queues + kFinishWaves * (RM * 64);  // kFinishDraw: queries of the range handed out so far
+  if (kFinishDraw && threadIdx.x == 0) *next = 0;
   __syncthreads();
   const int n_lists_all = a.n_split * nw_scan;
   const int T_all = n_lists_all * RL;  // chunks per query in the workspace (<= NCH)
   const bool euclid = a.euclid != 0;
-  for (int q = (int)blockIdx.x * kFinishWaves + wave; q < a.nq; q += (int)gridDim.x * kFinishWaves) {
+  // (RM = 16: the queries strided over the grid's waves, as before -- see the header)
+  const int q_lo = kFinishRanges ? (int)((int64_t)blockIdx.x * a.nq / (int64_t)gridDim.x) : (int)blockIdx.x * kFinishWaves;
+  const int q_hi = kFinishRanges ? (int)(((int64_t)blockIdx.x + 1) * a.nq / (int64_t)gridDim.x) : a.nq;
+  const int stride = kFinishRanges ? kFinishWaves : (int)gridDim.x * kFinishWaves;
+  for (int turn = wave;; turn += stride) {
+    int q = q_lo + turn;
+    if constexpr (kFinishDraw) {
+      int t = 0;
+      if (lane == 0) t = atomicAdd(next, 1);
+      q = q_lo + __builtin_amdgcn_readfirstlane(t);
+    }
+    if (q >= q_hi) break;
     if (a.flags[q] == a.epoch) continue;  // the scan left the query to the exact kernel
     // (tail split: an unsplit query filled the lists of its one part only; the stride is that of n_split parts)
     // (dispatch order, ScanArgs::rank: the unsplit queries are the first `unsplit` of the order)
     const int n_lists = (a.rank ? a.rank[q] : q) < a.unsplit ? nw_scan : n_lists_all;
-    const int T = n_lists * RL;  // chunks in use
+    int T = n_lists * RL;  // chunks in use
+    if (cnt) {             // (the cell-major form: one list of T_all chunks, filled from the front)
+      const int room = (T_all - seed_chunks) * 64, n = cnt[q];
+      T = seed_chunks + ((n < room ? n : room) + 63) / 64;
+    }
     // the query: component i in lane i % 64 of register i / 64; |q_j|^2 (ascending-dimension fma chain) in lane j
     float xv[2] = {0.f, 0.f}, q2v = 0.f;
     if constexpr (!FROM_LUT) {
@@ -162,28 +246,25 @@ __global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kerne
     if (lane < n_lists) evict = a.list_evict[(int64_t)q * n_lists_all + lane];
     const float band = a.ws_delta[q];
     // F_k: the largest key image t with at least k entries >= t (0 while fewer than k entries exist)
-    unsigned fk = 0u;
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-      const unsigned t = fk | (1u << bit);
-      int n = 0;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) n += __popcll(__ballot(hi[c] >= t));
-      fk = n >= a.k ? t : fk;
-    }
+    const unsigned fk = finish_fk_upto<2, NCH>(hi, T, a.k);
     const float cut = (fk ? key2f(fk) : -INFINITY) - band;
     const unsigned cutk = f2key(cut);
-    // survivors -> queue; a list that evicted and still ends at or above the cut lost one that mattered
-    int n_c = 0;
+    // survivors -> queue (those of the seed chunks are only counted: they keep their values, see the header); a list
+    // that evicted and still ends at or above the cut lost one that mattered
+    int n_c = 0, n_q = 0;
     bool lost = false;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
+      if (c >= T) break;  // (wave-uniform)
       const bool want = hi[c] != 0u && hi[c] >= cutk;
       const unsigned long long mask = __ballot(want);
       const int n = __popcll(mask);
       const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-      if (want && n_c + rank < RM * 64) qi[n_c + rank] = ix[c];
       n_c += n;
+      if (c >= seed_chunks) {  // (wave-uniform)
+        if (want && n_q + rank < RM * 64) qi[n_q + rank] = ix[c];
+        n_q += n;
+      }
       // (chunk c is rank chunk c % RL of list c / RL: its lane 63 is the list's last entry when c % RL == RL - 1)
       const int l = c / (RL > 0 ? RL : 1);
       const bool last_chunk = (c % (RL > 0 ? RL : 1)) == RL - 1;
@@ -198,10 +279,24 @@ __global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kerne
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     WaveTopK<RM> ex;
     ex.init();
+    // the seed chunks' survivors, as they are
+#pragma unroll 1
+    for (int s = 0; s < seed_chunks; ++s) {
+      unsigned h = 0u;
+      int x = kPadIdx;
+#pragma unroll
+      for (int c = 0; c < kSeedMax; ++c) {
+        h = c == s ? hi[c] : h;  // (wave-uniform selects: the chunks stay in their registers)
+        x = c == s ? ix[c] : x;
+      }
+      const bool want = h != 0u && h >= cutk;
+      if (__ballot(want) == 0ull) continue;
+      ex.insert_unsorted(want ? Key{h, ~(unsigned)x} : pad_key());
+    }
 #pragma unroll
     for (int r = 0; r < RM; ++r) {
-      if (r * 64 >= n_c) break;  // wave-uniform
-      const bool want = r * 64 + lane < n_c;
+      if (r * 64 >= n_q) break;  // wave-uniform
+      const bool want = r * 64 + lane < n_q;
       const int idx = want ? qi[r * 64 + lane] : 0;  // (idle lanes walk slot 0's bytes: in range)
       typename L::chunk_t cw[L::kChunks];
       L::load(a.packed, a.n_slots, idx, cw);

@@ -95,7 +95,7 @@ static bool fuse_fits(int m, int RM) {
   int dispatch_pool_##M(const ScanArgs& a, int RL, hipStream_t st);                                  \
   int dispatch_dump_##M(const ScanArgs& a, int RL, int R, int mode, hipStream_t st);                 \
   int dump_occupancy_##M(int mode);                                                                  \
-  int dispatch_finish_##M(const ScanArgs& a, int chunks, int R, hipStream_t st);
+  int dispatch_finish_##M(const ScanArgs& a, int chunks, int R, int seed_chunks, const int* cnt, hipStream_t st);
 TPQ_PACKED_M_LIST(TPQ_DECLARE_PACKED)
 #undef TPQ_DECLARE_PACKED
 

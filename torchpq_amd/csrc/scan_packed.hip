@@ -79,10 +79,15 @@ static int finish_by_chunks(int T, Go&& go) {
 // what they gain is the early end of the scan workgroup.
 // the finish kernel: survivors in RM = 2, 4 or 8 registers (k <= 56 rides on 2); the exact entries from the codebook
 // in LDS (fused calls; sub-vector length 1 / 2 compiled in at m = 64, read from the arguments otherwise) or gathered from
-// the caller's table (m <= 32); 4, 8 or 16 chunks of 64 keys per query
+// the caller's table (m <= 32); 4, 8 or 16 chunks of 64 keys per query.  seed_chunks, cnt: the cell-major form's stage 5
+// (scan_finish.h) -- one list per query whose first seed_chunks chunks hold exact values, cnt[q] entries behind them
 template <int RM, int M>
-static int launch_finish(const ScanArgs& a, int nw_scan, int RL, hipStream_t st) {
+static int launch_finish(const ScanArgs& a, int nw_scan, int RL, hipStream_t st, int seed_chunks = 0,
+                         const int* cnt = nullptr) {
   const bool from_lut = a.lut != nullptr;
+  TPQ_REQUIRE(seed_chunks >= 0 && seed_chunks <= RM && seed_chunks <= a.n_split * nw_scan * RL,
+              "scan_packed (finish): %d seed chunks beside %d list registers", seed_chunks, RM);
+  TPQ_REQUIRE(!cnt || (a.n_split == 1 && RL == 1), "scan_packed (finish): entry counts take one list per query");
   const size_t flds = finish_lds_bytes(M, a.ds, RM, from_lut);
   // one persistent workgroup per CU (its LDS holds the codebook)
   int dev = 0, n_cus = 0;
@@ -97,7 +102,7 @@ static int launch_finish(const ScanArgs& a, int nw_scan, int RL, hipStream_t st)
   auto go = [&](auto kernel) -> int {
     int rc = set_lds(kernel, flds, "scan_finish_exact_kernel");
     if (rc) return rc;
-    hipLaunchKernelGGL(kernel, grid, block, flds, st, a, nw_scan, RL);
+    hipLaunchKernelGGL(kernel, grid, block, flds, st, a, nw_scan, RL, seed_chunks, cnt);
     TPQ_LAUNCH_CHECK("scan_finish_exact_kernel");
     return TPQ_OK;
   };
@@ -187,12 +192,14 @@ int TPQ_CAT(dispatch_dump_, TPQ_PACKED_M)(const ScanArgs& a, int RL, int R, int 
 }
 
 // the finish kernel on its own (the cell-major form, scan_cells.hip): a query's lists arrive as `chunks` (8 or 16) lists
-// of one chunk of 64 keys each; R = registers of the exact list (dump_finish_regs)
-int TPQ_CAT(dispatch_finish_, TPQ_PACKED_M)(const ScanArgs& a, int chunks, int R, hipStream_t st) {
+// of one chunk of 64 keys each; R = registers of the exact list (dump_finish_regs); the first seed_chunks of them hold
+// exact values, cnt[q] entries follow (launch_finish)
+int TPQ_CAT(dispatch_finish_, TPQ_PACKED_M)(const ScanArgs& a, int chunks, int R, int seed_chunks, const int* cnt,
+                                            hipStream_t st) {
   if constexpr (dump_built(TPQ_PACKED_M, kDumpSel16)) {
-    if (R <= 2) return launch_finish<2, TPQ_PACKED_M>(a, chunks, 1, st);
-    if (R == 4) return launch_finish<4, TPQ_PACKED_M>(a, chunks, 1, st);
-    if (R == 8) return launch_finish<8, TPQ_PACKED_M>(a, chunks, 1, st);
+    if (R <= 2) return launch_finish<2, TPQ_PACKED_M>(a, chunks, 1, st, seed_chunks, cnt);
+    if (R == 4) return launch_finish<4, TPQ_PACKED_M>(a, chunks, 1, st, seed_chunks, cnt);
+    if (R == 8) return launch_finish<8, TPQ_PACKED_M>(a, chunks, 1, st, seed_chunks, cnt);
   }
   set_error("scan_packed (finish): no instantiation for %d list registers at m = %d", R, TPQ_PACKED_M);
   return TPQ_ERR_UNSUPPORTED;
