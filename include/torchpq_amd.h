@@ -260,6 +260,24 @@ int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* query, const fl
                               int32_t* out_count, uint32_t* out_keys, uint32_t* out_addr, float* out_delta,
                               int32_t* out_flags, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 float tpq_ivfpq_cell_fold_threshold(float threshold, float q2);
+/* The threshold form of the cell-major form: steps 1 and 2 above are replaced by a first pass of step 4's kernel over
+ * each query's first probes that keeps only group maxima of its values; the k-th largest maximum M_k bounds the k-th
+ * best value from below, every slot of ALL probes with value >= M_k - 2 delta_q is appended, and step 5 evaluates the
+ * lists.  No query-major pass, no seeds; same results, bit for bit.
+ * tpq_ivfpq_scan_cell_threshold (arguments of tpq_ivfpq_scan_cell_major): 1 when tpq_ivfpq_search_fused_cells takes this
+ * form -- tpq_ivfpq_scan_cell_norms is 1, the form's arrays fit the workspace behind the norms, there are more probes
+ * than the first pass covers, slots_hint / max_nprobe >= 512 and the maxima expected of the first pass are at least 2 k.
+ * tpq_ivfpq_scan_use_cell_threshold(on): the A/B switch of the two forms, process-wide, read on the host during a call;
+ * 0 keeps every later call to steps 1 and 2, whatever tpq_ivfpq_scan_cell_threshold says.  Returns the previous setting.
+ * tpq_ivfpq_scan_cell_threshold_probes(): the probes per query the first pass covers.
+ * Diagnostics: the first pass fills a query's list of maxima from the END of its key area downwards, and the count of
+ * them is kept behind the form's arrays, so both can be read from the workspace after the call
+ * (IVFPQTopkHip.last_cell_threshold_state). */
+int tpq_ivfpq_scan_cell_threshold(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
+                                  int has_lut, int has_packed, int has_tickets, int residual, int n_cells,
+                                  int64_t n_slots, size_t workspace_bytes);
+int tpq_ivfpq_scan_use_cell_threshold(int on);
+int tpq_ivfpq_scan_cell_threshold_probes(void);
 
 /* ---------------------------------------------------------------------------
  * SURVEY 8(f)-3  residual-PQ list scan (pq_use_residual=True)

@@ -54,6 +54,9 @@ SIGNATURES = {
     "tpq_ivfpq_cell_candidates": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tpq_ivfpq_cell_fold_threshold": (_f, [_f, _f]),
+    "tpq_ivfpq_scan_cell_threshold": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
+    "tpq_ivfpq_scan_use_cell_threshold": (_i, [_i]),
+    "tpq_ivfpq_scan_cell_threshold_probes": (_i, []),
     "tpq_ivfpq_scan_topk_residual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "tpq_residual_part1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -9,7 +9,7 @@
 # scan_args.h only, so the other scan headers -- the packed ones above all -- leave it alone; scan_filtered.hip (the filtered
 # top-k scan) takes scan_ref.h for the split merge and, through it, the same three;
 # scan_order.hip (the large batches' dispatch order) takes scan_order.h alone, which scan.hip shares; scan_cells.hip (the
-# cell-major candidates of the m = 64 large-batch route) takes scan_cells.h, which scan.hip shares, mfma_util.h and wave_topk.h; fp16_cascade.h
+# cell-major candidates of the m = 64 large-batch route) takes scan_cells.h, which scan.hip shares, mfma_util.h, wave_topk.h and scan_fk.h (the k-th key search, shared with scan_finish.h); fp16_cascade.h
 # rebuilds the four cascade units (cascade_core, assign_cascade, probe_sims, lloyd) and assign_fast; row_select.h (the
 # row select's device code) rebuilds select, coarse_probe and probe_sims; probe_fast.h rebuilds coarse_probe and
 # probe_sims; mfma_util.h (the MFMA units' shared device helpers) rebuilds the cascade units, assign_fast, coarse_probe,

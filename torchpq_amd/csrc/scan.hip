@@ -459,7 +459,8 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   c.codes = a.codes; c.query = a.query; c.codebook = a.codebook; c.is_empty = a.is_empty;
   c.cell_start = a.cell_start; c.cell_size = a.cell_size; c.n_probe_list = a.n_probe_list; c.cells = cm.cells;
   c.n_slots = a.n_slots; c.nq = nq; c.max_nprobe = a.max_nprobe; c.n_cells = cm.n_cells; c.ds = a.ds;
-  c.euclid = a.euclid; c.p0 = kCellP0; c.k = a.k; c.chunks = chunks; c.epoch = a.epoch; c.rel = cell_delta_rel(a.ds);
+  c.euclid = a.euclid; c.p0 = kCellP0; c.p_hi = a.max_nprobe; c.k = a.k; c.chunks = chunks; c.epoch = a.epoch;
+  c.rel = cell_delta_rel(a.ds);
   c.seed_vals = a.out_vals; c.seed_addr = a.out_addr;
   c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
   c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
@@ -471,6 +472,53 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   //    cut at F_k - 2 delta_q, the survivors among the candidates evaluated exactly; those among the seeds keep the
   //    values stage 1 gave them (scan_finish.h)
   return u.finish(a, chunks, p.Rf, (a.k + 63) / 64, c.cnt, st);
+}
+
+// The threshold form of the cell-major form (scan_cells.hip: `The threshold from group maxima`): no query-major pass and
+// no seeds -- the threshold comes from the candidate kernel's own accumulators over each query's first kCellThrProbes
+// probes.  Taken when
+//  * the cell-major form and its per-call slot norms are taken (pass A reads the norm array);
+//  * the form's arrays (cell_thr_bytes) fit behind the lists, the extras and the norms;
+//  * there are more than kCellThrProbes probes;
+//  * the mean probed cell is long: slots_hint / max_nprobe >= kCellThrMinCell;
+//  * the maxima expected of the first kCellThrProbes cells outnumber k twice -- fewer than k maxima give no threshold at
+//    all (-inf admits everything), and a threshold from just over k of them is loose.
+// Pure host arithmetic: tpq_ivfpq_scan_cell_threshold answers without a GPU.
+static bool cell_threshold_form(const ScanArgs& a, int chunks, int n_cells, size_t workspace_bytes) {
+  if (!cell_major_norms(a, chunks, n_cells, workspace_bytes) || a.max_nprobe <= kCellThrProbes) return false;
+  const size_t need = ws_bytes_for(a.nq, 1, chunks) + cell_extra_bytes(a.nq, a.max_nprobe, n_cells, kCellP0) +
+                      cell_norm_bytes(a.n_slots) + cell_thr_bytes(a.nq, a.max_nprobe, n_cells);
+  const int64_t mean_cell = a.slots_hint / a.max_nprobe;
+  return workspace_bytes >= need && mean_cell >= kCellThrMinCell &&
+         (int64_t)kCellThrProbes * mean_cell / kCellThrGroup >= 2 * (int64_t)a.k;
+}
+
+// the threshold form's stages (the flag-gated redo over ALL probes is the caller's next line)
+static int run_cell_threshold(ScanArgs& a, const ScanPlan& p, const PackedUnit& u, const CellMajor& cm, int chunks,
+                              void* workspace, hipStream_t st) {
+  const int nq = a.nq;
+  a.n_split = 1;
+  a.unsplit = 0;
+  fill_ws(a, workspace, 1, chunks);
+  CellArgs c{};
+  c.codes = a.codes; c.query = a.query; c.codebook = a.codebook; c.is_empty = a.is_empty;
+  c.cell_start = a.cell_start; c.cell_size = a.cell_size; c.n_probe_list = a.n_probe_list; c.cells = cm.cells;
+  c.n_slots = a.n_slots; c.nq = nq; c.max_nprobe = a.max_nprobe; c.n_cells = cm.n_cells; c.ds = a.ds;
+  c.euclid = a.euclid; c.p0 = 0; c.p_hi = a.max_nprobe; c.k = 0; c.thr_k = a.k; c.chunks = chunks; c.epoch = a.epoch;
+  c.rel = cell_delta_rel(a.ds);
+  c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
+  c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
+  // the extras where the seeded form has them (its pairs array, max_nprobe - kCellP0 per query, stays unused: pass B's
+  // pairs are the form's own), the norms behind them, the form's arrays behind the norms (the gate: all of it fits)
+  char* at = reinterpret_cast<char*>(workspace) + ws_bytes_for(nq, 1, chunks);
+  const size_t head = cell_extra_bytes(nq, a.max_nprobe, cm.n_cells, kCellP0) + cell_norm_bytes(a.n_slots);
+  cell_fill_extras(c, at, head, kCellP0);
+  CellThrArrays t{};
+  cell_fill_thr(t, at + head, nq, a.max_nprobe, cm.n_cells);
+  int rc = launch_cell_threshold(c, t, st);
+  if (rc) return rc;
+  // stage 5 without seed chunks: every survivor of the cut is evaluated by the finish kernel's ascending-j chain
+  return u.finish(a, chunks, p.Rf, 0, c.cnt, st);
 }
 
 extern "C" int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
@@ -495,6 +543,24 @@ extern "C" int tpq_ivfpq_scan_cell_norms(int nq, int k, int n_split, int m, int 
   const int chunks = cell_major_chunks(a, p, residual != 0, n_cells, workspace_bytes);
   return cell_major_norms(a, chunks, n_cells, workspace_bytes) ? 1 : 0;
 }
+
+extern "C" int tpq_ivfpq_scan_cell_threshold(int nq, int k, int n_split, int m, int ds, int max_nprobe,
+                                             int64_t slots_hint, int has_lut, int has_packed, int has_tickets,
+                                             int residual, int n_cells, int64_t n_slots, size_t workspace_bytes) {
+  if (nq <= 0 || k < 1 || k > 1024 || m < 4 || m % 4 != 0 || n_split < 1 || max_nprobe < 1) return -1;
+  if (!has_packed) return 0;
+  ScanArgs a = route_query_args(nq, k, n_split, m, ds, max_nprobe, slots_hint, has_lut, has_tickets);
+  a.n_slots = n_slots;
+  const ScanPlan p = plan_scan(a, residual != 0);
+  const int chunks = cell_major_chunks(a, p, residual != 0, n_cells, workspace_bytes);
+  return cell_threshold_form(a, chunks, n_cells, workspace_bytes) ? 1 : 0;
+}
+
+// the A/B switch of the two forms (index.use_cell_threshold): process-wide, read once per call on the host; 0 keeps
+// every later call to the seeded form.  Returns the previous setting.  tpq_ivfpq_scan_cell_threshold does not look at it.
+static std::atomic<int> g_cell_threshold{1};
+extern "C" int tpq_ivfpq_scan_use_cell_threshold(int on) { return g_cell_threshold.exchange(on ? 1 : 0); }
+extern "C" int tpq_ivfpq_scan_cell_threshold_probes(void) { return kCellThrProbes; }
 
 static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_t workspace_bytes,
                       tpq_stream_t stream, const CellMajor* cm = nullptr) {
@@ -540,7 +606,9 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
     case TPQ_SCAN_ROUTE_DUMP_SEL16:
     case TPQ_SCAN_ROUTE_DUMP_SEL16_W8: {
       if (const int chunks = cm ? cell_major_chunks(a, p, ra != nullptr, cm->n_cells, workspace ? workspace_bytes : 0) : 0) {
-        rc = run_cell_major(a, p, u, *cm, chunks, workspace, workspace_bytes, st);
+        rc = g_cell_threshold.load() && cell_threshold_form(a, chunks, cm->n_cells, workspace_bytes)
+                 ? run_cell_threshold(a, p, u, *cm, chunks, workspace, st)
+                 : run_cell_major(a, p, u, *cm, chunks, workspace, workspace_bytes, st);
         break;
       }
       plan_dump_dispatch(p, nq, dump_slots(u, p.mode), workspace ? workspace_bytes : 0);

@@ -9,6 +9,21 @@ namespace tpq {
 #define TPQ_CELL_P0 4  // (variant builds: the A/B of 3, 4 and 6)
 #endif
 constexpr int kCellP0 = TPQ_CELL_P0;
+// The threshold form (scan_cells.hip: `The threshold from group maxima`): no query-major pass at all.  The candidate
+// kernel's pass A runs over each query's first kCellThrProbes probes and keeps, per lane and tile, the maximum of every
+// kCellThrGroup of its 16 rows; the k-th largest of a query's maxima bounds its k-th best value from below.
+#ifndef TPQ_CELL_THR_PROBES
+#define TPQ_CELL_THR_PROBES 6  // (variant builds: the A/B of 4, 6 and 8 -- profiles/cell_threshold_bench.json)
+#endif
+#ifndef TPQ_CELL_THR_GROUP
+#define TPQ_CELL_THR_GROUP 16  // (variant builds: the A/B of 8 and 16)
+#endif
+constexpr int kCellThrProbes = TPQ_CELL_THR_PROBES;
+constexpr int kCellThrGroup = TPQ_CELL_THR_GROUP;
+static_assert(kCellThrGroup == 8 || kCellThrGroup == 16, "a group is half or all of a lane's 16 rows of a tile");
+// the threshold form is taken from this mean length of a probed cell on: the maxima of short cells are few, and the
+// existing form's tests pin its behaviour at mean cells of 50 - 381 slots
+constexpr int kCellThrMinCell = 512;
 // the form applies from this many re-reads of the mean code byte on (nq x slots_hint / n_slots)
 constexpr int kCellMinRereads = 96;
 constexpr int kCellQSplit = 256;  // halfs per query of the split copy: [hi, lo][128 components]
@@ -34,8 +49,11 @@ struct CellArgs {
   const int64_t* cells;          // [nq][max_nprobe]
   int64_t n_slots;
   int nq, max_nprobe, n_cells, ds, euclid;
-  int p0;                        // the pairs listed are (q, p), p0 <= p < n_probe_list[q]
+  int p0;                        // the pairs listed are (q, p), p0 <= p < min(n_probe_list[q], p_hi)
+  int p_hi;                      // (max_nprobe: every probe from p0 on)
   int k;                         // seeds per query (0: none)
+  int thr_k;                     // the threshold form: the call's k (k == 0 there; 0 everywhere else)
+  int work;                      // the candidate kernel's block counter: params + 8 + work (0 or 1)
   int chunks;                    // capacity of a query's lists in chunks of 64 keys, seed chunks included
   int epoch;                     // flags[q] == epoch: the query takes no part / overflowed
   float rel;                     // delta_q = rel (|q| + |x|max)^2
@@ -62,6 +80,17 @@ struct CellArgs {
   _Float16* qsplit;              // [nq][2][128] the fp16 pieces of s_q q (hi, lo)
   // behind the extras, when the workspace has the room (cell_norm_bytes); nullptr: the candidate kernel's own chain
   float* norm;                   // [n_slots] |x'|^2 / s_x^2 of every slot of a listed cell, by address (NaN: tombstone)
+  // the threshold form (behind the norms, cell_thr_bytes): the second inversion's histogram, which cell_prep_kernel
+  // zeroes with the first (nullptr: none), and where cell_kth_kernel leaves the number of maxima pass A reserved
+  // (nullptr: nowhere)
+  int* hist2;                    // [n_cells]
+  int* n_max;                    // [nq]
+};
+// the arrays of the threshold form: pass B's pairs (all probes: the extras hold max_nprobe - kCellP0 per query), then
+// pass A's inversion -- hist, cell_off, blk_off, cell_st, cell_sz, pairs --, then the maxima counts [nq]
+struct CellThrArrays {
+  int* pairs_b;
+  int *hist, *cell_off, *blk_off, *cell_st, *cell_sz, *pairs, *n_max;
 };
 
 inline size_t cell_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -73,6 +102,12 @@ inline size_t cell_extra_bytes(int nq, int max_nprobe, int n_cells, int p0) {
 }
 // the slot norms of a call (cell_norm_kernel): one fp32 per slot address
 inline size_t cell_norm_bytes(int64_t n_slots) { return cell_align((size_t)(n_slots > 0 ? n_slots : 0) * 4); }
+// the threshold form's arrays (CellThrArrays), behind the extras and the norms
+inline size_t cell_thr_bytes(int nq, int max_nprobe, int n_cells) {
+  const int t = max_nprobe < kCellThrProbes ? max_nprobe : kCellThrProbes;
+  return cell_align((size_t)nq * max_nprobe * 4) + 3 * cell_align((size_t)n_cells * 4) +
+         2 * cell_align(((size_t)n_cells + 1) * 4) + cell_align((size_t)nq * t * 4) + cell_align((size_t)nq * 4);
+}
 // The candidate kernel's folded threshold.  A row is admitted when fl(a - q2) >= thr (a = fl(2 dot - |x|^2), q2 = |q|^2
 // finite); rounding is monotone, so the rows admitted are those with a >= thr2 for ONE float thr2 = the smallest a that
 // passes, and the subtraction leaves the tile loop.  -inf stays -inf, +inf stays +inf, NaN stays NaN (nothing passes).
@@ -116,11 +151,18 @@ __host__ __device__ inline float cell_fold_threshold(float thr, float q2) {
 }
 
 // points the extras of `a` into `at` (cell_extra_bytes of it); `room` bytes are the caller's from `at` on: the slot
-// norms follow the extras when they fit, else a.norm = nullptr
-void cell_fill_extras(CellArgs& a, void* at, size_t room);
+// norms follow the extras when they fit, else a.norm = nullptr.  layout_p0 >= 0: the extras are laid out as for that first
+// probe whatever a.p0 is (the threshold form keeps the seeded form's layout, whose pairs array it leaves unused)
+void cell_fill_extras(CellArgs& a, void* at, size_t room, int layout_p0 = -1);
 // delta_q / (|q| + |x|max)^2 (derivation: scan_cells.hip)
 float cell_delta_rel(int ds);
 // stages 2-4 on `st`: seed (or the caller's thresholds), inversion, candidates
 int launch_cell_candidates(const CellArgs& a, hipStream_t st);
+// points `t` into `at` (cell_thr_bytes of it)
+void cell_fill_thr(CellThrArrays& t, void* at, int nq, int max_nprobe, int n_cells);
+// the threshold form on `st`, a.k == 0, a.thr_k = the call's k, a.norm set, a.p0 == 0: per-query part, inversion of all
+// probes and slot norms, inversion of the first kCellThrProbes, pass A (group maxima into a.keys), cell_kth_kernel (thr,
+// zero counts) and the candidates of all probes
+int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t st);
 
 }  // namespace tpq

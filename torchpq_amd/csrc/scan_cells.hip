@@ -56,6 +56,9 @@
 //                        update per flush -- at the end of the block, or when a segment is full (a returning atomic
 //                        per row was four or five dependent round trips per tile, one per lane and tile still one).
 //                        A probe listed twice in a row is skipped as the scan skips it (fetch_probes, scan_shared.h).
+//                        <.., MAXIMA>: pass A of the threshold form -- group maxima instead of admitted rows.
+//   cell_kth_kernel      the threshold form, one wave per query: the k-th largest of pass A's maxima -> thr[q]; zeroes
+//                        cnt[q] (`The threshold from group maxima`, below).
 //                        (Measured on the headline batch, 10 000 queries x 28 listed probes: sub-vectors gathered from
 //                        the fp32 codebook in global memory into a staged 128-slot tile, 2.66 ms; this form with the
 //                        queries read from [d][nq] per block, 1.06 ms; with the split copy, 0.91 ms; with the norms of a
@@ -122,10 +125,51 @@
 // 30 us, tools/experiments/cell_planes.patch --; the gathers of the next k-step issued ahead of a k-step's products,
 // 335 us against 340 and one register over the budget without the slot norms; twelve waves per workgroup, which now fit
 // 168 registers without a spill: 321-331 us, 0.65 % of the step, under five times the step's run-to-run spread.)
+//
+// The threshold from group maxima (the threshold form: launch_cell_threshold; the gate: scan.hip, cell_threshold_form).
+// The seeded form pays the query-major scan for ONE number per query -- tau_q, a lower bound on the k-th best value --
+// and for k seeds.  A bound needs no selection.  Pass A is cell_cand_kernel<.., MAXIMA> over the pairs (q, p), p < T =
+// kCellThrProbes: the same staging, tile loop, loads and MFMAs; lane (query column, half) holds 16 rows of its query's
+// column per tile and keeps, per group of G = kCellThrGroup of them, the MAXIMUM of their tested values.
+//   The tested value against the stored value.  Of a row r the lane forms a_r = fma(S_r, um, -|x_r|^2) (euclidean; inner
+//   product: fma(S_r, u, z_r)) -- the operand of the admission test, see `The admission test`; t_r = fl(a_r - |q|^2)
+//   (inner product: a_r) is the TESTED value, the one that statement's containment is argued for: |t_r - exact_r| <=
+//   delta_q for every live row, and t_r is NaN for a row past the size or a tombstone.  What is stored for a group g is
+//   f2key(fl(max_{r in g} a_r - |q|^2)): rounding is monotone, so this is max_{r in g} t_r -- the tested value of the
+//   group's best row, not a new quantity with an error of its own.  The maximum is taken with fmaxf from -inf: a NaN
+//   never wins, and -inf comes out exactly when the group has no live row (a_r is finite for a live row: |S| < 2^36,
+//   norms <= 3e38 / 4); such a group stores the key image 0, which no search over key images counts.
+//   Why M_k bounds.  Groups are disjoint sets of rows of the multiset the reference scans (a probe listed twice, not in
+//   a row, is scanned twice by the reference too, and its rows are two entries of that multiset in both).  Let M_k be
+//   the k-th largest stored maximum of a query.  k groups have a maximum >= M_k, so k DISTINCT entries have t >= M_k,
+//   hence exact >= M_k - delta_q: the exact k-th best value E_k over ALL listed probes is >= M_k - delta_q.
+//   Why M_k - 2 delta_q admits every member, ties included.  Pass B admits a row when t >= thr = fl(M_k - 2 delta_q)
+//   (tested as a >= cell_fold_threshold(thr, |q|^2)).  A member of the exact top-k -- any entry with exact >= E_k, so
+//   every entry tied at the k-th place -- has t >= exact - delta_q >= E_k - delta_q >= M_k - 2 delta_q.  delta_q is
+//   1.25 x the sum of the error terms, so the two uses of it leave 0.4 delta_q >= 2^-19 B^2 of slack, against one more
+//   rounding of a number below 4 B^2 in thr (2^-22 B^2, the line `the two subtractions`); 2 delta_q is ws_delta, exact.
+//   Stage 5 then works as in the seeded form, without seed chunks: F_k over the candidates' stored keys, the cut at F_k -
+//   2 delta_q, all survivors evaluated exactly by the finish kernel's ascending-j chain -- the same bits.
+//   Why dropped maxima, repeated probes and -inf are harmless.  A subset of the maxima has a k-th largest element that is
+//   no larger: M_k only moves down, the bound stays a bound and more is admitted.  So entries at or beyond the capacity
+//   of the query's key area are simply not written (the lane reserves its tiles x 16 / G entries with one returning
+//   atomic before the tile loop, and cnt[q] counts them all; cell_kth_kernel reads min(cnt, capacity) of them -- every one
+//   of those positions was written, since a lane stores to each position it reserved below the capacity).  Repeated
+//   probes: above.  Fewer than k maxima: M_k = -inf, thr = -inf, pass B admits every live row; what does not fit flags the
+//   query for the exact kernel, as -inf does in the seeded form.
+//   The list is the query's own key area (chunks x 64 entries of ws_vals), unused until pass B, filled from its END
+//   downwards: entry e of the list is position capacity - 1 - e.  Pass B appends from position 0 upwards, so what it does
+//   not reach of the maxima is still there after the call, with cell_kth_kernel's count of them (n_max) -- which is what
+//   the diagnostics and the float64 test of pass A read from a kept workspace.  Pass A writes KEYS only;
+//   the seed kernel has written the pad index into every entry of the index area, pass B writes key and index of each
+//   entry it appends from position 0 on, and the finish kernel zeroes the key of every entry whose index is pad: stage 5
+//   never sees a maximum.  The two candidate launches draw their blocks from two counters (params + 8, + 9).
+// (Measured on the headline batch: profiles/cell_threshold_bench.json.)
 #include <cmath>
 
 #include "mfma_util.h"
 #include "scan_cells.h"
+#include "scan_fk.h"
 #include "wave_topk.h"
 
 namespace tpq {
@@ -137,16 +181,17 @@ float cell_delta_rel(int ds) {
   return (float)(1.25 * sum * (1.0 + 1.0 / 1024));  // (+ 2^-10: B^2 and the product are evaluated in fp32)
 }
 
-void cell_fill_extras(CellArgs& a, void* at, size_t room) {
+void cell_fill_extras(CellArgs& a, void* at, size_t room, int layout_p0) {
   char* p = reinterpret_cast<char*>(at);
-  const size_t extras = cell_extra_bytes(a.nq, a.max_nprobe, a.n_cells, a.p0);
+  const int p0 = layout_p0 >= 0 ? layout_p0 : a.p0;
+  const size_t extras = cell_extra_bytes(a.nq, a.max_nprobe, a.n_cells, p0);
   a.norm = room >= extras && room - extras >= cell_norm_bytes(a.n_slots) ? reinterpret_cast<float*>(p + extras) : nullptr;
   auto take = [&](size_t bytes) {
     char* r = p;
     p += cell_align(bytes);
     return r;
   };
-  const int np = a.max_nprobe > a.p0 ? a.max_nprobe - a.p0 : 0;
+  const int np = a.max_nprobe > p0 ? a.max_nprobe - p0 : 0;
   a.params = reinterpret_cast<float*>(take(256));
   a.thr = reinterpret_cast<float*>(take((size_t)a.nq * 4));
   a.qscale = reinterpret_cast<float*>(take((size_t)a.nq * 4));
@@ -175,6 +220,8 @@ __global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) maxbits_s = 0u;
   for (int i = tid; i < a.n_cells; i += 1024) a.hist[i] = 0;
+  if (a.hist2)
+    for (int i = tid; i < a.n_cells; i += 1024) a.hist2[i] = 0;
   __syncthreads();
   unsigned mb = 0u;
   for (int j = wave; j < 64; j += 16) {
@@ -206,18 +253,20 @@ __global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
     a.params[1] = x2;
     a.params[2] = ok ? 1.f : 0.f;
     a.params[3] = ok ? pow2i(kCellScaleExp - e) : 0.f;  // s_x
-    reinterpret_cast<int*>(a.params)[8] = 0;            // cell_cand_kernel's block counter
+    reinterpret_cast<int*>(a.params)[8] = 0;            // cell_cand_kernel's block counters: CellArgs::work
+    reinterpret_cast<int*>(a.params)[9] = 0;
   }
 }
 
-// the listed probes of query q: p0 <= p < n_probe_list[q] (clamped), the cell not empty and not the previous probe's again
+// the listed probes of query q: p0 <= p < min(n_probe_list[q], p_hi) (clamped), the cell not empty and not the previous
+// probe's again
 struct ListedProbe {
   bool listed;
   int cell;
 };
 __device__ __forceinline__ int cell_n_probe(const CellArgs& a, int q) {
   const int n = (int)a.n_probe_list[q];
-  return n < 0 ? 0 : (n > a.max_nprobe ? a.max_nprobe : n);
+  return n < 0 ? 0 : (n > a.p_hi ? a.p_hi : n);
 }
 __device__ __forceinline__ ListedProbe listed_probe(const CellArgs& a, int q, int p) {
   const int64_t o = (int64_t)q * a.max_nprobe + p;
@@ -250,7 +299,8 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
     bad_cell = bad_cell || c < 0 || c >= (int64_t)a.n_cells;
   }
   bad_cell = __ballot(bad_cell) != 0ull;
-  const float tau = a.k > 0 ? a.seed_vals[(int64_t)q * a.k + a.k - 1] : a.thr_in[q];
+  // (the threshold form: no threshold yet -- cell_kth_kernel writes thr[q] of every query that is not flagged here)
+  const float tau = a.k > 0 ? a.seed_vals[(int64_t)q * a.k + a.k - 1] : (a.thr_k > 0 ? 0.f : a.thr_in[q]);
   const int eq = exp_of_bits(mb);
   const bool flagged = a.k > 0 && a.flags[q] == a.epoch;
   const bool scalable = a.params[2] != 0.f && mb != 0u && mb <= kMaxFiniteBits && eq >= -kCellMaxExp &&
@@ -269,7 +319,7 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
   const float delta = a.rel * (B * B);
   if (lane == 0) {
     // the candidate kernel's threshold: a row passes when fl(a - |q|^2) >= tau - delta, tested as a >= the fold
-    a.thr[q] = a.euclid ? cell_fold_threshold(tau - delta, q2) : tau - delta;
+    if (a.thr_k == 0) a.thr[q] = a.euclid ? cell_fold_threshold(tau - delta, q2) : tau - delta;
     a.ws_delta[q] = 2.f * delta;
     a.qscale[q] = pow2i(kCellScaleExp - eq);
     a.qnorm[q] = q2;
@@ -312,7 +362,7 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
 constexpr int kCellSliceThreads = 1024;
 template <class F>
 __device__ __forceinline__ void for_slice_pairs(const CellArgs& a, int q0, F&& f) {
-  const int np = a.max_nprobe - a.p0;  // (> 0: the launch)
+  const int np = a.p_hi - a.p0;  // (> 0: the launch)
   const int nqs = a.nq - q0 < kCellSlice ? a.nq - q0 : kCellSlice;
   for (int i = (int)threadIdx.x; i < nqs * np; i += kCellSliceThreads) {
     const int dq = i / np;
@@ -538,8 +588,14 @@ __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
 // lane's segment cannot take (the row's mask AND one ballot, scalar): a flush is ONE counter update per lane that holds
 // entries, followed by the capacity rule as before (entries at or beyond cap are not written, the query is flagged, cnt
 // counts them all).  EUCLID: the metric, so that the tile loop selects nothing on it (the header: `The admission test`).
-template <int DS, bool NORMS, bool EUCLID>
+// MAXIMA: pass A of the threshold form (the header: `The threshold from group maxima`).  Nothing is tested or staged:
+// the lane reserves tiles x 16 / kCellThrGroup entries of its query's key area with ONE returning atomic before the tile
+// loop and stores, per tile, the key image of the largest tested value of every group of kCellThrGroup of its 16 rows --
+// 0, which counts for nothing in a search over key images, for a group without a live row.  Entries at or beyond the
+// capacity are dropped.  NORMS only: the form requires the norm array.
+template <int DS, bool NORMS, bool EUCLID, bool MAXIMA = false>
 __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellArgs a) {
+  static_assert(!MAXIMA || NORMS, "pass A reads the slot norms");
   using T = CellBook<DS>;
   constexpr int KS = T::KS;
   constexpr int kDepth = T::kDepth;
@@ -548,7 +604,7 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* x2w = reinterpret_cast<float*>(smem + T::kBook) + wave * 32;
   uint2* stage = reinterpret_cast<uint2*>(smem + T::kBook + T::kNorms) + wave * (64 * kDepth) + lane;  // [entry][lane]
-  int* work = reinterpret_cast<int*>(a.params) + 8;
+  int* work = reinterpret_cast<int*>(a.params) + 8 + a.work;
   const int n_blocks = a.blk_off[a.n_cells];
   const int col = lane & 31, half = lane >> 5;
   const float sx = a.params[3];
@@ -648,6 +704,12 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
       }
       fill = 0;
     };
+    // MAXIMA: the lane's entries of its query's key area, reserved here once; a lane without a query stores nothing
+    int me = (int)cap;
+    unsigned* __restrict__ mkeys = a.keys + (int64_t)q * cap;
+    if constexpr (MAXIMA) {
+      if (qvalid) me = atomicAdd(&a.cnt[q], ((sz + 31) >> 5) * (16 / kCellThrGroup));
+    }
     uint32_t w[8], wn[8];
     unsigned aux = 0u, aux_n = 0u;
     load_tile(0, w, aux);
@@ -716,6 +778,33 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
       // accumulator register 4 g + i holds row 8 g + 4 half + i of the tile: four 16-byte reads bring the 16 norms.
       // A row's compare leaves its 64 lanes' answers in a scalar register pair: whether anybody admitted the row is
       // scalar work, and a row nobody admitted costs no vector instruction beyond its fma and compare
+      if constexpr (MAXIMA) {
+        // the tested values of the lane's 16 rows, reduced per group: fmaxf takes the other operand over a NaN (a row
+        // past the size, a tombstone), so a group's maximum is -inf exactly when none of its rows is live
+        float gm[16 / kCellThrGroup];
+#pragma unroll
+        for (int g = 0; g < 16 / kCellThrGroup; ++g) gm[g] = -INFINITY;
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const f32x4 x4 = *reinterpret_cast<const f32x4*>(x2w + 8 * gq + 4 * half);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = 4 * gq + i;
+            gm[r / kCellThrGroup] = fmaxf(gm[r / kCellThrGroup], fmaf(acc[r], um, -x4[i]));
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < 16 / kCellThrGroup; ++g) {
+          const unsigned key = gm[g] == -INFINITY ? 0u : f2key(EUCLID ? gm[g] - q2 : gm[g]);
+          if (me < (int)cap) mkeys[(int)cap - 1 - me] = key;  // (from the end of the area downwards: the header)
+          ++me;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = wn[i];
+        aux = aux_n;
+        continue;
+      }
       float xr[16];
       bool adm[16];
       unsigned long long any[16];  // (the compare's scalar register pair)
@@ -760,21 +849,62 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
   }
 }
 
-// the metric is the kernel's: no select on it in the tile loop
-template <int DS, bool NORMS>
-static int launch_cand(const CellArgs& a, dim3 grid, dim3 wg, hipStream_t st) {
-  return a.euclid ? launch_with_lds(cell_cand_kernel<DS, NORMS, true>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a)
-                  : launch_with_lds(cell_cand_kernel<DS, NORMS, false>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a);
+// The threshold form's step between its two passes, one wave per query: M_k, the k-th largest of the min(cnt, capacity)
+// group maxima pass A left in the query's key area -- the finish kernel's search over key images (scan_fk.h), the chunks
+// in registers; fewer than k maxima: -inf --, then thr[q] = M_k - 2 delta_q, folded over |q|^2 when euclidean, where the
+// candidate kernel reads it.  cnt[q] is zeroed for pass B.  Pass A wrote keys only: the pad indices and the eviction
+// words of the seed kernel stand as they were, so nothing else is restored.  A flagged query keeps thr = +inf.
+template <int NCH>
+__global__ __launch_bounds__(256) void cell_kth_kernel(CellArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (q >= a.nq) return;  // (wave-uniform)
+  const int n_all = __builtin_amdgcn_readfirstlane(a.cnt[q]);
+  if (lane == 0) {
+    a.cnt[q] = 0;
+    if (a.n_max) a.n_max[q] = n_all;  // (diagnostics: what pass A reserved)
+  }
+  if (a.flags[q] == a.epoch) return;
+  const int cap = a.chunks * 64;  // (the launch: chunks <= NCH)
+  const int n = n_all < cap ? n_all : cap;
+  const unsigned* __restrict__ keys = a.keys + (int64_t)q * cap;
+  unsigned hi[NCH];
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) hi[t] = t * 64 + lane < n ? keys[cap - 1 - (t * 64 + lane)] : 0u;  // (0: counts for nothing)
+  const unsigned fk = finish_fk_upto<2, NCH>(hi, (n + 63) / 64, a.thr_k);
+  if (lane == 0) {
+    const float t = (fk ? key2f(fk) : -INFINITY) - a.ws_delta[q];
+    a.thr[q] = a.euclid ? cell_fold_threshold(t, a.qnorm[q]) : t;
+  }
 }
 
-int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
-  if (a.nq <= 0) return TPQ_OK;
+// the metric is the kernel's: no select on it in the tile loop
+template <int DS, bool NORMS, bool MAXIMA = false>
+static int launch_cand(const CellArgs& a, dim3 grid, dim3 wg, hipStream_t st) {
+  return a.euclid ? launch_with_lds(cell_cand_kernel<DS, NORMS, true, MAXIMA>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a)
+                  : launch_with_lds(cell_cand_kernel<DS, NORMS, false, MAXIMA>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a);
+}
+
+static int cell_cus() {
+  int dev = 0, n_cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
+    n_cus = 256;
+  return n_cus;
+}
+
+static int launch_cell_head(const CellArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(cell_prep_kernel, dim3(1), dim3(1024), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_prep_kernel");
-  const dim3 per_query((unsigned)((a.nq + 3) / 4));
-  hipLaunchKernelGGL(cell_seed_kernel, per_query, dim3(256), 0, st, a);
+  hipLaunchKernelGGL(cell_seed_kernel, dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_seed_kernel");
-  // the inversion: a workgroup per slice of kCellSlice queries over an LDS histogram, while one fits
+  return TPQ_OK;
+}
+
+// the inversion of the pairs (q, p), p0 <= p < p_hi, into a's hist / cell_off / blk_off / cell_st / cell_sz / pairs:
+// a workgroup per slice of kCellSlice queries over an LDS histogram, while one fits
+static int launch_cell_inversion(const CellArgs& a, hipStream_t st) {
+  const dim3 per_query((unsigned)((a.nq + 3) / 4));
   const bool lds_hist = a.n_cells <= kCellLdsCells;
   const dim3 per_slice((unsigned)((a.nq + kCellSlice - 1) / kCellSlice)), slice_wg(kCellSliceThreads);
   const size_t hist_lds = (size_t)a.n_cells * sizeof(int);  // (<= 64 KiB: no attribute to raise)
@@ -794,28 +924,94 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(cell_scatter_wide_kernel, per_query, dim3(256), 0, st, a);
     TPQ_LAUNCH_CHECK("cell_scatter_wide_kernel");
   }
-  int dev = 0, n_cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
-    n_cus = 256;
-  // one workgroup of eight waves per CU, fewer when the call cannot list that many (cell, group) blocks: at most one
-  // per listed cell plus one per full group of pairs
-  const int64_t np = (int64_t)a.nq * (a.max_nprobe > a.p0 ? a.max_nprobe - a.p0 : 0);
+  return TPQ_OK;
+}
+
+// the norms of the listed cells, once per call: cells dealt over at most one workgroup per CU
+static int launch_cell_norms(const CellArgs& a, int n_cus, hipStream_t st) {
+  const dim3 norm_grid((unsigned)(a.n_cells < n_cus ? a.n_cells : n_cus)), wg(512);
+  return a.ds == 1 ? launch_with_lds(cell_norm_kernel<1>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 4, st, a)
+                   : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
+}
+
+// one workgroup of eight waves per CU, fewer when the call cannot list that many (cell, group) blocks: at most one
+// per listed cell plus one per full group of pairs; 0: nothing can be listed
+static unsigned cell_cand_grid(const CellArgs& a, int n_cus) {
+  const int64_t np = (int64_t)a.nq * (a.p_hi > a.p0 ? a.p_hi - a.p0 : 0);
   int64_t blocks = (int64_t)a.n_cells + np / kCellGroup;
   if (blocks > np) blocks = np;
-  if (blocks < 1) return TPQ_OK;
+  if (blocks < 1) return 0;
   blocks = (blocks + kCellWaves - 1) / kCellWaves;
-  if (blocks > n_cus) blocks = n_cus;
-  const dim3 grid((unsigned)blocks), wg(512), cand_wg(64 * kCellWaves);
+  return (unsigned)(blocks > n_cus ? n_cus : blocks);
+}
+
+int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
+  if (a.nq <= 0) return TPQ_OK;
+  if (int rc = launch_cell_head(a, st)) return rc;
+  if (a.p_hi <= a.p0) return TPQ_OK;
+  if (int rc = launch_cell_inversion(a, st)) return rc;
+  const int n_cus = cell_cus();
+  const dim3 grid(cell_cand_grid(a, n_cus)), cand_wg(64 * kCellWaves);
   if (a.norm) {
-    // the norms of the listed cells, once per call: cells dealt over at most one workgroup per CU
-    const dim3 norm_grid((unsigned)(a.n_cells < n_cus ? a.n_cells : n_cus));
-    const int rc = a.ds == 1 ? launch_with_lds(cell_norm_kernel<1>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 4, st, a)
-                             : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
-    if (rc) return rc;
+    if (int rc = launch_cell_norms(a, n_cus, st)) return rc;
     return a.ds == 1 ? launch_cand<1, true>(a, grid, cand_wg, st) : launch_cand<2, true>(a, grid, cand_wg, st);
   }
   return a.ds == 1 ? launch_cand<1, false>(a, grid, cand_wg, st) : launch_cand<2, false>(a, grid, cand_wg, st);
+}
+
+void cell_fill_thr(CellThrArrays& t, void* at, int nq, int max_nprobe, int n_cells) {
+  char* p = reinterpret_cast<char*>(at);
+  auto take = [&](size_t bytes) {
+    int* r = reinterpret_cast<int*>(p);
+    p += cell_align(bytes);
+    return r;
+  };
+  const int tp = max_nprobe < kCellThrProbes ? max_nprobe : kCellThrProbes;
+  t.pairs_b = take((size_t)nq * max_nprobe * 4);
+  t.hist = take((size_t)n_cells * 4);
+  t.cell_off = take(((size_t)n_cells + 1) * 4);
+  t.blk_off = take(((size_t)n_cells + 1) * 4);
+  t.cell_st = take((size_t)n_cells * 4);
+  t.cell_sz = take((size_t)n_cells * 4);
+  t.pairs = take((size_t)nq * tp * 4);
+  t.n_max = take((size_t)nq * 4);
+}
+
+int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t st) {
+  if (a.nq <= 0) return TPQ_OK;
+  TPQ_REQUIRE(a.norm && a.k == 0 && a.thr_k >= 1 && a.p0 == 0 && a.p_hi == a.max_nprobe && a.chunks <= 16,
+              "ivfpq_scan (cell threshold): arguments outside the form");
+  // pass B's view: every probe, its pairs in the form's own array; pass A's: the first kCellThrProbes, its own inversion
+  // arrays and block counter.  The cells A lists are among B's (the same rule over a prefix of the same probes), so
+  // the slot norms of B's cells cover them
+  CellArgs b = a;
+  b.n_max = t.n_max;
+  b.pairs = t.pairs_b;
+  b.hist2 = t.hist;
+  b.work = 0;
+  CellArgs pa = b;
+  pa.p_hi = a.max_nprobe < kCellThrProbes ? a.max_nprobe : kCellThrProbes;
+  pa.hist = t.hist; pa.cell_off = t.cell_off; pa.blk_off = t.blk_off; pa.cell_st = t.cell_st; pa.cell_sz = t.cell_sz;
+  pa.pairs = t.pairs;
+  pa.hist2 = nullptr;
+  pa.work = 1;
+  if (int rc = launch_cell_head(b, st)) return rc;
+  if (int rc = launch_cell_inversion(b, st)) return rc;
+  const int n_cus = cell_cus();
+  if (int rc = launch_cell_norms(b, n_cus, st)) return rc;
+  if (int rc = launch_cell_inversion(pa, st)) return rc;
+  const dim3 cand_wg(64 * kCellWaves);
+  if (int rc = a.ds == 1 ? launch_cand<1, true, true>(pa, dim3(cell_cand_grid(pa, n_cus)), cand_wg, st)
+                         : launch_cand<2, true, true>(pa, dim3(cell_cand_grid(pa, n_cus)), cand_wg, st))
+    return rc;
+  const dim3 per_query((unsigned)((a.nq + 3) / 4));
+  if (a.chunks <= 8)
+    hipLaunchKernelGGL(cell_kth_kernel<8>, per_query, dim3(256), 0, st, b);
+  else
+    hipLaunchKernelGGL(cell_kth_kernel<16>, per_query, dim3(256), 0, st, b);
+  TPQ_LAUNCH_CHECK("cell_kth_kernel");
+  const dim3 grid(cell_cand_grid(b, n_cus));
+  return a.ds == 1 ? launch_cand<1, true>(b, grid, cand_wg, st) : launch_cand<2, true>(b, grid, cand_wg, st);
 }
 
 }  // namespace tpq
@@ -851,7 +1047,7 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
   a.cell_start = cell_start; a.cell_size = cell_size; a.n_probe_list = n_probe_list; a.cells = cells;
   a.n_slots = n_slots; a.nq = nq; a.max_nprobe = max_nprobe; a.n_cells = n_cells; a.ds = ds;
   a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
-  a.p0 = first_probe; a.k = 0; a.chunks = capacity / 64; a.epoch = 1; a.rel = cell_delta_rel(ds);
+  a.p0 = first_probe; a.p_hi = max_nprobe; a.k = 0; a.chunks = capacity / 64; a.epoch = 1; a.rel = cell_delta_rel(ds);
   a.thr_in = threshold;
   a.keys = out_keys; a.idx = out_addr; a.flags = out_flags; a.ws_delta = out_delta;
   cell_fill_extras(a, workspace, workspace_bytes);  // (with room behind the extras: the slot norms, once per call)

@@ -2,6 +2,7 @@
 #pragma once
 #include "scan_shared.h"
 #include "scan_exact.h"
+#include "scan_fk.h"
 #include "scan_packed_kernel.h"
 
 namespace tpq {
@@ -147,30 +148,7 @@ static size_t finish_lds_bytes(int m, int ds, int RM, bool from_lut) {
   return (from_lut ? 0 : (size_t)m * ds * 1024) + (size_t)finish_waves(RM) * RM * 64 * 4 +
          (finish_draws(RM, from_lut) ? 16 : 0);
 }
-// F_k over the first N chunks: the largest key image t with at least k entries >= t (0 while fewer than k entries exist)
-template <int N, int NCH>
-__device__ __forceinline__ unsigned finish_fk(const unsigned (&hi)[NCH], int k) {
-  unsigned fk = 0u;
-#pragma unroll 1
-  for (int bit = 31; bit >= 0; --bit) {
-    const unsigned t = fk | (1u << bit);
-    int n = 0;
-#pragma unroll
-    for (int c = 0; c < N; ++c) n += __popcll(__ballot(hi[c] >= t));
-    fk = n >= k ? t : fk;
-  }
-  return fk;
-}
-// ... over the T chunks in use (wave-uniform; the chunks behind them hold 0 and count for nothing)
-template <int N, int NCH>
-__device__ __forceinline__ unsigned finish_fk_upto(const unsigned (&hi)[NCH], int T, int k) {
-  if constexpr (N >= NCH) {
-    return finish_fk<NCH, NCH>(hi, k);
-  } else {
-    if (T <= N) return finish_fk<N, NCH>(hi, k);
-    return finish_fk_upto<(N < 8 ? N + 2 : N + 4), NCH>(hi, T, k);
-  }
-}
+// (F_k -- finish_fk, finish_fk_upto: scan_fk.h, shared with the cell-major form's cell_kth_kernel)
 template <int RM, int M, int DS, int NCH, bool FROM_LUT = false>
 __global__ __launch_bounds__(finish_waves(RM) * 64) void scan_finish_exact_kernel(ScanArgs a, int nw_scan, int RL,
                                                                                    int seed_chunks,

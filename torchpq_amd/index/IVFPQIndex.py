@@ -30,6 +30,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     # sub-vector length; the workgroup then reads m * ds KiB of L2-resident codebook per query
     fused_lut_max_subvector = 4
     use_cell_major = True
+    use_cell_threshold = True
 
     def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None,
                  expand_step_size=128, expand_mode="double", distance="euclidean",
@@ -65,6 +66,9 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         # hand the probed cells to the fused scan: a large cell-dense batch at m = 64 may then take the cell-major
         # form (csrc/scan_cells.hip; the library's rule decides, IVFPQTopkHip.last_cell_major() tells)
         self.use_cell_major = True
+        # ... and that form may take its threshold from the candidate kernel's group maxima instead of a query-major pass
+        # over the first probes (the library's rule decides, IVFPQTopkHip.last_cell_threshold() tells)
+        self.use_cell_threshold = True
 
         self._init_coarse(n_cells, verbose)
         self.pq_codec = PQCodec(d_vector=d_vector, n_subvectors=n_subvectors, n_clusters=256,
@@ -294,7 +298,8 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         elif fused:
             found = self._ivfpq_topk.topk_fused(
                 packed=self._scan_layout(), query=x, codebook=self.pq_codec.codebook, k=k, distance=self.distance,
-                slots_hint=slots_hint, cells=cells if self.use_cell_major else None, n_cells=self.n_cells, **lists)
+                slots_hint=slots_hint, cells=cells if self.use_cell_major else None, n_cells=self.n_cells,
+                cell_threshold=self.use_cell_threshold, **lists)
         else:
             found = self._ivfpq_topk.topk(
                 packed=self._scan_layout(), precomputed=self.pq_codec.precompute_adc(x), k=k,

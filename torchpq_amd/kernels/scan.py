@@ -45,6 +45,7 @@ class IVFPQTopkHip:
         self.last_workspace_bytes = None
         self._last_device = None
         self._last_cells = None       # (n_cells, n_slots) when the last call handed over its probed cells
+        self._last_withheld = False   # the last call switched the cell-major form's threshold form off
 
     def _tickets(self, n_query, n_split, device):
         """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
@@ -167,6 +168,66 @@ class IVFPQTopkHip:
             return False
         return self.cell_norms(self.last_workspace_bytes, *self._last_cells)
 
+    def cell_threshold(self, workspace_bytes, n_cells, n_slots):
+        """diagnostics: whether such a call takes the cell-major form's threshold form -- no query-major pass, the
+        threshold from group maxima of the candidate kernel's own values (tpq_ivfpq_scan_cell_threshold: the library's
+        own rule, nothing is launched)"""
+        return self._cell_query("tpq_ivfpq_scan_cell_threshold", workspace_bytes, n_cells, n_slots)
+
+    def last_cell_threshold(self):
+        """diagnostics: whether the last topk / topk_fused call ran the cell-major form's threshold form
+        (csrc/scan_cells.hip); False where last_cell_norms() is, and for a call that switched it off
+        (cell_threshold=False)"""
+        if self.last_call is None:
+            return None
+        if self._last_cells is None or self._last_withheld:
+            return False
+        return self.cell_threshold(self.last_workspace_bytes, *self._last_cells)
+
+    def last_cell_threshold_state(self):
+        """diagnostics (synchronises; needs keep_workspace and a last call that ran the threshold form): what the form's
+        first pass and cell_kth_kernel left in the workspace, as a dict of
+          count      i32 [nq]       maxima the first pass reserved room for (beyond the capacity: dropped)
+          maxima     f32 [nq, cap]  entry e of a query's list as a fast value: NaN for a group without a live slot, -inf
+                                    past min(count, cap)
+          survived   bool [nq, cap] the entry is still the first pass's: the list is filled from the END of the query's key
+                                    area downwards, the candidates from its front, which overwrote the others
+          threshold  f32 [nq]       what the candidate pass tested against: M_k - 2 delta_q, folded over |q|^2 when
+                                    euclidean (tpq_ivfpq_cell_fold_threshold); +inf for a flagged query
+          band       f32 [nq]       2 delta_q (-1 for a query redone exactly);  qnorm f32 [nq]: |q|^2
+          candidates i32 [nq]       entries the candidate pass appended (beyond the capacity: counted, not stored)"""
+        assert self.last_workspace is not None and self.last_cell_threshold() is True
+        ws, c = self.last_workspace, self.last_call
+        nq, k, n_probe = c["n_query"], c["k"], c["n_probe"]
+        n_cells, n_slots = self._last_cells
+        align = lambda n: (n + 255) // 256 * 256  # noqa: E731
+        lists = lambda ch: 2 * align(nq * 4) + nq * ch * 512 + align(nq * ch * 4)  # noqa: E731
+        extras = load().tpq_ivfpq_cell_candidates_workspace_bytes(nq, n_probe, n_cells, 4)   # (kCellP0's layout)
+        chunks = next(ch for ch in (16, 8) if (k + 63) // 64 < ch and self.last_workspace_bytes >= lists(ch) + extras)
+        cap = chunks * 64
+
+        def arr(off, n, dtype):
+            return ws[off:off + 4 * n].view(dtype)
+        band = arr(align(nq * 4), nq, torch.float32).clone()
+        keys = arr(2 * align(nq * 4), nq * cap, torch.int32).view(nq, cap)
+        ex = lists(chunks) + 256
+        thr, qnorm, cand = (arr(ex + i * align(nq * 4), nq, t).clone()
+                            for i, t in ((0, torch.float32), (2, torch.float32), (3, torch.int32)))
+        # behind the extras and the norms: pass B's pairs, pass A's inversion, then the counts (csrc/scan_cells.h)
+        t_probes = load().tpq_ivfpq_scan_cell_threshold_probes()
+        off = (lists(chunks) + extras + align(n_slots * 4) + align(nq * n_probe * 4) + 3 * align(n_cells * 4)
+               + 2 * align((n_cells + 1) * 4) + align(nq * min(t_probes, n_probe) * 4))
+        count = arr(off, nq, torch.int32).clone()
+        e = torch.arange(cap, device=ws.device)[None, :]
+        stored = e < count.clamp(max=cap)[:, None]
+        rev = keys.flip(1)                                   # entry e is position cap - 1 - e
+        bits = torch.where(rev < 0, rev & 0x7fffffff, ~rev).view(torch.float32)
+        maxima = torch.where(stored, bits, torch.full_like(bits, -float("inf")))
+        maxima = torch.where(stored & (rev == 0), torch.full_like(bits, float("nan")), maxima)
+        survived = stored & (cap - 1 - e >= cand.clamp(max=cap)[:, None])
+        return dict(count=count, maxima=maxima, survived=survived, threshold=thr, band=band, qnorm=qnorm,
+                    candidates=cand)
+
     def _n_split(self, n_query, device, slots_hint=None):
         """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
         if self.n_cus is None:
@@ -177,7 +238,7 @@ class IVFPQTopkHip:
         return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
 
     def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed,
-              cells=None, n_cells=0, **route):
+              cells=None, n_cells=0, cell_threshold=True, **route):
         """What topk / topk_fused / topk_residual_packed share once their arguments are checked: the outputs, the
         split, the diagnostics, the workspace and the call of `name` -- its own `inputs`, then the arguments every
         scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint; `cells`:
@@ -194,6 +255,7 @@ class IVFPQTopkHip:
         self.last_call = dict(n_query=n_query, k=k, n_split=n_split, n_probe=n_probe, slots_hint=slots_hint,
                               packed=packed is not None, **route)
         self._last_cells = (int(n_cells), int(n_data)) if cells is not None else None
+        self._last_withheld = not cell_threshold
         ws_bytes = lib.tpq_ivfpq_scan_workspace_bytes(n_query, k, n_split, self.m)
         if self.workspace_bytes is not None:
             ws_bytes = int(self.workspace_bytes)
@@ -210,8 +272,13 @@ class IVFPQTopkHip:
                 tail = (ptr(tickets), int(slots_hint or 0))
                 if cells is not None:
                     tail += (ptr(cells), int(n_cells))
-            rc = getattr(lib, name)(*inputs, ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data, n_query,
-                                    n_probe, self.m, k, n_split, ptr(ws), ws_bytes, *tail, stream_ptr(device))
+            # (the switch is the library's, process-wide and read on the host during the call: set for this call alone)
+            before = lib.tpq_ivfpq_scan_use_cell_threshold(1 if cell_threshold else 0)
+            try:
+                rc = getattr(lib, name)(*inputs, ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data, n_query,
+                                        n_probe, self.m, k, n_split, ptr(ws), ws_bytes, *tail, stream_ptr(device))
+            finally:
+                lib.tpq_ivfpq_scan_use_cell_threshold(before)
             if rc != 0 and ticketed:
                 self._drop_tickets(device)
             check(rc, name)
@@ -263,12 +330,13 @@ class IVFPQTopkHip:
 
     def topk_fused(self, data, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
                    n_candidates, distance="euclidean", packed=None, address2id=None, n_split=None,
-                   slots_hint=None, cells=None, n_cells=0):
+                   slots_hint=None, cells=None, n_cells=0, cell_threshold=True):
         """precompute_adc + topk in one pass: the LUT is built inside the scan workgroups
         (query [d, n_query] f32, codebook [m, ds, 256] f32); results identical to
         topk(precomputed=AdcLutHip()(query, codebook)).  `cells` [n_query, max_n_probe] int64 -- the probed cells
         behind cell_start / cell_size, ids in [0, n_cells) -- lets a cell-dense large batch at m = 64 take the
-        cell-major form (tpq_ivfpq_search_fused_cells; `last_cell_major()`): same results."""
+        cell-major form (tpq_ivfpq_search_fused_cells; `last_cell_major()`): same results.  `cell_threshold=False`
+        keeps that form to its seeded variant (tpq_ivfpq_scan_use_cell_threshold; `last_cell_threshold()`)."""
         n_data = data.shape[1]
         n_query, n_probe = cell_start.shape
         m, ds, kk = codebook.shape
@@ -291,7 +359,8 @@ class IVFPQTopkHip:
             cells = cells.contiguous()
             require_gpu(cells)
             return self._scan("tpq_ivfpq_search_fused_cells", inputs, data, cell_start, address2id, n_candidates,
-                              n_split, slots_hint, packed, True, cells=cells, n_cells=n_cells, ds=ds, has_lut=False)
+                              n_split, slots_hint, packed, True, cells=cells, n_cells=n_cells, cell_threshold=cell_threshold,
+                              ds=ds, has_lut=False)
         return self._scan("tpq_ivfpq_search_fused_tickets", inputs, data, cell_start, address2id, n_candidates,
                           n_split, slots_hint, packed, True, ds=ds, has_lut=False)
 
