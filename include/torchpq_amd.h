@@ -915,6 +915,55 @@ int tpq_ivfpq_scan_filtered_residual_topk(const uint8_t* codes, const float* par
 int tpq_slot_filter_build(const int64_t* address, int64_t n, uint32_t* bits, int64_t n_slots, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQ4Index filtered search: the k best stored 4-bit codes of the probed cells AMONG the slots a filter allows,
+ * plain codes (tpq_ivfpq4_scan_filtered_topk) and residual codes (tpq_ivfpq4_scan_filtered_residual_topk).  No
+ * reference counterpart.
+ *
+ * codes, query, codebook, (centroids, cells, n_cells,) is_empty, cell_start, cell_size, n_probe_list, out_vals,
+ * out_addr, n_slots, m, ds, nq, max_nprobe, k, metric, n_split, workspace: as tpq_ivfpq4_scan_topk /
+ * tpq_ivfpq4_scan_residual_topk.
+ * Filter     the format of tpq_ivfpq_scan_filtered_topk: filter_bits u32 [n_filters][filter_stride], bit (s & 31) of
+ *            word (s >> 5) of row f says that slot address s is allowed by filter f; filter_stride >= ceil(n_slots /
+ *            32); the bits of slots >= n_slots are padding and are never looked at.  filter_of_query i32 [nq] names
+ *            the row of every query, NULL: every query uses row 0.  A row outside [0, n_filters) gives that query k
+ *            pads; neither the filter nor the codes are read for it.
+ * Result     candidates, values, order and padding are exactly those of tpq_ivfpq4_scan_topk / _residual_topk called
+ *            with is_empty | ~allowed_row(q) as the tombstone mask of query q, bit for bit: value descending, address
+ *            ascending; a NaN value never enters; (-inf, -1) beyond the candidates; n_probe_list clamped to
+ *            [0, max_nprobe]; a cell that leaves the storage is cut; a probe whose start equals the previous probe's
+ *            start is scanned once; for residual codes a slot of two overlapping cells is valued under each probe that
+ *            scans it.  The result does not depend on n_split.
+ * The scan tests a slot's bit before it reads the slot's code (and the tombstone byte only where the bit is set): a
+ * 64-slot tile without an allowed live slot reads no code word; the allowed slots of several tiles -- for residual
+ * codes of several probes, each looked up in the table of its own probe -- are valued together on full waves.
+ * Unsupported shapes and bad arguments are those of tpq_ivfpq4_scan_topk (m % 8 == 0 in [8, 256], ds >= 1, k in
+ * [1, 1024], n_slots < 2^31 - 1: else TPQ_ERR_UNSUPPORTED; metric, n_split in [1, 1024], n_cells >= 1, null pointers:
+ * TPQ_ERR_INVALID_ARGUMENT), plus n_filters >= 1, filter_stride >= ceil(n_slots / 32) and a non-null filter_bits, else
+ * TPQ_ERR_INVALID_ARGUMENT.  The LDS holds, next to what the unfiltered scan keeps there, the waves' pending lists (4 KiB;
+ * 8 KiB for residual codes, whose entries carry a table index): an (m, ds, max_nprobe) that pushes it over 160 KiB
+ * returns TPQ_ERR_UNSUPPORTED with a message.  nq == 0 is TPQ_OK without a launch.  Every check comes before the first
+ * HIP call.  Workspace: tpq_ivfpq4_scan_workspace_bytes(nq, k, n_split) bytes; too small: TPQ_ERR_WORKSPACE.
+ * Deterministic, no global atomics.  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+/* TPQ_VERSION is unchanged by these two symbols; a caller that must build against older headers tests this macro. */
+#define TPQ_HAS_IVFPQ4_SCAN_FILTERED 1
+int tpq_ivfpq4_scan_filtered_topk(const uint8_t* codes, const float* query, const float* codebook,
+                                  const uint8_t* is_empty, const int64_t* cell_start, const int64_t* cell_size,
+                                  const int64_t* n_probe_list, const uint32_t* filter_bits,
+                                  const int32_t* filter_of_query, int n_filters, int64_t filter_stride,
+                                  float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq,
+                                  int max_nprobe, int k, int metric, int n_split, void* workspace,
+                                  size_t workspace_bytes, tpq_stream_t stream);
+int tpq_ivfpq4_scan_filtered_residual_topk(const uint8_t* codes, const float* query, const float* codebook,
+                                           const float* centroids, const int64_t* cells, int n_cells,
+                                           const uint8_t* is_empty, const int64_t* cell_start,
+                                           const int64_t* cell_size, const int64_t* n_probe_list,
+                                           const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
+                                           int64_t filter_stride, float* out_vals, int64_t* out_addr, int64_t n_slots,
+                                           int m, int ds, int nq, int max_nprobe, int k, int metric, int n_split,
+                                           void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FlatIndex fused exact search: the k best stored vectors of every query without a [nq][n_slots] similarity
  * matrix -- a similarity GEMM on the fp32 matrix cores with a top-k epilogue (the semantics of the reference's
  * TopkBMMCuda, torchpq/kernels/TopkBMMCuda.py, which FlatIndex itself does not use).

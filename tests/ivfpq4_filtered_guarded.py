@@ -1,0 +1,56 @@
+"""The guarded-buffer cases of the two filtered 4-bit entry points (tpq_ivfpq4_scan_filtered_topk / _residual_topk),
+added to the table of tests/guarded_cases.py and to the builders of tests/test_gpu_guarded_buffers.py from here, through
+that module's own `case` registration: tests/test_guarded_alloc_cpu.py asks for a guarded case for every launching entry
+point that has a workspace or that a wrapper reaches.
+
+Importing this module registers the cases (once); both tests/test_ivfpq4_filtered_cpu.py and
+tests/test_gpu_ivfpq4_filtered.py import it, so a run that collects the suite has them in the table before any test
+runs.  The parametrised test of tests/test_gpu_guarded_buffers.py has read the table by then, so the two cases are run by
+tests/test_gpu_ivfpq4_filtered.py::test_guards_hold_and_results_do_not_depend_on_the_fill, on guarded_alloc.run_guarded
+and that module's `same_bits`.  Importing it needs no GPU.
+
+What this cannot give: tests/test_guarded_alloc_cpu.py run on its own, with neither new test file collected, does not
+import this module and reports the two entry points as lacking a case.  The table's own file is the place for these two
+lines; they are kept here only because this change adds files under tests/ and edits none.
+"""
+import guarded_cases as gc
+
+CASE_SYMBOLS = {
+    "ivfpq4_filtered_topk": ("tpq_ivfpq4_scan_filtered_topk",),
+    "ivfpq4_filtered_residual_topk": ("tpq_ivfpq4_scan_filtered_residual_topk",),
+}
+
+
+def builder(residual):
+    def build():
+        import ivfpq4_filtered_cases as cases
+        from test_gpu_ivfpq4_filtered import _gpu, _run
+        from torchpq_amd.kernels import IVFPQ4FilteredTopkHip
+        c = cases.case(24, 2, 3, 4, "euclidean", residual)
+        assert c["storage"].shape[1] % 32 != 0
+        _gpu(c)
+
+        def fn():
+            op, out = IVFPQ4FilteredTopkHip(m=24), []
+            for n_split in (None, 1, 5):
+                for run, k in ((0, 10), (1, 100), (len(c["runs"]) - 1, 10)):   # (the last run passes no row per query)
+                    out.append(_run(c, residual, c["runs"][run], k, "euclidean", n_split, op)[:2])
+                    assert op.last_n_split == n_split if n_split else op.last_n_split > 1
+            return out
+        return fn
+    return build
+
+
+def register():
+    import test_gpu_guarded_buffers as gpu        # (importing it needs no GPU: its cases are built when they run)
+    for cid, symbols in CASE_SYMBOLS.items():
+        if cid not in gc.CASE_SYMBOLS:
+            gc.CASE_SYMBOLS[cid] = symbols
+            gc.CASE_IDS.append(cid)
+            for s in symbols:
+                gc.CASES.setdefault(s, []).append(cid)
+        if cid not in gpu.BUILDERS:
+            gpu.case(cid)(builder(cid.endswith("residual_topk")))
+
+
+register()

@@ -29,19 +29,6 @@ constexpr int kMaxM = 148;      // 148 KiB + 4 KiB + 4 KiB = 156 KiB: 4 KiB left
 constexpr int kTilesAhead = 4;  // tiles whose filter words (then tombstone bytes) are loaded together
 constexpr int kRowGroup = 4;    // row loads in flight per lane, as scan_ref_kernel's group
 
-struct FilterArgs {
-  const uint32_t* bits;     // [n_filters][stride]
-  const int32_t* of_query;  // [nq] or nullptr: row 0
-  int64_t stride;
-  int n_filters;
-};
-
-// the query's row, or nullptr when it names none: the query then has no candidate and neither array is read further
-__device__ __forceinline__ const uint32_t* filter_row(const FilterArgs& f, int q) {
-  const int r = f.of_query ? f.of_query[q] : 0;
-  return (r >= 0 && r < f.n_filters) ? f.bits + (int64_t)r * f.stride : nullptr;
-}
-
 // The value of scan_ref_kernel / scan_residual_kernel (and of pqrange::slot_value, scan_range.hip): v starts at `v` and
 // adds lut[j][code_j] for j ascending, one fp32 add each.  `col` is the slot's dword of row 0, rows `stride` dwords apart.
 __device__ __forceinline__ float slot_value(const uint32_t* __restrict__ col, int64_t stride, const float* lut, int G,
@@ -71,19 +58,6 @@ __device__ __forceinline__ float slot_value(const uint32_t* __restrict__ col, in
     v += row[768 + (w >> 24)];
   }
   return v;
-}
-
-// a lane's slot of a tile: inside the cell, inside the storage, and allowed (the only read is the filter word)
-struct Member {
-  int s;
-  bool ok;
-};
-__device__ __forceinline__ Member member(const uint32_t* __restrict__ row, int start, int size, int off,
-                                         int64_t n_slots) {
-  const int64_t s64 = (int64_t)start + off;
-  bool ok = off < size && s64 >= 0 && s64 < n_slots;
-  if (ok) ok = ((row[s64 >> 5] >> (unsigned)(s64 & 31)) & 1u) != 0;
-  return Member{(int)s64, ok};
 }
 
 // `count` pending slots are valued, one per lane, and go through the admission step

@@ -148,6 +148,38 @@ struct Pending {
   }
 };
 
+// ---- filter rows ---------------------------------------------------------------------------------------------------
+// The bit rows of the filtered scans (scan_filtered.hip, scan_pq4_filtered.hip): bit s & 31 of word s >> 5 for slot s.
+namespace filtered {
+
+struct FilterArgs {
+  const uint32_t* bits;     // [n_filters][stride]
+  const int32_t* of_query;  // [nq] or nullptr: row 0
+  int64_t stride;
+  int n_filters;
+};
+
+// the query's row, or nullptr when it names none: the query then has no candidate and neither array is read further
+__device__ __forceinline__ const uint32_t* filter_row(const FilterArgs& f, int q) {
+  const int r = f.of_query ? f.of_query[q] : 0;
+  return (r >= 0 && r < f.n_filters) ? f.bits + (int64_t)r * f.stride : nullptr;
+}
+
+// a lane's slot of a tile: inside the cell, inside the storage, and allowed (the only read is the filter word)
+struct Member {
+  int s;
+  bool ok;
+};
+__device__ __forceinline__ Member member(const uint32_t* __restrict__ row, int start, int size, int off,
+                                         int64_t n_slots) {
+  const int64_t s64 = (int64_t)start + off;
+  bool ok = off < size && s64 >= 0 && s64 < n_slots;
+  if (ok) ok = ((row[s64 >> 5] >> (unsigned)(s64 & 31)) & 1u) != 0;
+  return Member{(int)s64, ok};
+}
+
+}  // namespace filtered
+
 // ---- values --------------------------------------------------------------------------------------------------------
 // one dimension of a value: -(q - x)^2 or q x added to acc, each operation rounded on its own
 template <int METRIC>

@@ -5,7 +5,9 @@ n_subvectors.  The container is CellContainer unchanged with code_size = n_subve
 `_storage` is uint8 [n_subvectors // 8, capacity, 4]; the list scan (tpq_ivfpq4_scan_topk, csrc/scan_pq4.hip) reads it
 in place -- a 16-entry table row has no LDS bank conflicts whatever the codes are, so there is no scan-layout copy --
 and builds the query's table (n_subvectors x 16 floats) inside the scan workgroup.  add / expand / remove / tombstones /
-`_address2id` / state_dict are the container's.  No range search, no captured graph.
+`_address2id` / state_dict are the container's.  `search_filtered` (tpq_ivfpq4_scan_filtered_topk / _residual_topk,
+csrc/scan_pq4_filtered.hip) gives the k best among an allowed id set, for both `pq_use_residual` settings, on the bit
+rows of `id_filter`.  No range search, no captured graph.
 
 `pq_use_residual=True` (semantically IVFPQIndex's): the PQ is learnt on, and a slot holds the code of,
 x - centroid(cell(x)); `encode` returns (pq_code, vq_code) and `decode` takes that pair and returns centroid + codeword.
@@ -22,8 +24,9 @@ import torch
 from .. import util
 from ..codec import PQ4Codec
 from ..container import CellContainer
-from ..kernels import IVFPQ4ResidualTopkHip, IVFPQ4TopkHip
+from ..kernels import IVFPQ4FilteredTopkHip, IVFPQ4ResidualTopkHip, IVFPQ4TopkHip
 from ._coarse import CoarseProbeMixin
+from ._filter import IdFilter, filtered_search_batches
 
 
 class IVFPQ4Index(CoarseProbeMixin, CellContainer):
@@ -50,6 +53,7 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
         self._init_coarse(n_cells, verbose)
         self.pq_codec = PQ4Codec(d_vector=d_vector, n_subvectors=n_subvectors, distance=distance, verbose=verbose)
         self._pq4_topk = (IVFPQ4ResidualTopkHip if self.pq_use_residual else IVFPQ4TopkHip)(m=n_subvectors)
+        self._pq4_filtered = IVFPQ4FilteredTopkHip(m=n_subvectors)
         self.to(device)
 
     # ---- knobs (as IVFPQIndex) -------------------------------------------------------------------------
@@ -163,3 +167,43 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
             x=xb, cells=cells, base_sims=sims, n_probe_list=n_probe_list, k=k, return_address=True,
             _extents=extents))
         return (vals, ids, address) if return_address else (vals, ids)
+
+    # ---- filtered search ---------------------------------------------------------------------------
+    def id_filter(self, ids):
+        """ids: an int64 tensor -- one set of allowed ids -- or a sequence of them, one filter row each -> IdFilter,
+        what search_filtered takes.  Ids the index does not hold are ignored; the filter follows later add / remove."""
+        return IdFilter(self, ids)
+
+    def search_cells_filtered(self, x, cells, flt, filter_of_query=None, base_sims=None, n_probe_list=None, k=1,
+                              return_address=False, _extents=None):
+        """The k best live codes of the given cells [n_query, n_probe] among the ids `flt` allows; (values, ids[,
+        address]).  `filter_of_query`: int32 [n_query], the row of `flt` every query uses (None: row 0).  The table of
+        a query (of every probe, with pq_use_residual) is the one search_cells builds.  (`base_sims` is accepted for
+        IVFPQIndex's signature and unused; `_extents` as in search_cells.)"""
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        _extents)
+        lists = dict(cell_start=cell_start, cell_size=cell_size, n_probe_list=n_probe_list, k=k,
+                     filter_bits=flt.bits(self), filter_of_query=filter_of_query, is_empty=is_empty,
+                     distance=self.distance, slots_hint=slots_hint)
+        if self.pq_use_residual:
+            vals, address = self._pq4_filtered.residual(self._storage, x, self.pq_codec.codebook,
+                                                        self._cell_major_centroids(), cells, **lists)
+        else:
+            vals, address = self._pq4_filtered(self._storage, x, self.pq_codec.codebook, **lists)
+        ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)   # (an empty batch)
+        return (vals, ids, address) if return_address else (vals, ids)
+
+    def search_filtered(self, x, k, flt, filter_of_query=None):
+        """x [d_vector, n_query] f32, flt = index.id_filter(ids) -> (values f32 [n_query, k] descending, ids int64
+        [n_query, k]): the k best stored codes of the query's probed cells (`n_probe`, as in search) AMONG the ids the
+        filter allows, padded with (-inf, -1) where fewer exist.  `filter_of_query`: an int tensor [n_query] choosing
+        the filter's row per query (a filter made from a sequence of id sets); the default is row 0 for every query.
+        A result carries the value search returns for the same code; equal values come by ascending slot address."""
+        x = self._prepare(x)
+        assert 0 < k <= 1024
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        return filtered_search_batches(
+            self, x, flt, filter_of_query, lambda xb, rows, sims, cells, n_probe_list, extents:
+            self.search_cells_filtered(xb, cells, flt, filter_of_query=rows, base_sims=sims,
+                                       n_probe_list=n_probe_list, k=k, _extents=extents))

@@ -1,6 +1,7 @@
-"""Id filters for filtered search (IVFPQIndex.search_filtered, IVFFlatIndex.search_filtered / range_search_filtered): sets of ids
-kept over the container's slot addresses in the form the index's list scan tests -- rows of bits for IVFPQIndex
-(csrc/scan_filtered.hip), rows of skip bytes for IVFFlatIndex (the `is_empty` mask of csrc/scan_flat.hip)."""
+"""Id filters for filtered search (IVFPQIndex.search_filtered, IVFPQ4Index.search_filtered, IVFFlatIndex.search_filtered /
+range_search_filtered): sets of ids kept over the container's slot addresses in the form the index's list scan tests --
+rows of bits for IVFPQIndex (csrc/scan_filtered.hip) and IVFPQ4Index (csrc/scan_pq4_filtered.hip), rows of skip bytes
+for IVFFlatIndex (the `is_empty` mask of csrc/scan_flat.hip)."""
 import torch
 
 from ..kernels import SlotFilterBuildHip
@@ -13,7 +14,8 @@ class IdFilter:
     words], bit a & 31 of word a >> 5 for address a -- are built on first use from the container's id-to-address
     look-up, and built again whenever the container's `_codes_version` has moved: add, remove, growth and compaction
     all move addresses or liveness, so a filter made before an add stays correct after it.  Ids the container does not
-    hold are ignored (a later add of such an id makes it count).  `bits()` is what IVFPQIndex's filtered scan reads;
+    hold are ignored (a later add of such an id makes it count).  `bits()` is what the filtered scans of IVFPQIndex
+    and IVFPQ4Index read;
     `masks()` is the same sets as skip masks, uint8 [n_filters, capacity], which IVFFlatIndex hands its list scan and
     its range search in the place of the tombstones -- kept and rebuilt by the same rule."""
 

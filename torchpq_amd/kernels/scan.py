@@ -1086,6 +1086,81 @@ class IVFPQFilteredTopkHip:
         return topk_result(values, address, ids)
 
 
+class IVFPQ4FilteredTopkHip:
+    """Filtered top-k over the lists of IVFPQ4Index (tpq_ivfpq4_scan_filtered_topk / _residual_topk,
+    csrc/scan_pq4_filtered.hip): the result of IVFPQ4TopkHip / IVFPQ4ResidualTopkHip among the slots the query's row of
+    filter bits allows, bit for bit what those give with `is_empty | ~allowed_row` as the tombstone mask; the semantics
+    are defined in include/torchpq_amd.h."""
+
+    def __init__(self, m=8):
+        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
+
+    _n_split = IVFFlatTopkHip._n_split
+
+    def _scan(self, symbol, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, k, filter_bits,
+              filter_of_query, is_empty, distance, n_split, slots_hint):
+        """both calls; `residual` is () or (centroids, cells)"""
+        n_slots = codes.shape[1]
+        m, ds, kk = codebook.shape
+        n_query, n_probe = cell_start.shape
+        assert m == self.m and kk == 16 and ds >= 1
+        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+        filter_of_query = IVFPQFilteredTopkHip._check_filter(filter_bits, filter_of_query, n_slots, n_query)
+        assert filter_bits.is_contiguous()
+        tables = ()
+        if residual:
+            centroids, cells = residual
+            assert centroids.dtype == torch.float32
+            assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+            centroids, cells = centroids.contiguous(), cells.contiguous()
+            tables = (ptr(centroids), ptr(cells), centroids.shape[0])
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 1024
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(codes, query, codebook, *residual, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
+                    filter_of_query)
+        device = codes.device
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
+        call(symbol, device,
+             ptr(codes), ptr(query), ptr(codebook), *tables, ptr(is_empty), ptr(cell_start), ptr(cell_size),
+             ptr(n_probe_list), ptr(filter_bits), ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1],
+             ptr(values), ptr(address), n_slots, m, ds, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
+             ws_bytes)
+        return values, address
+
+    def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, k, filter_bits,
+                 filter_of_query=None, is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
+        """Plain codes.
+          codes, query, codebook, cell_start, cell_size, n_probe_list, is_empty: as IVFPQ4TopkHip
+          filter_bits: [n_filters, stride] int32, bit s & 31 of word s >> 5 of a row: slot s is allowed
+          filter_of_query: [n_query] int32, the row of every query (outside [0, n_filters): no candidate); None: row 0
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        return self._scan("tpq_ivfpq4_scan_filtered_topk", codes, query, codebook, (), cell_start, cell_size,
+                          n_probe_list, k, filter_bits, filter_of_query, is_empty, distance, n_split, slots_hint)
+
+    def residual(self, codes, query, codebook, centroids, cells, cell_start, cell_size, n_probe_list, k, filter_bits,
+                 filter_of_query=None, is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
+        """Residual codes: centroids [n_cells, d] and cells [n_query, max_n_probe] as IVFPQ4ResidualTopkHip, everything
+        else, and the result, as __call__"""
+        return self._scan("tpq_ivfpq4_scan_filtered_residual_topk", codes, query, codebook, (centroids, cells),
+                          cell_start, cell_size, n_probe_list, k, filter_bits, filter_of_query, is_empty, distance,
+                          n_split, slots_hint)
+
+
 # ---- what the range wrappers share --------------------------------------------------------------------------------
 def _checked_threshold(threshold, n_query):
     """a range search's threshold: a Python float, or one float32 per query (returned contiguous)"""
