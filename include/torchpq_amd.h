@@ -248,7 +248,7 @@ int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max
 int tpq_ivfpq_scan_cell_norms(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint, int has_lut,
                               int has_packed, int has_tickets, int residual, int n_cells, int64_t n_slots,
                               size_t workspace_bytes);
-/* The workspace need not be zeroed: cell_prep_kernel and cell_seed_kernel clear every counter and array the later stages read. */
+/* The workspace need not be zeroed: cell_seed_kernel clears every counter and array the later stages read. */
 size_t tpq_ivfpq_cell_candidates_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe);
 /* The workspace need not be zeroed: the slot norms behind the arrays above are written by cell_norm_kernel for every listed cell. */
 size_t tpq_ivfpq_cell_candidates_norms_workspace_bytes(int nq, int max_nprobe, int n_cells, int first_probe,
@@ -278,6 +278,33 @@ int tpq_ivfpq_scan_cell_threshold(int nq, int k, int n_split, int m, int ds, int
                                   int64_t n_slots, size_t workspace_bytes);
 int tpq_ivfpq_scan_use_cell_threshold(int on);
 int tpq_ivfpq_scan_cell_threshold_probes(void);
+/* The kept state of the cell-major form: what a call of the form with slot norms derives from the index alone -- the
+ * codebook's scale and bound, the split fp16 codebook as the candidate kernels stage it, and an fp32 norm per slot
+ * address (NaN: tombstone) -- in a caller-owned device buffer of tpq_ivfpq_cell_kept_bytes(n_slots, ds) bytes (host
+ * arithmetic; 0 for ds outside 1, 2), so that a caller that searches an unchanged index many times pays for it once.
+ * tpq_ivfpq_search_fused_cells_kept: tpq_ivfpq_search_fused_cells plus `kept`, its size and `kept_valid`.  A call that
+ * takes the form with slot norms (tpq_ivfpq_scan_cell_norms is 1) and is handed kept_valid == 0 first writes the state, on
+ * `stream`, then reads it; with kept_valid == 1 it only reads it: no parameter pass, no norm pass, no codebook
+ * conversion.  The caller sets kept_valid = 1 for later calls while codes, codebook and tombstones are unchanged, and
+ * orders calls on other streams behind the call that wrote the state.  Any other call ignores `kept` and writes nothing
+ * to it, as does a call whose `kept` is NULL or smaller than the size above: those are tpq_ivfpq_search_fused_cells.  Same
+ * results, bit for bit.  `kept` must be 16-byte aligned (the image is read with 16-byte loads; any other alignment is
+ * rejected before anything is launched).  TPQ_VERSION is unchanged by these symbols.
+ * tpq_ivfpq_scan_cell_inversions (diagnostics, host only): the count / scan / scatter chains the cell-major form has
+ * launched in this process so far -- one per call of the seeded form and of the threshold form's one walk, two per call
+ * of the threshold form beyond 8 192 cells. */
+#define TPQ_HAS_IVFPQ_CELL_KEPT 1
+size_t tpq_ivfpq_cell_kept_bytes(int64_t n_slots, int ds);
+long long tpq_ivfpq_scan_cell_inversions(void);
+int tpq_ivfpq_search_fused_cells_kept(const uint8_t* packed, const uint8_t* codes, const float* query,
+                                      const float* codebook, int ds, int metric, const uint8_t* is_empty,
+                                      const int64_t* cell_start, const int64_t* cell_size,
+                                      const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
+                                      const int64_t* address2id, int64_t* out_ids, int64_t n_slots,
+                                      int nq, int max_nprobe, int m, int k, int n_split, void* workspace,
+                                      size_t workspace_bytes, int32_t* tickets, int64_t slots_hint,
+                                      const int64_t* cells, int n_cells, void* kept, size_t kept_bytes,
+                                      int kept_valid, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * SURVEY 8(f)-3  residual-PQ list scan (pq_use_residual=True)

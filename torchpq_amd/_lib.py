@@ -47,6 +47,11 @@ SIGNATURES = {
                                             _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp]),
     "tpq_ivfpq_search_fused_cells": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp, _i, _vp]),
+    "tpq_ivfpq_search_fused_cells_kept": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp, _i, _vp, _sz, _i,
+                                               _vp]),
+    "tpq_ivfpq_cell_kept_bytes": (_sz, [_i64, _i]),
+    "tpq_ivfpq_scan_cell_inversions": (_i64, []),
     "tpq_ivfpq_scan_cell_major": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
     "tpq_ivfpq_scan_cell_norms": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
     "tpq_ivfpq_cell_candidates_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -408,7 +408,16 @@ extern "C" int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds,
 struct CellMajor {
   const int64_t* cells;  // [nq][max_nprobe]
   int n_cells;
+  // the caller's kept state (scan_cells.hip: `The kept state`; nullptr: none) and whether it is valid for these codes,
+  // codebook and tombstones; a call that takes the form with slot norms builds it first when it is not
+  void* kept = nullptr;
+  size_t kept_bytes = 0;
+  int kept_valid = 0;
 };
+// a state too small for the index is not used (and not written)
+static void cell_major_use_kept(CellArgs& c, const CellMajor& cm) {
+  if (cm.kept && c.norm && cm.kept_bytes >= cell_kept_bytes(c.n_slots, c.ds)) cell_use_kept(c, cm.kept, cm.kept_valid);
+}
 static int cell_major_chunks(const ScanArgs& a, const ScanPlan& p, bool residual, int n_cells, size_t workspace_bytes) {
   if (residual || p.route != TPQ_SCAN_ROUTE_DUMP_SEL16 || a.lut || a.m != 64 || a.ds < 1 || a.ds > 2) return 0;
   if (a.k > 128 || a.max_nprobe <= kCellP0 || n_cells < 1 || a.n_slots <= 0 || a.slots_hint <= 0) return 0;
@@ -466,6 +475,7 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
   const size_t cm_lists = ws_bytes_for(nq, 1, chunks);  // (the gate saw to it: lists and extras fit)
   cell_fill_extras(c, reinterpret_cast<char*>(workspace) + cm_lists, workspace_bytes - cm_lists);
+  cell_major_use_kept(c, cm);  // (with room for per-call norms only: tpq_ivfpq_scan_cell_norms is the rule for both)
   rc = launch_cell_candidates(c, st);
   if (rc) return rc;
   // 5. the finish kernel over the chunks that were filled (the seed chunks and ceil(cnt[q] / 64) behind them): F_k, the
@@ -513,6 +523,7 @@ static int run_cell_threshold(ScanArgs& a, const ScanPlan& p, const PackedUnit& 
   char* at = reinterpret_cast<char*>(workspace) + ws_bytes_for(nq, 1, chunks);
   const size_t head = cell_extra_bytes(nq, a.max_nprobe, cm.n_cells, kCellP0) + cell_norm_bytes(a.n_slots);
   cell_fill_extras(c, at, head, kCellP0);
+  cell_major_use_kept(c, cm);
   CellThrArrays t{};
   cell_fill_thr(t, at + head, nq, a.max_nprobe, cm.n_cells);
   int rc = launch_cell_threshold(c, t, st);
@@ -646,6 +657,35 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
 // ---- entry points (their ScanArgs: scan_args, scan_list.h) ---------------------------------------------
 extern "C" size_t tpq_ivfpq_scan_tickets_bytes(int nq) { return nq > 0 ? (size_t)nq * sizeof(int32_t) : 0; }
 
+extern "C" size_t tpq_ivfpq_cell_kept_bytes(int64_t n_slots, int ds) {
+  return n_slots > 0 && (ds == 1 || ds == 2) ? cell_kept_bytes(n_slots, ds) : 0;
+}
+
+extern "C" int tpq_ivfpq_search_fused_cells_kept(const uint8_t* packed, const uint8_t* codes,
+                                                 const float* query, const float* codebook, int ds,
+                                                 int metric, const uint8_t* is_empty,
+                                                 const int64_t* cell_start, const int64_t* cell_size,
+                                                 const int64_t* n_probe_list, float* out_vals,
+                                                 int64_t* out_addr, const int64_t* address2id,
+                                                 int64_t* out_ids, int64_t n_slots, int nq, int max_nprobe,
+                                                 int m, int k, int n_split, void* workspace,
+                                                 size_t workspace_bytes, int32_t* tickets,
+                                                 int64_t slots_hint, const int64_t* cells, int n_cells,
+                                                 void* kept, size_t kept_bytes, int kept_valid,
+                                                 tpq_stream_t stream) {
+  TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER,
+              "ivfpq_search_fused: bad metric %d", metric);
+  TPQ_REQUIRE(ds >= 1 && ds <= 1024, "ivfpq_search_fused: bad sub-vector length %d", ds);
+  ScanArgs a = scan_args(codes, packed, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
+  a.query = query; a.codebook = codebook; a.ds = ds; a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
+  a.tickets = tickets; a.slots_hint = slots_hint;
+  TPQ_REQUIRE((reinterpret_cast<uintptr_t>(kept) & 15) == 0, "ivfpq_search_fused: the kept state must be 16-byte aligned");
+  const CellMajor cm{cells, n_cells, kept, kept_bytes, kept_valid};
+  return packed ? run_packed(a, nullptr, workspace, workspace_bytes, stream, cells ? &cm : nullptr)
+                : run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t* codes,
                                             const float* query, const float* codebook, int ds,
                                             int metric, const uint8_t* is_empty,
@@ -657,16 +697,10 @@ extern "C" int tpq_ivfpq_search_fused_cells(const uint8_t* packed, const uint8_t
                                             size_t workspace_bytes, int32_t* tickets,
                                             int64_t slots_hint, const int64_t* cells, int n_cells,
                                             tpq_stream_t stream) {
-  TPQ_REQUIRE(metric == TPQ_METRIC_NEG_SQ_L2 || metric == TPQ_METRIC_INNER,
-              "ivfpq_search_fused: bad metric %d", metric);
-  TPQ_REQUIRE(ds >= 1 && ds <= 1024, "ivfpq_search_fused: bad sub-vector length %d", ds);
-  ScanArgs a = scan_args(codes, packed, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
-                         address2id, out_ids, n_slots, nq, max_nprobe, m, k, n_split);
-  a.query = query; a.codebook = codebook; a.ds = ds; a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
-  a.tickets = tickets; a.slots_hint = slots_hint;
-  const CellMajor cm{cells, n_cells};
-  return packed ? run_packed(a, nullptr, workspace, workspace_bytes, stream, cells ? &cm : nullptr)
-                : run_ref(a, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return tpq_ivfpq_search_fused_cells_kept(packed, codes, query, codebook, ds, metric, is_empty, cell_start, cell_size,
+                                           n_probe_list, out_vals, out_addr, address2id, out_ids, n_slots, nq,
+                                           max_nprobe, m, k, n_split, workspace, workspace_bytes, tickets, slots_hint,
+                                           cells, n_cells, nullptr, 0, 0, stream);
 }
 
 extern "C" int tpq_ivfpq_search_fused_tickets(const uint8_t* packed, const uint8_t* codes,

@@ -28,6 +28,18 @@ constexpr int kCellThrMinCell = 512;
 constexpr int kCellMinRereads = 96;
 constexpr int kCellQSplit = 256;  // halfs per query of the split copy: [hi, lo][128 components]
 constexpr int kCellGroup = 32;   // queries per candidate block: the 32 MFMA columns of a wave
+// A candidate block -- (cell, group) over the cell's whole length -- is dealt in this many pieces of whole tiles: piece i
+// of S covers tiles [i nt / S, (i + 1) nt / S) of the cell's nt = ceil(size / 32).  The launch ends a block's length
+// after its last draw at the latest; pieces shorten that unit (profiles/cell_pieces_bench.json).  1: the block undivided
+#ifndef TPQ_CELL_PIECES_A
+#define TPQ_CELL_PIECES_A 2  // pass A of the threshold form (variant builds: the A/B of 1, 2 and 4)
+#endif
+#ifndef TPQ_CELL_PIECES_B
+#define TPQ_CELL_PIECES_B 1  // the candidates proper, either form: 2 stayed inside the trace-to-trace variation
+#endif
+constexpr int kCellPiecesA = TPQ_CELL_PIECES_A, kCellPiecesB = TPQ_CELL_PIECES_B;
+static_assert(kCellPiecesA >= 1 && kCellPiecesA <= 8 && kCellPiecesB >= 1 && kCellPiecesB <= 8, "pieces per block");
+constexpr int cell_pieces(bool maxima) { return maxima ? kCellPiecesA : kCellPiecesB; }
 // the inversion counts and scatters per workgroup, over a slice of this many consecutive queries, in an LDS histogram of
 // one int per cell (profiles/cell_inversion_bench.json)
 #ifndef TPQ_CELL_SLICE
@@ -37,6 +49,11 @@ constexpr int kCellSlice = TPQ_CELL_SLICE;
 // cells the LDS histogram takes: 64 KiB, two workgroups per CU.  Beyond it the inversion issues one global atomic per
 // listed pair (a slice's pairs hardly share a cell there, and every workgroup would walk the whole histogram twice)
 constexpr int kCellLdsCells = 16384;
+
+// one view of the inversion: the pairs of a range of probes grouped by cell (the fields of that name in CellArgs)
+struct CellView {
+  int *hist, *cell_off, *blk_off, *cell_st, *cell_sz, *pairs;
+};
 
 struct CellArgs {
   const uint8_t* codes;          // reference layout [16][n_slots][4]
@@ -83,9 +100,35 @@ struct CellArgs {
   // the threshold form (behind the norms, cell_thr_bytes): the second inversion's histogram, which cell_prep_kernel
   // zeroes with the first (nullptr: none), and where cell_kth_kernel leaves the number of maxima pass A reserved
   // (nullptr: nowhere)
-  int* hist2;                    // [n_cells]
+  int* hist2;                    // [n_cells]: the one walk's second histogram and cursor (pass A's view) as well
   int* n_max;                    // [nq]
+  // the threshold form's one walk (launch_cell_threshold, n_cells <= kCellLdsCells / 2: two LDS histograms): the count,
+  // scan and scatter launches of the view above also count (into hist2) and place the pairs with p < p_a -- pass A's
+  // view -- into this one (va.hist == hist2); p_a == 0: one view
+  int p_a;
+  CellView va;
+  // what depends on the index alone (`The kept state`, scan_cells.hip).  kparams: the four numbers of cell_prep_kernel --
+  // params itself, or the head of a caller-owned kept state; the block counters stay at params + 8.  book: the split
+  // codebook as the candidate kernels stage it (CellBook<DS>), copied into LDS instead of converted; nullptr: no kept
+  // state, every workgroup converts.  With a kept state `norm` points into it and covers every slot address.
+  // kept_build: the state is not valid yet -- this call writes it first, on its stream
+  float* kparams;
+  unsigned* book;
+  int kept_build;
 };
+// the kept state: [256 bytes: the parameters][the codebook image, 64 x 256 x 4 ds bytes][an fp32 norm per slot address]
+inline size_t cell_book_bytes(int ds) { return (size_t)64 * 256 * 4 * ds; }
+inline size_t cell_kept_bytes(int64_t n_slots, int ds) {
+  return 256 + cell_book_bytes(ds) + ((((size_t)(n_slots > 0 ? n_slots : 0) * 4) + 255) & ~(size_t)255);
+}
+// points a.kparams, a.book and a.norm into the kept state at `kept` (cell_kept_bytes of it)
+inline void cell_use_kept(CellArgs& a, void* kept, int valid) {
+  char* p = reinterpret_cast<char*>(kept);
+  a.kparams = reinterpret_cast<float*>(p);
+  a.book = reinterpret_cast<unsigned*>(p + 256);
+  a.norm = reinterpret_cast<float*>(p + 256 + cell_book_bytes(a.ds));
+  a.kept_build = valid ? 0 : 1;
+}
 // the arrays of the threshold form: pass B's pairs (all probes: the extras hold max_nprobe - kCellP0 per query), then
 // pass A's inversion -- hist, cell_off, blk_off, cell_st, cell_sz, pairs --, then the maxima counts [nq]
 struct CellThrArrays {
@@ -93,6 +136,10 @@ struct CellThrArrays {
   int *hist, *cell_off, *blk_off, *cell_st, *cell_sz, *pairs, *n_max;
 };
 
+// the view the loose fields of `a` describe
+__host__ __device__ inline CellView cell_view(const CellArgs& a) {
+  return CellView{a.hist, a.cell_off, a.blk_off, a.cell_st, a.cell_sz, a.pairs};
+}
 inline size_t cell_align(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t cell_extra_bytes(int nq, int max_nprobe, int n_cells, int p0) {
   const int np = max_nprobe > p0 ? max_nprobe - p0 : 0;

@@ -10,12 +10,14 @@
 //
 // Kernels (all on the caller's stream; no host read, no allocation):
 //   cell_prep_kernel     one block: the codebook's max |entry| (-> the power-of-two scale s_x) and X^2 = sum_j max_c
-//                        |c_jc|^2 >= |x|^2 of every decodable slot; zeroes the histogram.
+//                        |c_jc|^2 >= |x|^2 of every decodable slot.  Not launched by a call that reads a kept state.
 //   cell_seed_kernel     one wave per query: tau_q (the k-th seed, or the caller's threshold), the query's scale s_q and
 //                        |q|^2, delta_q, the admission threshold tau_q - delta_q (euclidean: folded over |q|^2, see `The
 //                        admission test`) and ws_delta = 2 delta_q; the seeds into the
 //                        first ceil(k / 64) chunks of the query's lists in the finish kernel's format (value image,
-//                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words.
+//                        ~address), pads (~kPadIdx) behind them; zero counter and eviction words.  Over its whole grid
+//                        it also zeroes what the later stages count in: the histogram(s) of the inversion and the
+//                        candidate kernel's two block counters.
 //                        A query that was flagged before, has a non-finite component, norm or
 //                        threshold (NaN, +inf), cannot be scaled or lists a cell outside [0, n_cells) is flagged and takes
 //                        no further part (tau = -inf is a threshold like any other: everything is admitted, and what
@@ -35,6 +37,9 @@
 //                        places the pairs: pairs[lds_cursor[cell]++] = q; the pair that takes a cell's first position
 //                        writes the cell's extent.  The order inside a cell varies from run to run; nothing downstream
 //                        depends on it.
+//                        <true>, with a second block of cell_scan_kernel: the threshold form's ONE walk -- a second LDS
+//                        histogram and cursor per cell for the pairs with p < kCellThrProbes, so that the three launches
+//                        fill pass A's view beside pass B's (n_cells <= kCellLdsCells / 2; launch_cell_threshold).
 //   cell_count_wide_kernel, cell_scatter_wide_kernel   n_cells > kCellLdsCells: one wave per query, one global atomic
 //                        per pair -- the form both stages had before; a slice's pairs hardly share a cell there.
 //   cell_norm_kernel     when the workspace has room for an fp32 per slot behind the other arrays (CellArgs::norm):
@@ -56,6 +61,9 @@
 //                        update per flush -- at the end of the block, or when a segment is full (a returning atomic
 //                        per row was four or five dependent round trips per tile, one per lane and tile still one).
 //                        A probe listed twice in a row is skipped as the scan skips it (fetch_probes, scan_shared.h).
+//                        A block is dealt in S pieces of whole tiles (scan_cells.h: kCellPiecesA for pass A, kCellPiecesB
+//                        otherwise; 1: undivided): draw w is piece w % S of block w / S, its flush or its reservation
+//                        of maxima the piece's own.  Whole tiles: the groups of pass A are the same sets of rows.
 //                        <.., MAXIMA>: pass A of the threshold form -- group maxima instead of admitted rows.
 //   cell_kth_kernel      the threshold form, one wave per query: the k-th largest of pass A's maxima -> thr[q]; zeroes
 //                        cnt[q] (`The threshold from group maxima`, below).
@@ -165,6 +173,30 @@
 //   entry it appends from position 0 on, and the finish kernel zeroes the key of every entry whose index is pad: stage 5
 //   never sees a maximum.  The two candidate launches draw their blocks from two counters (params + 8, + 9).
 // (Measured on the headline batch: profiles/cell_threshold_bench.json.)
+//
+// The kept state (tpq_ivfpq_search_fused_cells_kept; CellArgs::kparams, book, norm; cell_use_kept, scan_cells.h).  Three
+// things a call of the form with slot norms computes are functions of the codebook, the codes and the tombstones alone --
+// no query enters: cell_prep_kernel's four numbers, the split fp16 codebook every candidate workgroup (and the norm
+// kernel) derives from the fp32 one before its first tile, and cell_norm_kernel's norms.  An index is searched many times
+// between two changes, so a caller that owns the index may own them too: a device buffer of cell_kept_bytes(n_slots, ds),
+//   [256 bytes: max |entry|, X^2, scalable, s_x][the codebook image: [j][c] -> DS hi pieces, DS lo pieces, what
+//   CellBook<DS> holds in LDS][an fp32 norm per slot ADDRESS in [0, n_slots), NaN for a tombstone]
+// The norms cover every address, not the listed cells: the chain of a slot reads that slot's 64 code bytes and its
+// tombstone byte only, so no cell structure is needed, and the bytes of a slot outside any cell decode to some value
+// that nobody reads.  Per slot the chain, and so the bits, are cell_norm_kernel's (the same kernel, ALL).
+//   kept_valid == 0   the call writes the state first, on its stream: cell_prep_kernel (into the state), cell_book_kernel
+//                     (the image, book_entry -- the one definition the per-call staging uses too), cell_norm_kernel<DS,
+//                     true>; then it runs as below.  The caller then hands the state to later calls as valid, for as long
+//                     as codes, codebook and tombstones are what they were, and orders other streams behind this call.
+//   kept_valid == 1   neither cell_prep_kernel nor cell_norm_kernel is launched; the candidate kernels copy the image into
+//                     LDS with 16-byte loads instead of converting 16 384 entries per workgroup; the seed kernel reads
+//                     `scalable` and X^2, the candidate kernels s_x, through kparams.  The zeroing cell_prep_kernel used
+//                     to do is the seed kernel's, so no single-block launch is left.
+// The block counters and everything per call stay in the workspace, whose size and layout are what they were (its norm
+// region is simply unused).  Only a call that takes the form WITH slot norms (scan.hip: cell_major_norms, either form)
+// uses a state; every other call ignores the pointer and writes nothing to it.  Same bits on every path: the state holds
+// exactly what the per-call kernels would have produced.
+#include <atomic>
 #include <cmath>
 
 #include "mfma_util.h"
@@ -204,6 +236,9 @@ void cell_fill_extras(CellArgs& a, void* at, size_t room, int layout_p0) {
   a.cell_sz = reinterpret_cast<int*>(take((size_t)a.n_cells * 4));
   a.pairs = reinterpret_cast<int*>(take((size_t)a.nq * np * 4));
   a.qsplit = reinterpret_cast<_Float16*>(take((size_t)a.nq * kCellQSplit * 2));
+  a.kparams = a.params;  // (no kept state: cell_use_kept, scan_cells.h, points these elsewhere)
+  a.book = nullptr;
+  a.kept_build = 0;
 }
 
 constexpr int kCellScaleExp = 12;   // the largest scaled component lies in [2^12, 2^13)
@@ -214,32 +249,51 @@ constexpr unsigned kMaxFiniteBits = 0x7f7fffffu;
 __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 __device__ __forceinline__ int exp_of_bits(unsigned bits) { return (int)((bits >> 23) & 255u) - 127; }
 
-__global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
-  __shared__ unsigned maxbits_s;
-  __shared__ float c2max_s[64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) maxbits_s = 0u;
-  for (int i = tid; i < a.n_cells; i += 1024) a.hist[i] = 0;
-  if (a.hist2)
-    for (int i = tid; i < a.n_cells; i += 1024) a.hist2[i] = 0;
-  __syncthreads();
+// a wave's share of the codebook's maxima: sub-quantizers wave, wave + 16, ...; per sub-quantizer the largest |c_jc|^2 into
+// c2max_s[j], and the largest |entry| bits of all it read.  DS is a constant so that the thread's 16 DS loads are issued
+// together, ahead of the arithmetic: with the length read from the arguments they went out one by one, each waited for
+// where it was issued, and the one block took 17 us over 128 KiB (profiles/cell_pieces_bench.json).  The chains and the
+// maxima are what they were: fma over e ascending per entry, maxima of non-negative numbers in any order
+template <int DS>
+__device__ __forceinline__ unsigned prep_maxima(const float* __restrict__ codebook, int lane, int wave, float* c2max_s) {
+  float y[4][4][DS];
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+      for (int e = 0; e < DS; ++e) y[jj][cc][e] = codebook[((wave + 16 * jj) * DS + e) * 256 + lane + 64 * cc];
   unsigned mb = 0u;
-  for (int j = wave; j < 64; j += 16) {
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
     float c2m = 0.f;
-    for (int c = lane; c < 256; c += 64) {
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {
       float c2 = 0.f;
-      for (int e = 0; e < a.ds; ++e) {
-        const float y = a.codebook[((int64_t)j * a.ds + e) * 256 + c];
-        const unsigned b = __float_as_uint(y) & 0x7fffffffu;
+#pragma unroll
+      for (int e = 0; e < DS; ++e) {
+        const unsigned b = __float_as_uint(y[jj][cc][e]) & 0x7fffffffu;
         mb = b > mb ? b : mb;
-        c2 = fmaf(y, y, c2);
+        c2 = fmaf(y[jj][cc][e], y[jj][cc][e], c2);
       }
       c2m = fmaxf(c2m, c2);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) c2m = fmaxf(c2m, __shfl_xor(c2m, d, 64));
-    if (lane == 0) c2max_s[j] = c2m;
+    if (lane == 0) c2max_s[wave + 16 * jj] = c2m;
   }
+  return mb;
+}
+
+__global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
+  __shared__ unsigned maxbits_s;
+  __shared__ float c2max_s[64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) maxbits_s = 0u;
+  __syncthreads();
+  // (ds is 1 or 2: the entry points of the form)
+  const unsigned mb = a.ds == 1 ? prep_maxima<1>(a.codebook, lane, wave, c2max_s)
+                                : prep_maxima<2>(a.codebook, lane, wave, c2max_s);
   atomicMax(&maxbits_s, mb);
   __syncthreads();
   if (tid == 0) {
@@ -249,12 +303,10 @@ __global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
     const unsigned bits = maxbits_s;
     const int e = exp_of_bits(bits);
     const bool ok = bits != 0u && bits <= kMaxFiniteBits && e >= -kCellMaxExp && e <= kCellMaxExp && x2 <= 3e38f;
-    a.params[0] = __uint_as_float(bits);
-    a.params[1] = x2;
-    a.params[2] = ok ? 1.f : 0.f;
-    a.params[3] = ok ? pow2i(kCellScaleExp - e) : 0.f;  // s_x
-    reinterpret_cast<int*>(a.params)[8] = 0;            // cell_cand_kernel's block counters: CellArgs::work
-    reinterpret_cast<int*>(a.params)[9] = 0;
+    a.kparams[0] = __uint_as_float(bits);
+    a.kparams[1] = x2;
+    a.kparams[2] = ok ? 1.f : 0.f;
+    a.kparams[3] = ok ? pow2i(kCellScaleExp - e) : 0.f;  // s_x
   }
 }
 
@@ -278,6 +330,13 @@ __device__ __forceinline__ ListedProbe listed_probe(const CellArgs& a, int q, in
 __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
   const int lane = (int)(threadIdx.x & 63);
   const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  // what the call's later stages count in: the histograms of the inversion and cell_cand_kernel's block counters
+  // (CellArgs::work).  Here, over the whole grid, so that a call with a kept state launches no block of its own for it
+  for (int i = (int)(blockIdx.x * 256 + threadIdx.x); i < a.n_cells; i += (int)gridDim.x * 256) {
+    a.hist[i] = 0;
+    if (a.hist2) a.hist2[i] = 0;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 2) reinterpret_cast<int*>(a.params)[8 + threadIdx.x] = 0;
   if (q >= a.nq) return;  // (wave-uniform)
   const int D = 64 * a.ds;
   const float x0 = lane < D ? a.query[(int64_t)lane * a.nq + q] : 0.f;
@@ -303,7 +362,7 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
   const float tau = a.k > 0 ? a.seed_vals[(int64_t)q * a.k + a.k - 1] : (a.thr_k > 0 ? 0.f : a.thr_in[q]);
   const int eq = exp_of_bits(mb);
   const bool flagged = a.k > 0 && a.flags[q] == a.epoch;
-  const bool scalable = a.params[2] != 0.f && mb != 0u && mb <= kMaxFiniteBits && eq >= -kCellMaxExp &&
+  const bool scalable = a.kparams[2] != 0.f && mb != 0u && mb <= kMaxFiniteBits && eq >= -kCellMaxExp &&
                         eq <= kCellMaxExp && q2 <= 3e38f;
   const bool tau_ok = tau == tau && tau != INFINITY;  // (-inf: fewer than k seeds -- everything is admitted)
   const bool active = !flagged && scalable && tau_ok && !bad_cell;
@@ -315,7 +374,7 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
     }
     return;
   }
-  const float B = sqrtf(q2) * 1.000001f + sqrtf(a.params[1]) * 1.000001f;
+  const float B = sqrtf(q2) * 1.000001f + sqrtf(a.kparams[1]) * 1.000001f;
   const float delta = a.rel * (B * B);
   if (lane == 0) {
     // the candidate kernel's threshold: a row passes when fl(a - |q|^2) >= tau - delta, tested as a >= the fold
@@ -372,20 +431,31 @@ __device__ __forceinline__ void for_slice_pairs(const CellArgs& a, int q0, F&& f
     if (lp.listed) f(q, p, lp.cell);
   }
 }
-// the slice's pairs per cell, in the workgroup's LDS histogram (n_cells ints, n_cells <= kCellLdsCells)
+// the slice's pairs per cell, in the workgroup's LDS histogram (n_cells ints, n_cells <= kCellLdsCells).
+// TWO: the threshold form's one walk -- a second histogram behind the first counts the pairs with p < a.p_a, pass A's
+// (2 n_cells ints, n_cells <= kCellLdsCells / 2)
+template <bool TWO>
 __device__ __forceinline__ void count_slice(const CellArgs& a, int q0, int* cell_h) {
-  for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) cell_h[c] = 0;
+  for (int c = (int)threadIdx.x; c < (TWO ? 2 : 1) * a.n_cells; c += kCellSliceThreads) cell_h[c] = 0;
   __syncthreads();
-  for_slice_pairs(a, q0, [&](int, int, int c) { atomicAdd(&cell_h[c], 1); });
+  for_slice_pairs(a, q0, [&](int, int p, int c) {
+    atomicAdd(&cell_h[c], 1);
+    if (TWO && p < a.p_a) atomicAdd(&cell_h[a.n_cells + c], 1);
+  });
   __syncthreads();
 }
 
+template <bool TWO>
 __global__ __launch_bounds__(kCellSliceThreads) void cell_count_kernel(CellArgs a) {
   extern __shared__ int cell_h[];
-  count_slice(a, (int)blockIdx.x * kCellSlice, cell_h);
+  count_slice<TWO>(a, (int)blockIdx.x * kCellSlice, cell_h);
   for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) {
     const int h = cell_h[c];
     if (h) atomicAdd(&a.hist[c], h);
+    if constexpr (TWO) {
+      const int ha = cell_h[a.n_cells + c];
+      if (ha) atomicAdd(&a.hist2[c], ha);
+    }
   }
 }
 
@@ -402,9 +472,15 @@ __global__ __launch_bounds__(256) void cell_count_wide_kernel(CellArgs a) {
   }
 }
 
+// (the one walk: a second block does the same for pass A's view)
 __global__ __launch_bounds__(1024) void cell_scan_kernel(CellArgs a) {
   __shared__ int sp[2][1024], sb[2][1024];
   const int tid = (int)threadIdx.x;
+  if (blockIdx.x == 1) {
+    a.hist = a.va.hist;
+    a.cell_off = a.va.cell_off;
+    a.blk_off = a.va.blk_off;
+  }
   const int per = (a.n_cells + 1023) / 1024;
   const int lo = tid * per < a.n_cells ? tid * per : a.n_cells;
   const int hi = lo + per < a.n_cells ? lo + per : a.n_cells;
@@ -442,26 +518,34 @@ __global__ __launch_bounds__(1024) void cell_scan_kernel(CellArgs a) {
 }
 
 // the pair that takes a cell's first position writes the cell's extent (every query lists it with the same)
-__device__ __forceinline__ void place_pair(const CellArgs& a, int q, int p, int c, int pos) {
-  a.pairs[pos] = q;
-  if (pos == a.cell_off[c]) {
+__device__ __forceinline__ void place_pair(const CellArgs& a, const CellView& v, int q, int p, int c, int pos) {
+  v.pairs[pos] = q;
+  if (pos == v.cell_off[c]) {
     const int64_t o = (int64_t)q * a.max_nprobe + p;
-    a.cell_st[c] = (int)a.cell_start[o];
-    a.cell_sz[c] = (int)a.cell_size[o];
+    v.cell_st[c] = (int)a.cell_start[o];
+    v.cell_sz[c] = (int)a.cell_size[o];
   }
 }
 
+template <bool TWO>
 __global__ __launch_bounds__(kCellSliceThreads) void cell_scatter_kernel(CellArgs a) {
   extern __shared__ int cell_h[];
   const int q0 = (int)blockIdx.x * kCellSlice;
-  count_slice(a, q0, cell_h);
+  count_slice<TWO>(a, q0, cell_h);
   // one returning atomic per cell the slice lists: its h consecutive positions, the first of them left in LDS
   for (int c = (int)threadIdx.x; c < a.n_cells; c += kCellSliceThreads) {
     const int h = cell_h[c];
     if (h) cell_h[c] = atomicAdd(&a.hist[c], h);
+    if constexpr (TWO) {
+      const int ha = cell_h[a.n_cells + c];
+      if (ha) cell_h[a.n_cells + c] = atomicAdd(&a.hist2[c], ha);
+    }
   }
   __syncthreads();
-  for_slice_pairs(a, q0, [&](int q, int p, int c) { place_pair(a, q, p, c, atomicAdd(&cell_h[c], 1)); });
+  for_slice_pairs(a, q0, [&](int q, int p, int c) {
+    place_pair(a, cell_view(a), q, p, c, atomicAdd(&cell_h[c], 1));
+    if (TWO && p < a.p_a) place_pair(a, a.va, q, p, c, atomicAdd(&cell_h[a.n_cells + c], 1));  // (pass A's view)
+  });
 }
 
 __global__ __launch_bounds__(256) void cell_scatter_wide_kernel(CellArgs a) {
@@ -472,7 +556,7 @@ __global__ __launch_bounds__(256) void cell_scatter_wide_kernel(CellArgs a) {
   const int n_probe = cell_n_probe(a, q);
   for (int p = a.p0 + lane; p < n_probe; p += 64) {
     const ListedProbe lp = listed_probe(a, q, p);
-    if (lp.listed) place_pair(a, q, p, lp.cell, atomicAdd(&a.hist[lp.cell], 1));
+    if (lp.listed) place_pair(a, cell_view(a), q, p, lp.cell, atomicAdd(&a.hist[lp.cell], 1));
   }
 }
 
@@ -502,19 +586,47 @@ __device__ __forceinline__ unsigned pack_f16x2(_Float16 lo, _Float16 hi) {
 __device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
 __device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
 
+// The split codebook as a candidate workgroup keeps it in LDS: entry (j, c) -> the fp16 pieces of s_x c_jc.  DS = 2:
+// two dwords (h0 h1, l0 l1); DS = 1: one (h l).  One definition for the per-call staging and the kept image
+template <int DS>
+__device__ __forceinline__ void book_entry(const float* __restrict__ codebook, float sx, int i, unsigned* book) {
+  const int j = i >> 8, c = i & 255;
+  _Float16 h[DS], l[DS];
+#pragma unroll
+  for (int e = 0; e < DS; ++e) {
+    const float ys = codebook[(j * DS + e) * 256 + c] * sx;
+    h[e] = (_Float16)ys;
+    l[e] = (_Float16)(ys - (float)h[e]);
+  }
+  if constexpr (DS == 2) {
+    book[2 * i] = pack_f16x2(h[0], h[1]);
+    book[2 * i + 1] = pack_f16x2(l[0], l[1]);
+  } else {
+    book[i] = pack_f16x2(h[0], l[0]);
+  }
+}
+// the kept state's codebook image: a.book in global memory, what book_entry leaves in LDS
+template <int DS>
+__global__ __launch_bounds__(256) void cell_book_kernel(CellArgs a) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);  // (the launch: 64 blocks, one thread per entry)
+  book_entry<DS>(a.codebook, a.kparams[3], i, a.book);
+}
+
 // The slot norms of a call: norm[slot] = |x'|^2 / s_x^2 of every slot of a listed cell, NaN for a tombstone -- the value
 // cell_cand_kernel<DS, false> forms per (cell, block) in its tile loop, here once per slot, with the same bits: per half
 // (components [16 s + 8 half, + 8), s ascending) the chain x2 = fma(v, v, x2) over v = fp32(hi piece) + fp32(lo piece),
 // then half 0 + half 1, then x inv_sx2.  The sums v do not depend on the slot, so the staging forms them once per entry:
 // the book in LDS is [j][c] -> DS fp32 sums (128 KiB at ds = 2).  One workgroup per CU at most, cells dealt round robin,
 // a thread per slot: its 16 code dwords are coalesced over the slots of the cell.
-template <int DS>
+// ALL: the kept state's norms -- every slot address in [0, n_slots), no cell structure: the bytes of a slot outside any
+// cell decode to some value nobody reads.  The same chain per slot, so the same bits for every slot of a cell.
+template <int DS, bool ALL = false>
 __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
   constexpr int KS = 4 * DS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sums = reinterpret_cast<float*>(smem);  // [j][c][DS]
   const int tid = (int)threadIdx.x;
-  const float sx = a.params[3];
+  const float sx = a.kparams[3];
   const float inv_sx = 1.f / sx;
   const float inv_sx2 = inv_sx * inv_sx;
   for (int i = tid; i < 64 * 256; i += 512) {  // entry (j, c)
@@ -528,11 +640,20 @@ __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
     }
   }
   __syncthreads();
-  for (int c = (int)blockIdx.x; c < a.n_cells; c += (int)gridDim.x) {
-    if (a.cell_off[c + 1] == a.cell_off[c]) continue;  // not listed: its extent was never written
-    const int64_t st = a.cell_st[c];
-    int sz = a.cell_sz[c];
-    if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (the candidate kernel's check)
+  // ALL: one round of "cells" of 512 consecutive slot addresses per workgroup, n_slots < 2^31 (the entry points)
+  const int n_units = ALL ? (int)((a.n_slots + 511) / 512) : a.n_cells;
+  for (int c = (int)blockIdx.x; c < n_units; c += (int)gridDim.x) {
+    int64_t st;
+    int sz;
+    if constexpr (ALL) {
+      st = (int64_t)c * 512;
+      sz = a.n_slots - st < 512 ? (int)(a.n_slots - st) : 512;
+    } else {
+      if (a.cell_off[c + 1] == a.cell_off[c]) continue;  // not listed: its extent was never written
+      st = a.cell_st[c];
+      sz = a.cell_sz[c];
+      if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (the candidate kernel's check)
+    }
     for (int r = tid; r < sz; r += 512) {
       const int64_t slot = st + r;
       const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(a.codes) + slot;
@@ -597,6 +718,7 @@ template <int DS, bool NORMS, bool EUCLID, bool MAXIMA = false>
 __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellArgs a) {
   static_assert(!MAXIMA || NORMS, "pass A reads the slot norms");
   using T = CellBook<DS>;
+  constexpr int S = cell_pieces(MAXIMA);
   constexpr int KS = T::KS;
   constexpr int kDepth = T::kDepth;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -607,26 +729,16 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
   int* work = reinterpret_cast<int*>(a.params) + 8 + a.work;
   const int n_blocks = a.blk_off[a.n_cells];
   const int col = lane & 31, half = lane >> 5;
-  const float sx = a.params[3];
+  const float sx = a.kparams[3];
   const float inv_sx = 1.f / sx;  // (a power of two: exact)
   const float inv_sx2 = inv_sx * inv_sx;
   // the tombstone bytes, or any readable bytes of one per slot when the index keeps none (the value is not used then)
   const uint8_t* __restrict__ emp = a.is_empty ? a.is_empty : a.codes;
-  for (int i = tid; i < 64 * 256; i += T::kThreads) {  // entry (j, c)
-    const int j = i >> 8, c = i & 255;
-    _Float16 h[DS], l[DS];
-#pragma unroll
-    for (int e = 0; e < DS; ++e) {
-      const float ys = a.codebook[(j * DS + e) * 256 + c] * sx;
-      h[e] = (_Float16)ys;
-      l[e] = (_Float16)(ys - (float)h[e]);
-    }
-    if constexpr (DS == 2) {
-      book[2 * i] = pack_f16x2(h[0], h[1]);
-      book[2 * i + 1] = pack_f16x2(l[0], l[1]);
-    } else {
-      book[i] = pack_f16x2(h[0], l[0]);
-    }
+  if (a.book) {  // the kept image: 16 bytes per thread and round, no conversion
+    const u32x4* __restrict__ img = reinterpret_cast<const u32x4*>(a.book);
+    for (int i = tid; i < (int)(T::kBook / 16); i += T::kThreads) reinterpret_cast<u32x4*>(book)[i] = img[i];
+  } else {
+    for (int i = tid; i < 64 * 256; i += T::kThreads) book_entry<DS>(a.codebook, sx, i, book);  // entry (j, c)
   }
   __syncthreads();
   const int64_t cap = (int64_t)a.chunks * 64;
@@ -635,6 +747,9 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
     int b = 0;
     if (lane == 0) b = atomicAdd(work, 1);
     b = __builtin_amdgcn_readfirstlane(b);
+    // draw w is piece w % S of block w / S (S = 1: the block)
+    const int piece = S > 1 ? b % S : 0;
+    if constexpr (S > 1) b /= S;
     if (b >= n_blocks) break;
     // the block's cell: blk_off[c] <= b < blk_off[c + 1]
     int lo = 0, hi = a.n_cells;
@@ -650,6 +765,16 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
     int sz = a.cell_sz[c];
     if (st < 0 || sz < 0 || st + sz > a.n_slots) sz = 0;  // (an extent outside the storage is never read)
     if (sz == 0) continue;
+    // the piece's rows [r_lo, r_hi): whole tiles of the cell's ceil(sz / 32), the last one cut at the size.  A cell of
+    // fewer tiles than pieces leaves some of them empty: the draw, and nothing else
+    int r_lo = 0, r_hi = sz;
+    if constexpr (S > 1) {
+      const int nt = (sz + 31) >> 5;
+      r_lo = (piece * nt / S) << 5;
+      r_hi = ((piece + 1) * nt / S) << 5;
+      if (r_lo == r_hi) continue;
+      if (r_hi > sz) r_hi = sz;
+    }
     // this lane's query: pieces of s_q q for the B operand, threshold and scales
     const bool qvalid = col < nqs;
     const int q = qvalid ? a.pairs[first + col] : 0;
@@ -708,13 +833,13 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
     int me = (int)cap;
     unsigned* __restrict__ mkeys = a.keys + (int64_t)q * cap;
     if constexpr (MAXIMA) {
-      if (qvalid) me = atomicAdd(&a.cnt[q], ((sz + 31) >> 5) * (16 / kCellThrGroup));
+      if (qvalid) me = atomicAdd(&a.cnt[q], ((r_hi - r_lo + 31) >> 5) * (16 / kCellThrGroup));
     }
     uint32_t w[8], wn[8];
     unsigned aux = 0u, aux_n = 0u;
-    load_tile(0, w, aux);
-    for (int r0 = 0; r0 < sz; r0 += 32) {
-      load_tile(r0 + 32, wn, aux_n);  // (the last tile: the cell's last row again)
+    load_tile(r_lo, w, aux);
+    for (int r0 = r_lo; r0 < r_hi; r0 += 32) {
+      load_tile(r0 + 32, wn, aux_n);  // (a piece's last tile: the next piece's first; the cell's: its last row again)
       const bool rv = r0 + col < sz;
       // (opaque: a load whose only use is a select is sunk under the select's condition, and waited for there)
       asm volatile("" : "+v"(aux));
@@ -893,9 +1018,32 @@ static int cell_cus() {
   return n_cus;
 }
 
-static int launch_cell_head(const CellArgs& a, hipStream_t st) {
+// the kept state (a.kparams, a.book, a.norm of cell_use_kept): parameters, codebook image, a norm per slot address
+static int launch_cell_kept_build(const CellArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(cell_prep_kernel, dim3(1), dim3(1024), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_prep_kernel");
+  if (a.ds == 1)
+    hipLaunchKernelGGL(cell_book_kernel<1>, dim3(64), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(cell_book_kernel<2>, dim3(64), dim3(256), 0, st, a);
+  TPQ_LAUNCH_CHECK("cell_book_kernel");
+  const int64_t units = (a.n_slots + 511) / 512;
+  if (units < 1) return TPQ_OK;
+  const int n_cus = cell_cus();
+  const dim3 grid((unsigned)(units < n_cus ? units : n_cus)), wg(512);
+  return a.ds == 1 ? launch_with_lds(cell_norm_kernel<1, true>, "cell_norm_kernel", grid, wg, 64 * 256 * 4, st, a)
+                   : launch_with_lds(cell_norm_kernel<2, true>, "cell_norm_kernel", grid, wg, 64 * 256 * 8, st, a);
+}
+
+// the head of a call: what depends on the index alone -- per call (cell_prep_kernel), or the kept state, built here when
+// it is not valid yet and otherwise left alone --, then the seed kernel
+static int launch_cell_head(const CellArgs& a, hipStream_t st) {
+  if (!a.book) {
+    hipLaunchKernelGGL(cell_prep_kernel, dim3(1), dim3(1024), 0, st, a);
+    TPQ_LAUNCH_CHECK("cell_prep_kernel");
+  } else if (a.kept_build) {
+    if (int rc = launch_cell_kept_build(a, st)) return rc;
+  }
   hipLaunchKernelGGL(cell_seed_kernel, dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_seed_kernel");
   return TPQ_OK;
@@ -903,13 +1051,25 @@ static int launch_cell_head(const CellArgs& a, hipStream_t st) {
 
 // the inversion of the pairs (q, p), p0 <= p < p_hi, into a's hist / cell_off / blk_off / cell_st / cell_sz / pairs:
 // a workgroup per slice of kCellSlice queries over an LDS histogram, while one fits
+// a.p_a > 0 (n_cells <= kCellLdsCells / 2: the caller's): the one walk, both views from these three launches
+static std::atomic<long long> g_cell_inversions{0};  // diagnostics: count / scan / scatter chains launched so far
 static int launch_cell_inversion(const CellArgs& a, hipStream_t st) {
+  g_cell_inversions.fetch_add(1);
   const dim3 per_query((unsigned)((a.nq + 3) / 4));
   const bool lds_hist = a.n_cells <= kCellLdsCells;
   const dim3 per_slice((unsigned)((a.nq + kCellSlice - 1) / kCellSlice)), slice_wg(kCellSliceThreads);
   const size_t hist_lds = (size_t)a.n_cells * sizeof(int);  // (<= 64 KiB: no attribute to raise)
+  if (a.p_a > 0) {
+    hipLaunchKernelGGL(cell_count_kernel<true>, per_slice, slice_wg, 2 * hist_lds, st, a);
+    TPQ_LAUNCH_CHECK("cell_count_kernel");
+    hipLaunchKernelGGL(cell_scan_kernel, dim3(2), dim3(1024), 0, st, a);
+    TPQ_LAUNCH_CHECK("cell_scan_kernel");
+    hipLaunchKernelGGL(cell_scatter_kernel<true>, per_slice, slice_wg, 2 * hist_lds, st, a);
+    TPQ_LAUNCH_CHECK("cell_scatter_kernel");
+    return TPQ_OK;
+  }
   if (lds_hist) {
-    hipLaunchKernelGGL(cell_count_kernel, per_slice, slice_wg, hist_lds, st, a);
+    hipLaunchKernelGGL(cell_count_kernel<false>, per_slice, slice_wg, hist_lds, st, a);
     TPQ_LAUNCH_CHECK("cell_count_kernel");
   } else {
     hipLaunchKernelGGL(cell_count_wide_kernel, per_query, dim3(256), 0, st, a);
@@ -918,7 +1078,7 @@ static int launch_cell_inversion(const CellArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, a);
   TPQ_LAUNCH_CHECK("cell_scan_kernel");
   if (lds_hist) {
-    hipLaunchKernelGGL(cell_scatter_kernel, per_slice, slice_wg, hist_lds, st, a);
+    hipLaunchKernelGGL(cell_scatter_kernel<false>, per_slice, slice_wg, hist_lds, st, a);
     TPQ_LAUNCH_CHECK("cell_scatter_kernel");
   } else {
     hipLaunchKernelGGL(cell_scatter_wide_kernel, per_query, dim3(256), 0, st, a);
@@ -934,26 +1094,35 @@ static int launch_cell_norms(const CellArgs& a, int n_cus, hipStream_t st) {
                    : launch_with_lds(cell_norm_kernel<2>, "cell_norm_kernel", norm_grid, wg, 64 * 256 * 8, st, a);
 }
 
-// one workgroup of eight waves per CU, fewer when the call cannot list that many (cell, group) blocks: at most one
-// per listed cell plus one per full group of pairs; 0: nothing can be listed
-static unsigned cell_cand_grid(const CellArgs& a, int n_cus) {
+// one workgroup of eight waves per CU, fewer when the call cannot list that many pieces of (cell, group) blocks: at
+// most one block per listed cell plus one per full group of pairs; 0: nothing can be listed
+static unsigned cell_cand_grid(const CellArgs& a, int n_cus, bool maxima = false) {
   const int64_t np = (int64_t)a.nq * (a.p_hi > a.p0 ? a.p_hi - a.p0 : 0);
   int64_t blocks = (int64_t)a.n_cells + np / kCellGroup;
   if (blocks > np) blocks = np;
   if (blocks < 1) return 0;
-  blocks = (blocks + kCellWaves - 1) / kCellWaves;
+  blocks = (blocks * cell_pieces(maxima) + kCellWaves - 1) / kCellWaves;
   return (unsigned)(blocks > n_cus ? n_cus : blocks);
+}
+
+// the candidate kernel's draw counter is an int: blocks x pieces, plus one failed draw per wave of the launch
+static bool cell_draws_fit(const CellArgs& a) {
+  const int64_t blocks = (int64_t)a.n_cells + (int64_t)a.nq * a.max_nprobe / kCellGroup;
+  const int s = kCellPiecesA > kCellPiecesB ? kCellPiecesA : kCellPiecesB;
+  return blocks * s + 65536 < 0x7fffffffLL;
 }
 
 int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   if (a.nq <= 0) return TPQ_OK;
+  TPQ_REQUIRE(cell_draws_fit(a), "ivfpq_scan (cell-major): more pieces of blocks than the draw counter holds");
   if (int rc = launch_cell_head(a, st)) return rc;
   if (a.p_hi <= a.p0) return TPQ_OK;
   if (int rc = launch_cell_inversion(a, st)) return rc;
   const int n_cus = cell_cus();
   const dim3 grid(cell_cand_grid(a, n_cus)), cand_wg(64 * kCellWaves);
   if (a.norm) {
-    if (int rc = launch_cell_norms(a, n_cus, st)) return rc;
+    if (!a.book)  // (a kept state holds the norms of every slot)
+      if (int rc = launch_cell_norms(a, n_cus, st)) return rc;
     return a.ds == 1 ? launch_cand<1, true>(a, grid, cand_wg, st) : launch_cand<2, true>(a, grid, cand_wg, st);
   }
   return a.ds == 1 ? launch_cand<1, false>(a, grid, cand_wg, st) : launch_cand<2, false>(a, grid, cand_wg, st);
@@ -981,6 +1150,7 @@ int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t
   if (a.nq <= 0) return TPQ_OK;
   TPQ_REQUIRE(a.norm && a.k == 0 && a.thr_k >= 1 && a.p0 == 0 && a.p_hi == a.max_nprobe && a.chunks <= 16,
               "ivfpq_scan (cell threshold): arguments outside the form");
+  TPQ_REQUIRE(cell_draws_fit(a), "ivfpq_scan (cell threshold): more pieces of blocks than the draw counter holds");
   // pass B's view: every probe, its pairs in the form's own array; pass A's: the first kCellThrProbes, its own inversion
   // arrays and block counter.  The cells A lists are among B's (the same rule over a prefix of the same probes), so
   // the slot norms of B's cells cover them
@@ -996,13 +1166,22 @@ int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t
   pa.hist2 = nullptr;
   pa.work = 1;
   if (int rc = launch_cell_head(b, st)) return rc;
+  // one walk for both views while two LDS histograms fit; beyond, pass A's own count / scan / scatter as before
+  const bool one_walk = a.n_cells <= kCellLdsCells / 2;
+  if (one_walk) {
+    b.p_a = pa.p_hi;
+    b.va = CellView{t.hist, t.cell_off, t.blk_off, t.cell_st, t.cell_sz, t.pairs};
+  }
   if (int rc = launch_cell_inversion(b, st)) return rc;
+  b.p_a = 0;
   const int n_cus = cell_cus();
-  if (int rc = launch_cell_norms(b, n_cus, st)) return rc;
-  if (int rc = launch_cell_inversion(pa, st)) return rc;
+  if (!b.book)  // (a kept state holds the norms of every slot)
+    if (int rc = launch_cell_norms(b, n_cus, st)) return rc;
+  if (!one_walk)
+    if (int rc = launch_cell_inversion(pa, st)) return rc;
   const dim3 cand_wg(64 * kCellWaves);
-  if (int rc = a.ds == 1 ? launch_cand<1, true, true>(pa, dim3(cell_cand_grid(pa, n_cus)), cand_wg, st)
-                         : launch_cand<2, true, true>(pa, dim3(cell_cand_grid(pa, n_cus)), cand_wg, st))
+  if (int rc = a.ds == 1 ? launch_cand<1, true, true>(pa, dim3(cell_cand_grid(pa, n_cus, true)), cand_wg, st)
+                         : launch_cand<2, true, true>(pa, dim3(cell_cand_grid(pa, n_cus, true)), cand_wg, st))
     return rc;
   const dim3 per_query((unsigned)((a.nq + 3) / 4));
   if (a.chunks <= 8)
@@ -1054,6 +1233,8 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
   a.cnt = out_count;
   return launch_cell_candidates(a, reinterpret_cast<hipStream_t>(stream));
 }
+
+extern "C" long long tpq_ivfpq_scan_cell_inversions(void) { return g_cell_inversions.load(); }
 
 extern "C" float tpq_ivfpq_cell_fold_threshold(float threshold, float q2) { return cell_fold_threshold(threshold, q2); }
 

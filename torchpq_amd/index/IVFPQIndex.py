@@ -12,7 +12,7 @@ from .. import util
 from ..codec import PQCodec
 from ..container import CellContainer
 from ..fn import IVFPQTopk
-from ..kernels import PACKED_M, IVFPQFilteredTopkHip, IVFPQRangeHip, ResidualPart1Hip, ResidualSlotTermsHip
+from ..kernels import PACKED_M, CellKeptState, IVFPQFilteredTopkHip, IVFPQRangeHip, ResidualPart1Hip, ResidualSlotTermsHip
 from ._coarse import CoarseProbeMixin
 from ._filter import IdFilter, filtered_search_batches
 from ._range import range_search_batches
@@ -31,6 +31,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     fused_lut_max_subvector = 4
     use_cell_major = True
     use_cell_threshold = True
+    use_cell_kept = True
 
     def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None,
                  expand_step_size=128, expand_mode="double", distance="euclidean",
@@ -69,6 +70,12 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         # ... and that form may take its threshold from the candidate kernel's group maxima instead of a query-major pass
         # over the first probes (the library's rule decides, IVFPQTopkHip.last_cell_threshold() tells)
         self.use_cell_threshold = True
+        # ... and keeps what it derives from codes, codebook and tombstones alone -- scale, split codebook, slot norms --
+        # across searches, rebuilt after add / remove / growth / load_state_dict / a write to the codebook
+        # (IVFPQTopkHip.last_cell_kept tells; False: derived again in every call)
+        self.use_cell_kept = True
+        self._cell_kept = None           # kernels.CellKeptState, keyed on what it was derived from
+        self._cell_kept_built = 0        # builds of the states dropped so far
 
         self._init_coarse(n_cells, verbose)
         self.pq_codec = PQCodec(d_vector=d_vector, n_subvectors=n_subvectors, n_clusters=256,
@@ -173,9 +180,42 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     pq_codec_tolerance = _codec_knob("pq_codec", "tol", False)
     del _codec_knob
 
+    def _cell_kept_state(self, n_bytes, device):
+        """the kept state of the cell-major form for the index as it stands: the one in hand while codes, codebook and
+        tombstones are what it was derived from (version counters and the buffers' identity), else a new, not yet valid
+        one, which the calling search builds.  None inside a stream capture that finds no valid state."""
+        def ident(t):
+            return None if t is None else (t.data_ptr(), tuple(t.shape), util.tensor_version(t), str(t.device))
+        key = (self._codes_version, bool(self._has_holes), ident(self.pq_codec.codebook), ident(self._storage),
+               ident(self._is_empty))
+        st = self._cell_kept
+        if st is not None and st.key == key and st.buf.numel() >= n_bytes and st.buf.device == torch.device(device):
+            return st
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        self._drop_cell_kept()
+        self._cell_kept = CellKeptState(n_bytes, device, key)
+        return self._cell_kept
+
+    def _drop_cell_kept(self):
+        if self._cell_kept is not None:
+            self._cell_kept_built += self._cell_kept.builds
+        self._cell_kept = None
+
+    @property
+    def cell_kept_builds(self):
+        """diagnostics: how often a search built the kept state so far"""
+        return self._cell_kept_built + (0 if self._cell_kept is None else self._cell_kept.builds)
+
+    def to(self, *args, **kwargs):
+        if getattr(self, "_cell_kept", None) is not None:   # (a state describes buffers of the device it is on)
+            self._drop_cell_kept()
+        return super().to(*args, **kwargs)
+
     def _after_load_state_dict(self):
         self.to(self.device)
         self._drop_part2()
+        self._drop_cell_kept()
         super()._after_load_state_dict()
 
     # ---- train / encode / add (reference :234-364) ------------------------------------------------
@@ -299,7 +339,8 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
             found = self._ivfpq_topk.topk_fused(
                 packed=self._scan_layout(), query=x, codebook=self.pq_codec.codebook, k=k, distance=self.distance,
                 slots_hint=slots_hint, cells=cells if self.use_cell_major else None, n_cells=self.n_cells,
-                cell_threshold=self.use_cell_threshold, **lists)
+                cell_threshold=self.use_cell_threshold,
+                kept=self._cell_kept_state if self.use_cell_kept and self.use_cell_major else None, **lists)
         else:
             found = self._ivfpq_topk.topk(
                 packed=self._scan_layout(), precomputed=self.pq_codec.precompute_adc(x), k=k,

@@ -23,13 +23,14 @@ class GraphedSearch:
     graph's static outputs -- clone them if they must survive the next call."""
 
     KNOBS = ("n_probe", "use_smart_probing", "_smart_probing_temperature", "use_packed_layout",
-             "use_fused_lut", "use_cell_major", "use_cell_threshold", "use_fused_probe", "use_cublas", "_use_precomputed", "pq_use_residual",
+             "use_fused_lut", "use_cell_major", "use_cell_threshold", "use_cell_kept", "use_fused_probe", "use_cublas", "_use_precomputed", "pq_use_residual",
              "distance", "max_query_batch", "_has_holes", "_codes_version")
 
     @staticmethod
     def _buffers(index):
         """the device buffers a search() reads (None where the index does not have one)"""
         slot = index._slot_terms
+        kept = getattr(index, "_cell_kept", None)
         return {
             "vq_codebook": index.vq_codec.codebook, "pq_codebook": index.pq_codec.codebook,
             "_storage": index._storage, "_packed": index._packed if index._packed_valid else None,
@@ -38,6 +39,8 @@ class GraphedSearch:
             "_part2_by_cell": index._part2_by_cell,
             "slot_term": None if slot is None else slot[1],
             "cell_bound": None if slot is None else slot[2],
+            # the cell-major form's kept state, built by the warm-up searches (never inside the capture)
+            "cell_kept": None if kept is None or not kept.valid else kept.buf,
         }
 
     @classmethod

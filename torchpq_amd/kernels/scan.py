@@ -13,6 +13,34 @@ def packed_chunk_width(m):
     return 16 if m % 16 == 0 else (8 if m % 8 == 0 else 4)
 
 
+class CellKeptState:
+    """The kept state of the cell-major form (csrc/scan_cells.hip, `The kept state`; tpq_ivfpq_search_fused_cells_kept):
+    a caller-owned device buffer with what the form derives from codes, codebook and tombstones alone.  `key` is the
+    owner's description of what it was derived from; the call that finds `valid` False builds the state on its
+    stream, and `ready` -- recorded behind that call -- orders the first use on every other stream.  `builds` counts."""
+
+    def __init__(self, n_bytes, device, key=None):
+        self.buf = torch.empty(n_bytes, device=device, dtype=torch.uint8)
+        self.key = key
+        self.valid = False
+        self.builds = 0
+        self.ready = None
+
+    def before_use(self, device):
+        """orders the current stream behind the build, every time: a wait on an event that has completed, or that the
+        stream is behind already, costs nothing on the device (a capturing stream is not asked to wait: whoever captures
+        has run the warm-up searches and joined their stream, GraphedSearch)"""
+        if self.valid and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(device).wait_event(self.ready)
+
+    def after_build(self, device):
+        stream = torch.cuda.current_stream(device)
+        self.ready = torch.cuda.Event()
+        self.ready.record(stream)
+        self.valid = True
+        self.builds += 1
+
+
 class IVFPQTopkHip:
     """IVF list scan + top-k.  Mirrors IVFPQTopkCuda (kernels/IVFPQTopkCuda.py:9-142);
     ``tpb``/``stack_capacity``/``sm_size`` are accepted for signature compatibility and
@@ -46,6 +74,7 @@ class IVFPQTopkHip:
         self._last_device = None
         self._last_cells = None       # (n_cells, n_slots) when the last call handed over its probed cells
         self._last_withheld = False   # the last call switched the cell-major form's threshold form off
+        self.last_cell_kept = None    # "built" / "reused": what the last call did with a kept state; None: it used none
 
     def _tickets(self, n_query, n_split, device):
         """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
@@ -238,11 +267,11 @@ class IVFPQTopkHip:
         return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
 
     def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed,
-              cells=None, n_cells=0, cell_threshold=True, **route):
+              cells=None, n_cells=0, cell_threshold=True, kept=None, **route):
         """What topk / topk_fused / topk_residual_packed share once their arguments are checked: the outputs, the
         split, the diagnostics, the workspace and the call of `name` -- its own `inputs`, then the arguments every
         scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint; `cells`:
-        it takes the probed cells and their number behind those)."""
+        it takes the probed cells and their number behind those; `kept`: see topk_fused)."""
         n_data, device = data.shape[1], data.device
         n_query, n_probe = cell_start.shape
         values, address, ids = alloc_topk(n_query, k, device, address2id)
@@ -261,6 +290,15 @@ class IVFPQTopkHip:
             ws_bytes = int(self.workspace_bytes)
         self.last_workspace_bytes, self._last_device = ws_bytes, device
         ws = torch.empty(max(ws_bytes, 1), device=device, dtype=torch.uint8)
+        # the kept state: asked for only when the library's own rule takes the form with slot norms for this call (a
+        # state is 4 bytes per slot), and never built inside a capture: such a call takes the per-call path
+        self.last_cell_kept = None
+        if kept is not None and cells is not None and self.cell_norms(ws_bytes, n_cells, n_data):
+            kept = kept(lib.tpq_ivfpq_cell_kept_bytes(int(n_data), int(route["ds"])), device)
+            if kept is not None and not kept.valid and torch.cuda.is_current_stream_capturing():
+                kept = None
+        else:
+            kept = None
         ev = None
         if self.record_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -272,6 +310,10 @@ class IVFPQTopkHip:
                 tail = (ptr(tickets), int(slots_hint or 0))
                 if cells is not None:
                     tail += (ptr(cells), int(n_cells))
+                if kept is not None:
+                    name = "tpq_ivfpq_search_fused_cells_kept"
+                    kept.before_use(device)
+                    tail += (ptr(kept.buf), kept.buf.numel(), int(kept.valid))
             # (the switch is the library's, process-wide and read on the host during the call: set for this call alone)
             before = lib.tpq_ivfpq_scan_use_cell_threshold(1 if cell_threshold else 0)
             try:
@@ -282,6 +324,10 @@ class IVFPQTopkHip:
             if rc != 0 and ticketed:
                 self._drop_tickets(device)
             check(rc, name)
+            if kept is not None:
+                self.last_cell_kept = "reused" if kept.valid else "built"
+                if not kept.valid:
+                    kept.after_build(device)
         if self.keep_workspace:
             self.last_workspace = ws
         if ev is not None:
@@ -330,13 +376,17 @@ class IVFPQTopkHip:
 
     def topk_fused(self, data, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
                    n_candidates, distance="euclidean", packed=None, address2id=None, n_split=None,
-                   slots_hint=None, cells=None, n_cells=0, cell_threshold=True):
+                   slots_hint=None, cells=None, n_cells=0, cell_threshold=True, kept=None):
         """precompute_adc + topk in one pass: the LUT is built inside the scan workgroups
         (query [d, n_query] f32, codebook [m, ds, 256] f32); results identical to
         topk(precomputed=AdcLutHip()(query, codebook)).  `cells` [n_query, max_n_probe] int64 -- the probed cells
         behind cell_start / cell_size, ids in [0, n_cells) -- lets a cell-dense large batch at m = 64 take the
         cell-major form (tpq_ivfpq_search_fused_cells; `last_cell_major()`): same results.  `cell_threshold=False`
-        keeps that form to its seeded variant (tpq_ivfpq_scan_use_cell_threshold; `last_cell_threshold()`)."""
+        keeps that form to its seeded variant (tpq_ivfpq_scan_use_cell_threshold; `last_cell_threshold()`).
+        `kept`: a callable (n_bytes, device) -> CellKeptState or None, asked only when the call takes that form with slot
+        norms: the state of what the form derives from `data`, `codebook` and `is_empty` alone, built by the first call
+        that finds it not valid and read by the others (tpq_ivfpq_search_fused_cells_kept; `last_cell_kept`: "built",
+        "reused" or None).  The caller answers for the state matching those three tensors."""
         n_data = data.shape[1]
         n_query, n_probe = cell_start.shape
         m, ds, kk = codebook.shape
@@ -360,7 +410,7 @@ class IVFPQTopkHip:
             require_gpu(cells)
             return self._scan("tpq_ivfpq_search_fused_cells", inputs, data, cell_start, address2id, n_candidates,
                               n_split, slots_hint, packed, True, cells=cells, n_cells=n_cells, cell_threshold=cell_threshold,
-                              ds=ds, has_lut=False)
+                              kept=kept, ds=ds, has_lut=False)
         return self._scan("tpq_ivfpq_search_fused_tickets", inputs, data, cell_start, address2id, n_candidates,
                           n_split, slots_hint, packed, True, ds=ds, has_lut=False)
 
