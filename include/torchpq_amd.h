@@ -991,6 +991,91 @@ int tpq_ivfpq4_scan_filtered_residual_topk(const uint8_t* codes, const float* qu
                                            void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFPQ4Index range search: every stored 4-bit code of the probed cells whose value reaches a threshold, optionally
+ * among the slots a filter allows; plain codes (tpq_ivfpq4_range_count / _fill) and residual codes
+ * (tpq_ivfpq4_range_residual_count / _fill).  No reference counterpart.
+ *
+ * codes, query, codebook, (centroids, cells, n_cells,) is_empty, cell_start, cell_size, n_probe_list, n_slots, m, ds,
+ * nq, max_nprobe, metric, n_split: as tpq_ivfpq4_scan_topk / tpq_ivfpq4_scan_residual_topk.
+ *
+ * Candidates of a query: exactly those of tpq_ivfpq4_scan_topk / _residual_topk -- its first n_probe_list[q] probes
+ *            (clamped to [0, max_nprobe]), a probe whose start equals the previous probe's start skipped, the slots
+ *            inside [start, start + size) and inside [0, n_slots) (a cell that leaves the storage is cut) that are not
+ *            tombstoned (is_empty); for residual codes a slot of two overlapping cells is a candidate once per probe
+ *            that scans it.
+ * Value      that of tpq_ivfpq4_scan_topk / _residual_topk: the table entries defined there (the workgroup builds
+ *            them, for residual codes from the probed cell's centroid; a cell index outside [0, n_cells) is clamped
+ *            into the range), then v = 0.f; for j = 0 ... m - 1 ascending: v = v + table[j][code_j], one fp32 add per
+ *            step.  Nothing is added to it: a range hit and a top-k result of one slot under one probe carry the same
+ *            bits.
+ * Hit        a candidate with value >= threshold[q] (threshold f32 [nq]).  A NaN value is never a hit, a NaN
+ *            threshold gives no hits, -inf gives every candidate whose value is not NaN.
+ * Filter     optional, the format of tpq_ivfpq4_scan_filtered_topk: filter_bits u32 [n_filters][filter_stride], bit
+ *            (s & 31) of word (s >> 5) of row f says that slot address s is allowed by filter f; filter_of_query i32
+ *            [nq] names the row of every query, NULL: every query uses row 0.  filter_bits == NULL: no filter, the
+ *            other three filter arguments are ignored.  With a filter a candidate must also have its bit set in the
+ *            query's row; a row outside [0, n_filters) gives that query no hit, and neither the filter nor the codes
+ *            are read for it.  The scan tests a slot's bit before its tombstone byte and before any code word: a
+ *            64-slot tile without an allowed live slot reads no code; other tiles are valued in place.
+ * Order      scan order: probe rank ascending, then address ascending.  Neither the order nor the bits depend on how
+ *            the work is cut (n_split).
+ * Output     lims i64 [nq + 1], lims[0] = 0: the hits of query q are out_vals[lims[q] : lims[q+1]] (f32) and
+ *            out_addr[lims[q] : lims[q+1]] (i64).
+ * A query with a NaN or +-Inf component returns what this definition gives and touches no other query's segment.
+ *
+ * Two passes, no global atomics, no sort, deterministic -- the protocol of tpq_ivfpq_range_count / _fill.
+ *   plain     a query's tiles are cut into n_split parts as in the top-k scan, a part's tiles into eight contiguous
+ *             chunks, one per wave: segment (q * n_split + part) * 8 + wave; tpq_ivfpq4_range_segments(nq, n_split)
+ *             = nq * n_split * 8 segments (0 for nq <= 0 or n_split outside [1, 1024]).
+ *   residual  the table depends on the probed cell: one workgroup per (query, probe rank), the cell's tiles in eight
+ *             contiguous chunks: segment (q * max_nprobe + p) * 8 + wave; tpq_ivfpq4_range_residual_segments(nq,
+ *             max_nprobe) = nq * max_nprobe * 8 segments (0 for nq <= 0 or max_nprobe < 1).  A probe that is not
+ *             scanned has eight zero counts.
+ *   1. the count pass writes the hits of every segment: wave_counts i32 [segments].
+ *   2. THE CALLER turns the counts into exclusive prefix sums: wave_offsets i64 [segments + 1], wave_offsets[0] = 0,
+ *      the last entry the total number of hits, which sizes out_vals / out_addr; lims[q] = wave_offsets[q * (segments
+ *      / nq)].  The library does not do this step and allocates nothing.
+ *   3. the fill pass, with the inputs of the count pass, computes the values again (the same code, the same bits)
+ *      and stores segment s at wave_offsets[s] onwards.  A wave stores nothing at or beyond wave_offsets[s + 1],
+ *      whatever it finds: inputs that changed between the passes lose hits, they do not become a store outside the
+ *      segment.  A segment without hits is not scanned again, a workgroup without hits stages nothing.
+ * m % 8 == 0 in [8, 256], ds >= 1, n_slots < 2^31 - 1, else TPQ_ERR_UNSUPPORTED; an invalid metric, n_split outside
+ * [1, 1024], n_cells < 1 or a null pointer: TPQ_ERR_INVALID_ARGUMENT; with a non-null filter_bits, n_filters >= 1 and
+ * filter_stride >= ceil(n_slots / 32), else TPQ_ERR_INVALID_ARGUMENT.  The workgroup's LDS holds the table (m x 64
+ * bytes), the staged query (m * ds * 4 bytes) and, for plain codes, the probe table: a shape over 160 KiB returns
+ * TPQ_ERR_UNSUPPORTED with a message.  nq == 0 is TPQ_OK without a launch.  Every check comes before the first HIP call.
+ * ------------------------------------------------------------------------- */
+/* TPQ_VERSION is unchanged by these six symbols; a caller that must build against older headers tests this macro. */
+#define TPQ_HAS_IVFPQ4_RANGE 1
+size_t tpq_ivfpq4_range_segments(int nq, int n_split);
+int tpq_ivfpq4_range_count(const uint8_t* codes, const float* query, const float* codebook, const uint8_t* is_empty,
+                           const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                           const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
+                           int64_t filter_stride, const float* threshold, int32_t* wave_counts, int64_t n_slots, int m,
+                           int ds, int nq, int max_nprobe, int metric, int n_split, tpq_stream_t stream);
+int tpq_ivfpq4_range_fill(const uint8_t* codes, const float* query, const float* codebook, const uint8_t* is_empty,
+                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                          const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
+                          int64_t filter_stride, const float* threshold, const int64_t* wave_offsets, float* out_vals,
+                          int64_t* out_addr, int64_t n_slots, int m, int ds, int nq, int max_nprobe, int metric,
+                          int n_split, tpq_stream_t stream);
+size_t tpq_ivfpq4_range_residual_segments(int nq, int max_nprobe);
+int tpq_ivfpq4_range_residual_count(const uint8_t* codes, const float* query, const float* codebook,
+                                    const float* centroids, const int64_t* cells, int n_cells, const uint8_t* is_empty,
+                                    const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                    const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
+                                    int64_t filter_stride, const float* threshold, int32_t* wave_counts,
+                                    int64_t n_slots, int m, int ds, int nq, int max_nprobe, int metric,
+                                    tpq_stream_t stream);
+int tpq_ivfpq4_range_residual_fill(const uint8_t* codes, const float* query, const float* codebook,
+                                   const float* centroids, const int64_t* cells, int n_cells, const uint8_t* is_empty,
+                                   const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                   const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
+                                   int64_t filter_stride, const float* threshold, const int64_t* wave_offsets,
+                                   float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq,
+                                   int max_nprobe, int metric, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FlatIndex fused exact search: the k best stored vectors of every query without a [nq][n_slots] similarity
  * matrix -- a similarity GEMM on the fp32 matrix cores with a top-k epilogue (the semantics of the reference's
  * TopkBMMCuda, torchpq/kernels/TopkBMMCuda.py, which FlatIndex itself does not use).

@@ -123,6 +123,14 @@ SIGNATURES = {
                                            _vp]),
     "tpq_ivfpq4_scan_filtered_residual_topk": (_i, [_vp] * 5 + [_i] + [_vp] * 6 + [_i, _i64, _vp, _vp, _i64, _i, _i,
                                                     _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tpq_ivfpq4_range_segments": (_sz, [_i, _i]),
+    "tpq_ivfpq4_range_count": (_i, [_vp] * 9 + [_i, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "tpq_ivfpq4_range_fill": (_i, [_vp] * 9 + [_i, _i64] + [_vp] * 4 + [_i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "tpq_ivfpq4_range_residual_segments": (_sz, [_i, _i]),
+    "tpq_ivfpq4_range_residual_count": (_i, [_vp] * 5 + [_i] + [_vp] * 6 + [_i, _i64, _vp, _vp, _i64, _i, _i, _i, _i,
+                                             _i, _vp]),
+    "tpq_ivfpq4_range_residual_fill": (_i, [_vp] * 5 + [_i] + [_vp] * 6 + [_i, _i64] + [_vp] * 4 + [_i64, _i, _i, _i,
+                                            _i, _i, _vp]),
     "tpq_ivfflat_range_segments": (_sz, [_i, _i]),
     "tpq_ivfflat_range_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "tpq_ivfflat_range_fill": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i,

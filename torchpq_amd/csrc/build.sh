@@ -4,7 +4,8 @@
 # one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
 # k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip, scan_flat.hip and
 # scan_pq4.hip alone (the 4-bit list scan takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it;
-# scan_pq4.h, its word loop and grouped tables, is shared with scan_pq4_filtered.hip, the filtered 4-bit scan, and rebuilds those two);
+# scan_pq4.h, its word loop and grouped tables, is shared with scan_pq4_filtered.hip, the filtered 4-bit scan, and scan_pq4_range.hip,
+# the 4-bit range search, and rebuilds those three);
 # scan_list.h (the frame of a list kernel) is included by scan_ref.h, scan_range.hip and, for clamped_n_probe, scan_packed_kernel.h,
 # so a change to it rebuilds every scan unit; scan_range.hip (IVFPQ range search) takes scan_list.h, scan_shared.h and
 # scan_args.h only, so the other scan headers -- the packed ones above all -- leave it alone; scan_filtered.hip (the filtered
@@ -51,7 +52,7 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_pq4.hip scan_pq4_filtered.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   if stale "$obj" "${HERE}/${src}"; then

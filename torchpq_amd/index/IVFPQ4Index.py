@@ -7,7 +7,10 @@ in place -- a 16-entry table row has no LDS bank conflicts whatever the codes ar
 and builds the query's table (n_subvectors x 16 floats) inside the scan workgroup.  add / expand / remove / tombstones /
 `_address2id` / state_dict are the container's.  `search_filtered` (tpq_ivfpq4_scan_filtered_topk / _residual_topk,
 csrc/scan_pq4_filtered.hip) gives the k best among an allowed id set, for both `pq_use_residual` settings, on the bit
-rows of `id_filter`.  No range search, no captured graph.
+rows of `id_filter`.  `range_search` / `range_search_filtered` (tpq_ivfpq4_range_count / _fill and their residual forms,
+csrc/scan_pq4_range.hip) give every stored code of the probed cells whose value reaches a threshold -- the value `search`
+returns for it, bit for bit -- on a two-pass scan of the same lists, optionally among the ids a filter allows.  No
+captured graph.
 
 `pq_use_residual=True` (semantically IVFPQIndex's): the PQ is learnt on, and a slot holds the code of,
 x - centroid(cell(x)); `encode` returns (pq_code, vq_code) and `decode` takes that pair and returns centroid + codeword.
@@ -24,9 +27,10 @@ import torch
 from .. import util
 from ..codec import PQ4Codec
 from ..container import CellContainer
-from ..kernels import IVFPQ4FilteredTopkHip, IVFPQ4ResidualTopkHip, IVFPQ4TopkHip
+from ..kernels import IVFPQ4FilteredTopkHip, IVFPQ4RangeHip, IVFPQ4ResidualTopkHip, IVFPQ4TopkHip
 from ._coarse import CoarseProbeMixin
-from ._filter import IdFilter, filtered_search_batches
+from ._filter import IdFilter, checked_filter_rows, filtered_search_batches
+from ._range import range_search_batches
 
 
 class IVFPQ4Index(CoarseProbeMixin, CellContainer):
@@ -54,6 +58,7 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
         self.pq_codec = PQ4Codec(d_vector=d_vector, n_subvectors=n_subvectors, distance=distance, verbose=verbose)
         self._pq4_topk = (IVFPQ4ResidualTopkHip if self.pq_use_residual else IVFPQ4TopkHip)(m=n_subvectors)
         self._pq4_filtered = IVFPQ4FilteredTopkHip(m=n_subvectors)
+        self._pq4_range = IVFPQ4RangeHip(m=n_subvectors)
         self.to(device)
 
     # ---- knobs (as IVFPQIndex) -------------------------------------------------------------------------
@@ -207,3 +212,68 @@ class IVFPQ4Index(CoarseProbeMixin, CellContainer):
             self, x, flt, filter_of_query, lambda xb, rows, sims, cells, n_probe_list, extents:
             self.search_cells_filtered(xb, cells, flt, filter_of_query=rows, base_sims=sims,
                                        n_probe_list=n_probe_list, k=k, _extents=extents))
+
+    # ---- range search ------------------------------------------------------------------------------
+    def range_search_cells(self, x, cells, threshold, base_sims=None, n_probe_list=None, return_address=False,
+                           _extents=None):
+        """Every live code of the given cells [n_query, n_probe] whose value is >= `threshold` (a float, or f32
+        [n_query]); (lims, values, ids[, address]) in scan order, see range_search.  The table of a query (of every
+        probe, with pq_use_residual) is the one search_cells builds.  (`base_sims` is accepted for IVFPQIndex's
+        signature and unused; `_extents` as in search_cells.)"""
+        return self._range_cells(x, cells, threshold, n_probe_list, return_address, _extents, None, None)
+
+    def range_search_cells_filtered(self, x, cells, threshold, flt, filter_of_query=None, base_sims=None,
+                                    n_probe_list=None, return_address=False, _extents=None):
+        """range_search_cells among the ids `flt` allows; `filter_of_query`: int32 [n_query], the row of `flt` every
+        query uses (None: row 0), as in search_cells_filtered.  The bit rows carry a row per query: one pair of passes
+        whatever rows the queries name."""
+        assert isinstance(flt, IdFilter), "flt is what index.id_filter(ids) returns"
+        return self._range_cells(x, cells, threshold, n_probe_list, return_address, _extents, flt, filter_of_query)
+
+    def _range_cells(self, x, cells, threshold, n_probe_list, return_address, extents, flt, filter_of_query):
+        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
+                                                                                        extents)
+        lists = dict(cell_start=cell_start, cell_size=cell_size, n_probe_list=n_probe_list, threshold=threshold,
+                     filter_bits=None if flt is None else flt.bits(self), filter_of_query=filter_of_query,
+                     is_empty=is_empty, distance=self.distance)
+        if self.pq_use_residual:
+            lims, vals, address = self._pq4_range.residual(self._storage, x, self.pq_codec.codebook,
+                                                           self._cell_major_centroids(), cells, **lists)
+        else:
+            lims, vals, address = self._pq4_range(self._storage, x, self.pq_codec.codebook, slots_hint=slots_hint,
+                                                  **lists)
+        ids = self.get_id_by_address(address) if address.numel() else torch.empty_like(address)
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+
+    def range_search(self, x, threshold, return_address=False, sort=False):
+        """x [d_vector, n_query] f32, threshold a float or f32 [n_query] -> (lims int64 [n_query + 1], values f32
+        [total], ids int64 [total][, address]): the hits of query q are values[lims[q]:lims[q+1]] and
+        ids[lims[q]:lims[q+1]] -- every stored code of the query's probed cells (`n_probe`, as in search) whose value is
+        >= threshold.  `threshold` is in the index's value space, the one search returns: -squared-L2 to the PQ
+        reconstruction for "euclidean" (everything within distance r: threshold = -r * r), the cosine similarity of
+        the reconstruction for "cosine".  A hit carries the bits search returns for the same slot.
+        Hits come in scan order (probe rank, then slot address); sort=True orders each query's hits by value
+        descending, equal values by address ascending.  Synchronises once per batch of `max_query_batch` queries:
+        the number of hits sizes the outputs."""
+        x = self._prepare(x)
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        return range_search_batches(
+            self, x, threshold, lambda xb, thr, sims, cells, n_probe_list, extents: self.range_search_cells(
+                xb, cells, thr, base_sims=sims, n_probe_list=n_probe_list, return_address=True, _extents=extents),
+            return_address, sort)
+
+    def range_search_filtered(self, x, threshold, flt, filter_of_query=None, return_address=False, sort=False):
+        """range_search among the ids a filter allows: flt = index.id_filter(ids), `filter_of_query` (an int tensor
+        [n_query]) chooses its row per query as in search_filtered (default: row 0; a row outside [0, n_filters) has
+        no hit).  The same values, order and outputs as range_search.  One pair of passes, and one synchronisation,
+        per batch of `max_query_batch` queries, whatever rows its queries name."""
+        x = self._prepare(x)
+        assert self.vq_codec.is_trained and self.pq_codec.is_trained, "index is not trained"
+        assert 1 <= self.n_probe <= self.n_cells
+        rows = checked_filter_rows(self, x, flt, filter_of_query)
+        return range_search_batches(
+            self, x, threshold, lambda xb, thr, rows_b, sims, cells, n_probe_list, extents:
+            self.range_search_cells_filtered(xb, cells, thr, flt, rows_b, base_sims=sims, n_probe_list=n_probe_list,
+                                             return_address=True, _extents=extents),
+            return_address, sort, alongside=(rows,))

@@ -1,4 +1,4 @@
-"""What the range searches of FlatIndex, IVFFlatIndex and IVFPQIndex share."""
+"""What the range searches of FlatIndex, IVFFlatIndex, IVFPQIndex and IVFPQ4Index share."""
 import torch
 
 

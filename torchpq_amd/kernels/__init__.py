@@ -13,7 +13,7 @@ from .container import (GetAddressByIdHip, GetCellByAddressHip, GetIdByAddressHi
                         GetWriteAddressHip, GrowCellsHip, PackCodesHip, PQDecodeHip, ScatterCodesHip)
 from .flat import FlatRangeHip, FlatTopkHip
 from .kmeans import ComputeCentroidsHip, CoarseAssignHip, LloydStepHip, MaxSimHip, MaxSimSelectHip
-from .scan import (PACKED_M, AdcLutHip, CellCandidatesHip, CellKeptState, IVFFlatRangeHip, IVFFlatTopkHip, IVFPQ4FilteredTopkHip, IVFPQ4ResidualTopkHip, IVFPQ4TopkHip, IVFPQFilteredTopkHip, IVFPQRangeHip,
+from .scan import (PACKED_M, AdcLutHip, CellCandidatesHip, CellKeptState, IVFFlatRangeHip, IVFFlatTopkHip, IVFPQ4FilteredTopkHip, IVFPQ4RangeHip, IVFPQ4ResidualTopkHip, IVFPQ4TopkHip, IVFPQFilteredTopkHip, IVFPQRangeHip,
                    IVFPQRerankHip, IVFPQTop1Hip, IVFPQTopkHip, ResidualPart1Hip, ResidualSlotTermsHip, ScanOrderHip, SlotFilterBuildHip,
                    packed_chunk_width)
 
@@ -21,5 +21,5 @@ __all__ = [
     "IVFPQTopkHip", "IVFPQTop1Hip", "ScanOrderHip", "CellCandidatesHip", "ResidualPart1Hip", "ResidualSlotTermsHip", "AdcLutHip", "TopkSelectHip", "CoarseSelectHip", "CoarseProbeHip", "Top1SelectHip",
     "Top32SelectHip", "SmartProbingHip", "MaxSimHip", "CoarseAssignHip", "MaxSimSelectHip", "LloydStepHip", "ComputeCentroidsHip", "GetIOAHip",
     "GetWriteAddressHip", "GetCellByAddressHip", "GetIdByAddressHip", "GetAddressByIdHip", "GrowCellsHip", "PQDecodeHip",
-    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "IVFPQ4TopkHip", "IVFPQ4ResidualTopkHip", "IVFPQ4FilteredTopkHip", "IVFPQRangeHip", "IVFPQFilteredTopkHip", "SlotFilterBuildHip", "FlatTopkHip", "FlatRangeHip", "packed_chunk_width", "PACKED_M", "CellKeptState",
+    "ScatterCodesHip", "PackCodesHip", "IVFPQRerankHip", "IVFFlatTopkHip", "IVFFlatRangeHip", "IVFPQ4TopkHip", "IVFPQ4ResidualTopkHip", "IVFPQ4FilteredTopkHip", "IVFPQ4RangeHip", "IVFPQRangeHip", "IVFPQFilteredTopkHip", "SlotFilterBuildHip", "FlatTopkHip", "FlatRangeHip", "packed_chunk_width", "PACKED_M", "CellKeptState",
 ]

@@ -1211,6 +1211,105 @@ class IVFPQ4FilteredTopkHip:
                           n_split, slots_hint)
 
 
+class IVFPQ4RangeHip:
+    """Range search over the lists of IVFPQ4Index (tpq_ivfpq4_range_count / _fill and their residual forms,
+    csrc/scan_pq4_range.hip): every candidate of IVFPQ4TopkHip / IVFPQ4ResidualTopkHip whose value is >= the query's
+    threshold, in scan order, optionally among the slots the query's row of filter bits allows; a hit carries the bits
+    those scans return for the slot; the semantics are defined in include/torchpq_amd.h."""
+
+    def __init__(self, m=8):
+        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
+        self.m = m
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
+
+    _n_split = IVFFlatTopkHip._n_split
+
+    def _inputs(self, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, threshold, filter_bits,
+                filter_of_query, is_empty, distance):
+        """the checks both calls share; `residual` is () or (centroids, cells) -> (the count / fill arguments in
+        front of the threshold, the checked threshold, (n_slots, m, ds, n_query, n_probe, metric), device)"""
+        n_slots = codes.shape[1]
+        m, ds, kk = codebook.shape
+        n_query, n_probe = cell_start.shape
+        assert m == self.m and kk == 16 and ds >= 1
+        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+        flt = (None, None, 0, 0)
+        if filter_bits is not None:
+            filter_of_query = IVFPQFilteredTopkHip._check_filter(filter_bits, filter_of_query, n_slots, n_query)
+            assert filter_bits.is_contiguous()
+            flt = (ptr(filter_bits), ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1])
+        else:
+            assert filter_of_query is None, "filter_of_query without filter_bits"
+        tables = ()
+        if residual:
+            centroids, cells = residual
+            assert centroids.dtype == torch.float32
+            assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+            centroids, cells = centroids.contiguous(), cells.contiguous()
+            tables = (ptr(centroids), ptr(cells), centroids.shape[0])
+            residual = (centroids, cells)
+        assert distance in ("euclidean", "cosine", "inner")
+        threshold = _checked_threshold(threshold, n_query)
+        query = query.contiguous()
+        codebook = codebook.contiguous()
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(codes, query, codebook, *residual, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
+                    filter_of_query, _tensor_or_none(threshold))
+        # (the tensors made contiguous above live until the passes have been launched: the closure holds them)
+        keep = (query, codebook, residual, cell_start, cell_size, filter_of_query)
+        inputs = (ptr(codes), ptr(query), ptr(codebook), *tables, ptr(is_empty), ptr(cell_start), ptr(cell_size),
+                  ptr(n_probe_list), *flt)
+        return inputs, threshold, (n_slots, m, ds, n_query, n_probe, metric_code(distance)), codes.device, keep
+
+    def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, threshold, filter_bits=None,
+                 filter_of_query=None, is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
+        """Plain codes.
+          codes, query, codebook, cell_start, cell_size, n_probe_list, is_empty: as IVFPQ4TopkHip
+          threshold: a Python float, or [n_query] float32 -- one per query
+          filter_bits: None, or [n_filters, stride] int32, bit s & 31 of word s >> 5 of a row: slot s is allowed
+          filter_of_query: [n_query] int32, the row of every query (outside [0, n_filters): no hit); None: row 0
+        returns (lims [n_query + 1] int64, values [total] float32, address [total] int64): the hits of query q are
+        values[lims[q]:lims[q+1]] / address[lims[q]:lims[q+1]], probe rank ascending, then address ascending.
+        Synchronises once: the number of hits sizes the outputs.
+        """
+        inputs, threshold, shape, device, keep = self._inputs(
+            codes, query, codebook, (), cell_start, cell_size, n_probe_list, threshold, filter_bits, filter_of_query,
+            is_empty, distance)
+        n_query = shape[3]
+
+        def passes():
+            split = self._n_split(n_query, device, slots_hint) if n_split is None else n_split
+            self.last_n_split = split
+            n_seg = load().tpq_ivfpq4_range_segments(n_query, split)
+            assert n_seg == n_query * split * 8, (n_query, split)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivfpq4_range_count", device, *inputs, thr, counts, *shape, split),
+                    lambda thr, *out: call("tpq_ivfpq4_range_fill", device, *inputs, thr, *out, *shape, split))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+    def residual(self, codes, query, codebook, centroids, cells, cell_start, cell_size, n_probe_list, threshold,
+                 filter_bits=None, filter_of_query=None, is_empty=None, distance="euclidean"):
+        """Residual codes: centroids [n_cells, d] and cells [n_query, max_n_probe] as IVFPQ4ResidualTopkHip, everything
+        else, and the result, as __call__; one workgroup per (query, probe): there is no n_split"""
+        inputs, threshold, shape, device, keep = self._inputs(
+            codes, query, codebook, (centroids, cells), cell_start, cell_size, n_probe_list, threshold, filter_bits,
+            filter_of_query, is_empty, distance)
+        n_query, n_probe = shape[3], shape[4]
+
+        def passes():
+            n_seg = load().tpq_ivfpq4_range_residual_segments(n_query, n_probe)
+            assert n_seg == n_query * n_probe * 8, (n_query, n_probe)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivfpq4_range_residual_count", device, *inputs, thr, counts, *shape),
+                    lambda thr, *out: call("tpq_ivfpq4_range_residual_fill", device, *inputs, thr, *out, *shape))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+
 # ---- what the range wrappers share --------------------------------------------------------------------------------
 def _checked_threshold(threshold, n_query):
     """a range search's threshold: a Python float, or one float32 per query (returned contiguous)"""
