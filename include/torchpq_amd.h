@@ -278,6 +278,21 @@ int tpq_ivfpq_scan_cell_threshold(int nq, int k, int n_split, int m, int ds, int
                                   int64_t n_slots, size_t workspace_bytes);
 int tpq_ivfpq_scan_use_cell_threshold(int on);
 int tpq_ivfpq_scan_cell_threshold_probes(void);
+/* The single-product key of the threshold form (ds = 2): both passes of step 4's kernel select on ONE fp16 product per
+ * k-step -- the hi pieces of codebook and query -- instead of three, from half the codebook image in LDS, with a band
+ * per query that bounds the dropped products per sub-quantizer from piece maxima of the codebook kept in the parameter
+ * block (of the workspace and of the kept state; tpq_ivfpq_cell_kept_bytes and the layouts are unchanged).  Every
+ * returned value is step 5's: same results, bit for bit.  The band is wider than that of three products (about three
+ * times on SIFT-like data): data with many rows within it of the k-th best fill the lists sooner, and a query whose lists
+ * overflow is redone exactly, as ever -- there is no automatic fall-back.
+ * tpq_ivfpq_scan_use_cell_single_product(on): the A/B switch, process-wide, read on the host during a call; default 1;
+ * 0 keeps every later call of the threshold form on three products.  Returns the previous setting.  ds = 1, the seeded
+ * form, tpq_ivfpq_cell_candidates and every query-major route run three products whatever it says.
+ * tpq_ivfpq_scan_last_cell_products(): the products per k-step the candidate kernels of the last packed scan call of this
+ * process ran -- 1 or 3 --, 0 when that call did not take the cell-major form.  TPQ_VERSION is unchanged by these. */
+#define TPQ_HAS_IVFPQ_CELL_SINGLE_PRODUCT 1
+int tpq_ivfpq_scan_use_cell_single_product(int on);
+int tpq_ivfpq_scan_last_cell_products(void);
 /* The kept state of the cell-major form: what a call of the form with slot norms derives from the index alone -- the
  * codebook's scale and bound, the split fp16 codebook as the candidate kernels stage it, and an fp32 norm per slot
  * address (NaN: tombstone) -- in a caller-owned device buffer of tpq_ivfpq_cell_kept_bytes(n_slots, ds) bytes (host

@@ -62,6 +62,8 @@ SIGNATURES = {
     "tpq_ivfpq_scan_cell_threshold": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i64, _sz]),
     "tpq_ivfpq_scan_use_cell_threshold": (_i, [_i]),
     "tpq_ivfpq_scan_cell_threshold_probes": (_i, []),
+    "tpq_ivfpq_scan_use_cell_single_product": (_i, [_i]),
+    "tpq_ivfpq_scan_last_cell_products": (_i, []),
     "tpq_ivfpq_scan_topk_residual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "tpq_residual_part1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

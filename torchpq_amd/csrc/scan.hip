@@ -405,6 +405,18 @@ extern "C" int tpq_ivfpq_scan_ordered(int nq, int k, int n_split, int m, int ds,
 // With room for one more array behind those -- an fp32 per slot (cell_norm_bytes) -- the slot norms are computed once
 // per call (cell_norm_kernel) instead of in every candidate block: cell_major_norms, tpq_ivfpq_scan_cell_norms.
 // Pure host arithmetic: tpq_ivfpq_scan_cell_major answers without a GPU.  Returns the chunks per query, 0 = today's path.
+// The A/B switch of the threshold form's selection key (index.use_cell_single_product): process-wide, read once per call
+// on the host; 1 (the default): one fp16 product per k-step and the per-query band of `The single-product key`
+// (scan_cells.hip) where that kernel is built (ds = 2); 0: three products.  Same results either way -- every returned
+// value is the finish kernel's --; the single product admits more candidates where many rows lie within 2 delta_q of the
+// k-th best, and a query whose lists overflow is redone exactly: that is the data the switch is for.
+// g_cell_products: the products per k-step the last packed scan call's candidate kernels ran, 0 when it did not take
+// the cell-major form.
+static std::atomic<int> g_cell_single_product{1};
+static std::atomic<int> g_cell_products{0};
+extern "C" int tpq_ivfpq_scan_use_cell_single_product(int on) { return g_cell_single_product.exchange(on ? 1 : 0); }
+extern "C" int tpq_ivfpq_scan_last_cell_products(void) { return g_cell_products.load(); }
+
 struct CellMajor {
   const int64_t* cells;  // [nq][max_nprobe]
   int n_cells;
@@ -470,6 +482,8 @@ static int run_cell_major(ScanArgs& a, ScanPlan p, const PackedUnit& u, const Ce
   c.n_slots = a.n_slots; c.nq = nq; c.max_nprobe = a.max_nprobe; c.n_cells = cm.n_cells; c.ds = a.ds;
   c.euclid = a.euclid; c.p0 = kCellP0; c.p_hi = a.max_nprobe; c.k = a.k; c.chunks = chunks; c.epoch = a.epoch;
   c.rel = cell_delta_rel(a.ds);
+  c.products = 3;
+  g_cell_products.store(3);
   c.seed_vals = a.out_vals; c.seed_addr = a.out_addr;
   c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
   c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
@@ -515,7 +529,10 @@ static int run_cell_threshold(ScanArgs& a, const ScanPlan& p, const PackedUnit& 
   c.cell_start = a.cell_start; c.cell_size = a.cell_size; c.n_probe_list = a.n_probe_list; c.cells = cm.cells;
   c.n_slots = a.n_slots; c.nq = nq; c.max_nprobe = a.max_nprobe; c.n_cells = cm.n_cells; c.ds = a.ds;
   c.euclid = a.euclid; c.p0 = 0; c.p_hi = a.max_nprobe; c.k = 0; c.thr_k = a.k; c.chunks = chunks; c.epoch = a.epoch;
-  c.rel = cell_delta_rel(a.ds);
+  // the selection key's arithmetic (scan_cells.hip: `The single-product key`): both passes on it, and its own band
+  c.products = g_cell_single_product.load() && cell_single_product_built(a.ds) ? 1 : 3;
+  c.rel = c.products == 1 ? cell_delta1_rel(a.ds) : cell_delta_rel(a.ds);
+  g_cell_products.store(c.products);
   c.keys = reinterpret_cast<unsigned*>(a.ws_vals); c.idx = reinterpret_cast<unsigned*>(a.ws_idx);
   c.list_evict = a.list_evict; c.flags = a.flags; c.ws_delta = a.ws_delta;
   // the extras where the seeded form has them (its pairs array, max_nprobe - kCellP0 per query, stays unused: pass B's
@@ -528,8 +545,10 @@ static int run_cell_threshold(ScanArgs& a, const ScanPlan& p, const PackedUnit& 
   cell_fill_thr(t, at + head, nq, a.max_nprobe, cm.n_cells);
   int rc = launch_cell_threshold(c, t, st);
   if (rc) return rc;
-  // stage 5 without seed chunks: every survivor of the cut is evaluated by the finish kernel's ascending-j chain
-  return u.finish(a, chunks, p.Rf, 0, c.cnt, st);
+  // stage 5 without seed chunks: every survivor of the cut is evaluated by the finish kernel's ascending-j chain; the
+  // exact list sized for the band of the key the candidates were selected on
+  const int Rf1 = c.products == 1 ? cell_single_finish_regs(a.k) : 0;
+  return u.finish(a, chunks, Rf1 > p.Rf ? Rf1 : p.Rf, 0, c.cnt, st);
 }
 
 extern "C" int tpq_ivfpq_scan_cell_major(int nq, int k, int n_split, int m, int ds, int max_nprobe, int64_t slots_hint,
@@ -578,6 +597,7 @@ static int run_packed(ScanArgs a, const ResidualArgs* ra, void* workspace, size_
   int rc = validate(a);
   if (rc) return rc;
   TPQ_REQUIRE(a.packed != nullptr, "ivfpq_scan_packed: null packed pointer");
+  g_cell_products.store(0);
   if (a.nq == 0) return TPQ_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ScanPlan p = plan_scan(a, ra != nullptr);

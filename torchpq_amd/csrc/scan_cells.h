@@ -115,7 +115,15 @@ struct CellArgs {
   float* kparams;
   unsigned* book;
   int kept_build;
+  // the MFMA products per k-step of the candidate kernels (scan_cells.hip: `The single-product key`): 3, or 1 -- the
+  // threshold form at ds = 2 when the switch is on; `rel` is then cell_delta1_rel and the seed kernel adds the query's
+  // own term from the piece maxima at kparams + kCellPieceMaxAt
+  int products;
 };
+// the piece maxima of cell_prep_kernel in the 256-byte parameter block: 64 numbers of 16 bits from this byte on -- per
+// pair i of sub-quantizers (2 i, 2 i + 1) the larger max_c |hi piece of s_x c_jc| (32 numbers), then the same of the lo
+// pieces --, each the upper half of an fp32 rounded UP.  Bytes [0, 16) and the block counters at ints 8 and 9 stay
+constexpr int kCellPieceMaxAt = 64;
 // the kept state: [256 bytes: the parameters][the codebook image, 64 x 256 x 4 ds bytes][an fp32 norm per slot address]
 inline size_t cell_book_bytes(int ds) { return (size_t)64 * 256 * 4 * ds; }
 inline size_t cell_kept_bytes(int64_t n_slots, int ds) {
@@ -203,6 +211,10 @@ __host__ __device__ inline float cell_fold_threshold(float thr, float q2) {
 void cell_fill_extras(CellArgs& a, void* at, size_t room, int layout_p0 = -1);
 // delta_q / (|q| + |x|max)^2 (derivation: scan_cells.hip)
 float cell_delta_rel(int ds);
+// the single-product key's delta_q is 1.25 x the query's own term (the seed kernel's) + this x (|q| + |x|max)^2
+float cell_delta1_rel(int ds);
+// whether the single-product candidate kernels are built for this ds (ds = 1 stays on three products)
+inline bool cell_single_product_built(int ds) { return ds == 2; }
 // stages 2-4 on `st`: seed (or the caller's thresholds), inversion, candidates
 int launch_cell_candidates(const CellArgs& a, hipStream_t st);
 // points `t` into `at` (cell_thr_bytes of it)

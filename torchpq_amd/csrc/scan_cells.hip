@@ -174,6 +174,41 @@
 //   never sees a maximum.  The two candidate launches draw their blocks from two counters (params + 8, + 9).
 // (Measured on the headline batch: profiles/cell_threshold_bench.json.)
 //
+// The single-product key (CellArgs::products == 1: the threshold form at ds = 2 with tpq_ivfpq_scan_use_cell_single_product
+// on, both passes, always together; cell_cand_kernel<.., PRODUCTS = 1>).  The candidate launches produce a selection key
+// only -- every returned value is the finish kernel's --, so the result depends on the key's error being inside a proven
+// band, not on its size.  S1 = sum over the k-steps of xh qh: ONE MFMA per k-step, the A operand four dword gathers from
+// the hi plane of the book (64 KiB at ds = 2, [j][c] -> h0 h1) straight into its register quad, the B operand the hi half
+// of qsplit.  The kept |x|^2 (still from both pieces), |q|^2, the fold, the one-fma test and the group maxima are as above.
+// Against g, with the notation of `Arithmetic`, N = D MFMA terms, per sub-quantizer j: XH_j = max_c |xh_jc|, XL_j =
+// max_c |xl_jc| over the scaled, split codebook, qh_j, ql_j the query's pieces:
+//   dropped products                    |xh.ql + xl.qh + xl.ql| <= sum_j (XH_j |ql_j| + XL_j |qh_j| + XL_j |ql_j|)
+//                                       (Cauchy-Schwarz per sub-quantizer) -> x 2 / (s_q s_x) in value units: the QUERY'S
+//                                       OWN TERM, evaluated by cell_seed_kernel, upwards (x 1.0001)
+//   piece residues                      |rq.x' + (qh + ql).rx| <= 2.03 2^-22 Q X + 1.01 eta sqrt(D) (Q + X)
+//   fp32 accumulation, any order        1.003 N 2^-23 Q X, N = D
+//     -> (2.03 2^-22 + 1.003 N 2^-23) B^2 / 2  +  1.01 sqrt(D) 2^-26 B^2
+//   the norm chains, |x|^2 from the pieces, the two subtractions, the exact chain's own rounding: as under `Arithmetic`
+// delta1_q = 1.25 x (the query's own term + the other lines' sum x B^2) -- cell_delta1_rel is 1.25 x that sum, and the seed
+// kernel applies 1.25 to its term.  ws_delta = 2 delta1_q and thr = M_k - 2 delta1_q in both passes, so `Why M_k bounds`
+// and `Why M_k - 2 delta_q admits every member` hold word for word with delta1_q for delta_q; the inner product's errors
+// are a subset (its term is taken with the same factor 2).
+// XH_j and XL_j depend on the index alone: cell_prep_kernel computes them behind its four numbers and leaves them in the
+// 256-byte parameter block -- of the workspace, or of the kept state -- from byte kCellPieceMaxAt on, per PAIR of
+// sub-quantizers (the larger of the two, 32 + 32 numbers) as the upper 16 bits of an fp32 rounded up: a pair's maximum
+// bounds either member, rounding up only loosens.  The first 16 bytes, the counters at ints 8 and 9, the image, the norms
+// and cell_kept_bytes are what they were.
+// The band is 3.35 x that of three products on the headline's SIFT-like index (2 delta: 2 309 against 689 value units) and
+// 5.8 x on Gaussian codebooks, whose largest entry per sub-quantizer is far from the typical one: 11 % more candidates on
+// the headline (253 against 227 per query).  More rows then survive the finish kernel's cut at F_k - 2 delta1_q, and its
+// exact list is sized for that: cell_single_finish_regs (scan_host.h) -- 256 entries instead of 128 at k = 100; with 128
+// a batch of the existing tests (7 probes, k = 100, inner product) had 20 of 1 025 queries redone exactly.
+// ds = 1 stays on three products: its single-product form (2-byte entries, pairs packed into the operand) was not built
+// or measured.  The seeded form, tpq_ivfpq_cell_candidates and the query-major routes keep three products.
+// (Measured on the headline batch, profiles/cell_single_product_bench.json: the candidates proper 416 -> 294 us, pass A
+// 132 -> 141 us, the finish kernel 115 -> 139 us, the scan's kernels together 741 -> 652-657 us, the step 0.821 -> 0.741
+// ms; twelve waves per workgroup (126 registers, no spill) against eight and sixteen: 0.732 / 0.754 / 0.750 ms.)
+//
 // The kept state (tpq_ivfpq_search_fused_cells_kept; CellArgs::kparams, book, norm; cell_use_kept, scan_cells.h).  Three
 // things a call of the form with slot norms computes are functions of the codebook, the codes and the tombstones alone --
 // no query enters: cell_prep_kernel's four numbers, the split fp16 codebook every candidate workgroup (and the norm
@@ -211,6 +246,14 @@ float cell_delta_rel(int ds) {
   const double sum = 0.5 * (3.03 * 4 * u + 1.003 * N * 2 * u) + 1.01 * std::sqrt(D) * u / 4 + (D + 1) * u + 14 * u + 4 * u +
                      1.001 * (64 + ds + 2) * u;
   return (float)(1.25 * sum * (1.0 + 1.0 / 1024));  // (+ 2^-10: B^2 and the product are evaluated in fp32)
+}
+
+// `The single-product key`: every line of the budget but the dropped products, which are the query's own term
+float cell_delta1_rel(int ds) {
+  const double D = 64.0 * ds, N = D, u = 1.0 / 16777216.0;  // u = 2^-24
+  const double sum = 0.5 * (2.03 * 4 * u + 1.003 * N * 2 * u) + 1.01 * std::sqrt(D) * u / 4 + (D + 1) * u + 14 * u + 4 * u +
+                     1.001 * (64 + ds + 2) * u;
+  return (float)(1.25 * sum * (1.0 + 1.0 / 1024));
 }
 
 void cell_fill_extras(CellArgs& a, void* at, size_t room, int layout_p0) {
@@ -285,9 +328,48 @@ __device__ __forceinline__ unsigned prep_maxima(const float* __restrict__ codebo
   return mb;
 }
 
+// the same share of the piece maxima (`The single-product key`): per sub-quantizer the largest |hi piece|^2 and |lo piece|^2
+// of s_x c_jc over its 256 entries, the pieces as book_entry forms them
+template <int DS>
+__device__ __forceinline__ void prep_piece_maxima(const float* __restrict__ codebook, float sx, int lane, int wave,
+                                                  float* xh2_s, float* xl2_s) {
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    float hm = 0.f, lm = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {
+      float h2 = 0.f, l2 = 0.f;
+#pragma unroll
+      for (int e = 0; e < DS; ++e) {
+        const float ys = codebook[((wave + 16 * jj) * DS + e) * 256 + lane + 64 * cc] * sx;
+        const _Float16 h = (_Float16)ys;
+        const float hf = (float)h, lf = (float)(_Float16)(ys - hf);
+        h2 = fmaf(hf, hf, h2);
+        l2 = fmaf(lf, lf, l2);
+      }
+      hm = fmaxf(hm, h2);
+      lm = fmaxf(lm, l2);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      hm = fmaxf(hm, __shfl_xor(hm, d, 64));
+      lm = fmaxf(lm, __shfl_xor(lm, d, 64));
+    }
+    if (lane == 0) {
+      xh2_s[wave + 16 * jj] = hm;
+      xl2_s[wave + 16 * jj] = lm;
+    }
+  }
+}
+// a positive float's upper 16 bits, rounded UP (the value first raised past the roundings of its chain and root)
+__device__ __forceinline__ unsigned short piece_max16(float sq_norm) {
+  return (unsigned short)((__float_as_uint(sqrtf(sq_norm) * 1.0001f) + 0xffffu) >> 16);
+}
+__device__ __forceinline__ float piece_max_of(unsigned short w) { return __uint_as_float((unsigned)w << 16); }
+
 __global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
   __shared__ unsigned maxbits_s;
-  __shared__ float c2max_s[64];
+  __shared__ float c2max_s[64], xh2_s[64], xl2_s[64], sx_s;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) maxbits_s = 0u;
   __syncthreads();
@@ -307,6 +389,21 @@ __global__ __launch_bounds__(1024) void cell_prep_kernel(CellArgs a) {
     a.kparams[1] = x2;
     a.kparams[2] = ok ? 1.f : 0.f;
     a.kparams[3] = ok ? pow2i(kCellScaleExp - e) : 0.f;  // s_x
+    sx_s = ok ? pow2i(kCellScaleExp - e) : 0.f;
+  }
+  __syncthreads();
+  // the piece maxima per pair of sub-quantizers (kCellPieceMaxAt, scan_cells.h); a codebook that cannot be scaled leaves
+  // numbers nobody reads: every query is flagged
+  if (a.ds == 1)
+    prep_piece_maxima<1>(a.codebook, sx_s, lane, wave, xh2_s, xl2_s);
+  else
+    prep_piece_maxima<2>(a.codebook, sx_s, lane, wave, xh2_s, xl2_s);
+  __syncthreads();
+  if (tid < 64) {
+    const float* s = tid < 32 ? xh2_s : xl2_s;
+    const int i = tid & 31;
+    unsigned short* out = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(a.kparams) + kCellPieceMaxAt);
+    out[tid] = piece_max16(fmaxf(s[2 * i], s[2 * i + 1]));
   }
 }
 
@@ -374,8 +471,33 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
     }
     return;
   }
+  // the pieces of s_q q: this lane's two components
+  const float sq = pow2i(kCellScaleExp - eq);
+  const float y0 = x0 * sq, y1 = x1 * sq;
+  const _Float16 h0 = (_Float16)y0, h1 = (_Float16)y1;
+  const _Float16 l0 = (_Float16)(y0 - (float)h0), l1 = (_Float16)(y1 - (float)h1);
   const float B = sqrtf(q2) * 1.000001f + sqrtf(a.kparams[1]) * 1.000001f;
-  const float delta = a.rel * (B * B);
+  float delta = a.rel * (B * B);
+  if (a.products == 1) {
+    // the single-product key: the dropped products, bounded per sub-quantizer from cell_prep_kernel's piece maxima (per
+    // pair of sub-quantizers) and the norms of this query's pieces per sub-quantizer -- component i belongs to
+    // sub-quantizer i / ds, a lane's neighbour holds the other component at ds = 2 --, in value units, upwards
+    const unsigned short* pm =
+        reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(a.kparams) + kCellPieceMaxAt);
+    auto subq_norm = [&](_Float16 v) {
+      float s = (float)v * (float)v;
+      if (a.ds == 2) s += __shfl_xor(s, 1, 64);
+      return sqrtf(s) * 1.000001f;
+    };
+    const float nh0 = subq_norm(h0), nl0 = subq_norm(l0), nh1 = subq_norm(h1), nl1 = subq_norm(l1);
+    const int i0 = lane / (2 * a.ds), i1 = a.ds == 2 ? 16 + (lane >> 2) : 0;  // (ds = 1: the second component is 0)
+    float t = fmaf(piece_max_of(pm[i0]), nl0, piece_max_of(pm[32 + i0]) * (nh0 + nl0)) +
+              fmaf(piece_max_of(pm[i1]), nl1, piece_max_of(pm[32 + i1]) * (nh1 + nl1));
+    if (a.ds == 2 && (lane & 1)) t = 0.f;  // (one lane per sub-quantizer)
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d, 64);
+    delta = fmaf(1.25f * 1.0001f * t, 2.f / (sq * a.kparams[3]), delta);
+  }
   if (lane == 0) {
     // the candidate kernel's threshold: a row passes when fl(a - |q|^2) >= tau - delta, tested as a >= the fold
     if (a.thr_k == 0) a.thr[q] = a.euclid ? cell_fold_threshold(tau - delta, q2) : tau - delta;
@@ -388,17 +510,14 @@ __global__ __launch_bounds__(256) void cell_seed_kernel(CellArgs a) {
   if (a.list_evict && lane < a.chunks) a.list_evict[(int64_t)q * a.chunks + lane] = 0;
   {
     // the pieces of s_q q, component-major per query: the candidate kernel's B operand is 16 contiguous bytes of it
-    const float sq = pow2i(kCellScaleExp - eq);
     _Float16* qs = a.qsplit + (int64_t)q * kCellQSplit;
-    const float y0 = x0 * sq, y1 = x1 * sq;
-    const _Float16 h0 = (_Float16)y0, h1 = (_Float16)y1;
     if (lane < D) {
       qs[lane] = h0;
-      qs[128 + lane] = (_Float16)(y0 - (float)h0);
+      qs[128 + lane] = l0;
     }
     if (64 + lane < D) {
       qs[64 + lane] = h1;
-      qs[192 + lane] = (_Float16)(y1 - (float)h1);
+      qs[192 + lane] = l1;
     }
   }
   const int64_t base = (int64_t)q * a.chunks * 64;
@@ -567,15 +686,23 @@ __global__ __launch_bounds__(256) void cell_scatter_wide_kernel(CellArgs a) {
 #define TPQ_CELL_WAVES 8  // (variant builds: the A/B of 12)
 #endif
 constexpr int kCellWaves = TPQ_CELL_WAVES;
+// the single-product kernels (`The single-product key`): half the book and fewer registers leave room for more waves
+#ifndef TPQ_CELL_WAVES1
+#define TPQ_CELL_WAVES1 12  // (variant builds: the A/B of 8, 12 and 16 -- profiles/cell_single_product_bench.json)
+#endif
+constexpr int kCellWaves1 = TPQ_CELL_WAVES1;
+constexpr int cell_waves(int products) { return products == 1 ? kCellWaves1 : kCellWaves; }
 constexpr size_t kCellLdsBytes = 160 * 1024;
-template <int DS>
+// PRODUCTS = 1: the hi plane alone, [j][c] -> DS hi pieces (ds = 2: 64 KiB), and the staging depth from what that leaves
+template <int DS, int PRODUCTS = 3>
 struct CellBook {
   static constexpr int KS = 4 * DS;                            // MFMA k-steps of 16 components
-  static constexpr size_t kBook = (size_t)64 * 256 * 4 * DS;   // the split codebook: [j][c] -> DS hi pieces, DS lo pieces
-  static constexpr int kWaves = kCellWaves;
+  static constexpr size_t kBook = (size_t)64 * 256 * (PRODUCTS == 1 ? 2 : 4) * DS;  // [j][c] -> DS hi pieces, DS lo pieces
+  static constexpr int kWaves = cell_waves(PRODUCTS);
   static constexpr int kThreads = 64 * kWaves;
   static constexpr size_t kNorms = (size_t)kWaves * 32 * 4;    // per wave: |x|^2 of the tile's 32 rows (NaN: not live)
-  static constexpr int kDepth = (int)((kCellLdsBytes - (size_t)64 * 256 * 8 - kNorms) / ((size_t)kWaves * 64 * 8));
+  static constexpr int kDepth = (int)((kCellLdsBytes - (PRODUCTS == 1 ? kBook : (size_t)64 * 256 * 8) - kNorms) /
+                                      ((size_t)kWaves * 64 * 8));
   static constexpr size_t kBytes = kBook + kNorms + (size_t)kWaves * 64 * kDepth * 8;
   static_assert(kDepth >= 1 && kBytes <= kCellLdsBytes, "the staging area does not fit the CU's LDS");
 };
@@ -714,10 +841,14 @@ __global__ __launch_bounds__(512) void cell_norm_kernel(CellArgs a) {
 // loop and stores, per tile, the key image of the largest tested value of every group of kCellThrGroup of its 16 rows --
 // 0, which counts for nothing in a search over key images, for a group without a live row.  Entries at or beyond the
 // capacity are dropped.  NORMS only: the form requires the norm array.
-template <int DS, bool NORMS, bool EUCLID, bool MAXIMA = false>
-__global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellArgs a) {
+// PRODUCTS = 1: `The single-product key` -- the hi plane of the book alone in LDS (one dword per entry at ds = 2), a
+// k-step's four entries gathered straight into the A operand's register quad, one MFMA per k-step against the hi half
+// of the split query.  NORMS only, ds = 2 only (ds = 1 stays on three products); everything behind the MFMAs as it was.
+template <int DS, bool NORMS, bool EUCLID, bool MAXIMA = false, int PRODUCTS = 3>
+__global__ __launch_bounds__(64 * cell_waves(PRODUCTS)) void cell_cand_kernel(CellArgs a) {
   static_assert(!MAXIMA || NORMS, "pass A reads the slot norms");
-  using T = CellBook<DS>;
+  static_assert(PRODUCTS == 3 || (PRODUCTS == 1 && DS == 2 && NORMS), "the single-product key: ds = 2 with slot norms");
+  using T = CellBook<DS, PRODUCTS>;
   constexpr int S = cell_pieces(MAXIMA);
   constexpr int KS = T::KS;
   constexpr int kDepth = T::kDepth;
@@ -734,7 +865,20 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
   const float inv_sx2 = inv_sx * inv_sx;
   // the tombstone bytes, or any readable bytes of one per slot when the index keeps none (the value is not used then)
   const uint8_t* __restrict__ emp = a.is_empty ? a.is_empty : a.codes;
-  if (a.book) {  // the kept image: 16 bytes per thread and round, no conversion
+  if constexpr (PRODUCTS == 1) {
+    if (a.book) {  // the hi dwords of two entries of the kept image per 16-byte load
+      const u32x4* __restrict__ img = reinterpret_cast<const u32x4*>(a.book);
+      for (int i = tid; i < 64 * 256 / 2; i += T::kThreads) {
+        const u32x4 v = img[i];
+        reinterpret_cast<uint2*>(book)[i] = make_uint2(v[0], v[2]);
+      }
+    } else {  // (book_entry's hi pieces)
+      for (int i = tid; i < 64 * 256; i += T::kThreads) {
+        const int j = i >> 8, c = i & 255;
+        book[i] = pack_f16x2((_Float16)(a.codebook[(j * 2) * 256 + c] * sx), (_Float16)(a.codebook[(j * 2 + 1) * 256 + c] * sx));
+      }
+    }
+  } else if (a.book) {  // the kept image: 16 bytes per thread and round, no conversion
     const u32x4* __restrict__ img = reinterpret_cast<const u32x4*>(a.book);
     for (int i = tid; i < (int)(T::kBook / 16); i += T::kThreads) reinterpret_cast<u32x4*>(book)[i] = img[i];
   } else {
@@ -785,13 +929,14 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
     // the admission test of a row is ONE fma and ONE compare (see the header): test = fma(acc, um, -|x|^2) >= thr2.
     // A lane without a query has um = 0 and thr2 = +inf: its test value is -|x|^2, 0 or NaN, and never passes
     const float um = EUCLID ? 2.f * unscale : unscale;
-    f16x8 qh[KS], ql[KS];
+    f16x8 qh[KS], ql[PRODUCTS == 3 ? KS : 1];
     const _Float16* __restrict__ qs = a.qsplit + (int64_t)q * kCellQSplit + 8 * half;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const u32x4 z = {0u, 0u, 0u, 0u};
       qh[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 16 * s) : z);
-      ql[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 128 + 16 * s) : z);
+      if constexpr (PRODUCTS == 3)
+        ql[s] = __builtin_bit_cast(f16x8, qvalid ? *reinterpret_cast<const u32x4*>(qs + 128 + 16 * s) : z);
     }
     // the code dwords of this lane's components: k-step s holds components [16 s + 8 half, + 8), i.e. sub-quantizers
     // [(16 s + 8 half) / DS, + 8 / DS): one dword at ds = 2, two at ds = 1; aux: the norm's bits (NORMS) or the tombstone
@@ -854,7 +999,13 @@ __global__ __launch_bounds__(CellBook<DS>::kThreads) void cell_cand_kernel(CellA
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         u32x4 vh, vl;
-        if constexpr (DS == 2) {
+        if constexpr (PRODUCTS == 1) {
+          const int j0 = 8 * s + 4 * half;
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) vh[bb] = book[(j0 + bb) * 256 + (int)((w[s] >> (8 * bb)) & 255u)];
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vh), qh[s], acc, 0, 0, 0);
+          continue;
+        } else if constexpr (DS == 2) {
           const int j0 = 8 * s + 4 * half;
           uint2 en[4];
 #pragma unroll
@@ -1004,10 +1155,12 @@ __global__ __launch_bounds__(256) void cell_kth_kernel(CellArgs a) {
 }
 
 // the metric is the kernel's: no select on it in the tile loop
-template <int DS, bool NORMS, bool MAXIMA = false>
-static int launch_cand(const CellArgs& a, dim3 grid, dim3 wg, hipStream_t st) {
-  return a.euclid ? launch_with_lds(cell_cand_kernel<DS, NORMS, true, MAXIMA>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a)
-                  : launch_with_lds(cell_cand_kernel<DS, NORMS, false, MAXIMA>, "cell_cand_kernel", grid, wg, CellBook<DS>::kBytes, st, a);
+template <int DS, bool NORMS, bool MAXIMA = false, int PRODUCTS = 3>
+static int launch_cand(const CellArgs& a, dim3 grid, hipStream_t st) {
+  using T = CellBook<DS, PRODUCTS>;
+  const dim3 wg(T::kThreads);
+  return a.euclid ? launch_with_lds(cell_cand_kernel<DS, NORMS, true, MAXIMA, PRODUCTS>, "cell_cand_kernel", grid, wg, T::kBytes, st, a)
+                  : launch_with_lds(cell_cand_kernel<DS, NORMS, false, MAXIMA, PRODUCTS>, "cell_cand_kernel", grid, wg, T::kBytes, st, a);
 }
 
 static int cell_cus() {
@@ -1101,7 +1254,8 @@ static unsigned cell_cand_grid(const CellArgs& a, int n_cus, bool maxima = false
   int64_t blocks = (int64_t)a.n_cells + np / kCellGroup;
   if (blocks > np) blocks = np;
   if (blocks < 1) return 0;
-  blocks = (blocks * cell_pieces(maxima) + kCellWaves - 1) / kCellWaves;
+  const int waves = cell_waves(a.products);
+  blocks = (blocks * cell_pieces(maxima) + waves - 1) / waves;
   return (unsigned)(blocks > n_cus ? n_cus : blocks);
 }
 
@@ -1119,13 +1273,14 @@ int launch_cell_candidates(const CellArgs& a, hipStream_t st) {
   if (a.p_hi <= a.p0) return TPQ_OK;
   if (int rc = launch_cell_inversion(a, st)) return rc;
   const int n_cus = cell_cus();
-  const dim3 grid(cell_cand_grid(a, n_cus)), cand_wg(64 * kCellWaves);
+  TPQ_REQUIRE(a.products == 3, "ivfpq_scan (cell-major): the seeded form runs three products");
+  const dim3 grid(cell_cand_grid(a, n_cus));
   if (a.norm) {
     if (!a.book)  // (a kept state holds the norms of every slot)
       if (int rc = launch_cell_norms(a, n_cus, st)) return rc;
-    return a.ds == 1 ? launch_cand<1, true>(a, grid, cand_wg, st) : launch_cand<2, true>(a, grid, cand_wg, st);
+    return a.ds == 1 ? launch_cand<1, true>(a, grid, st) : launch_cand<2, true>(a, grid, st);
   }
-  return a.ds == 1 ? launch_cand<1, false>(a, grid, cand_wg, st) : launch_cand<2, false>(a, grid, cand_wg, st);
+  return a.ds == 1 ? launch_cand<1, false>(a, grid, st) : launch_cand<2, false>(a, grid, st);
 }
 
 void cell_fill_thr(CellThrArrays& t, void* at, int nq, int max_nprobe, int n_cells) {
@@ -1179,9 +1334,12 @@ int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t
     if (int rc = launch_cell_norms(b, n_cus, st)) return rc;
   if (!one_walk)
     if (int rc = launch_cell_inversion(pa, st)) return rc;
-  const dim3 cand_wg(64 * kCellWaves);
-  if (int rc = a.ds == 1 ? launch_cand<1, true, true>(pa, dim3(cell_cand_grid(pa, n_cus, true)), cand_wg, st)
-                         : launch_cand<2, true, true>(pa, dim3(cell_cand_grid(pa, n_cus, true)), cand_wg, st))
+  // both passes on the same arithmetic, always: they share delta_q
+  const bool single = a.products == 1;
+  const dim3 grid_a(cell_cand_grid(pa, n_cus, true));
+  if (int rc = a.ds == 1 ? launch_cand<1, true, true>(pa, grid_a, st)
+               : single  ? launch_cand<2, true, true, 1>(pa, grid_a, st)
+                         : launch_cand<2, true, true>(pa, grid_a, st))
     return rc;
   const dim3 per_query((unsigned)((a.nq + 3) / 4));
   if (a.chunks <= 8)
@@ -1190,7 +1348,9 @@ int launch_cell_threshold(const CellArgs& a, const CellThrArrays& t, hipStream_t
     hipLaunchKernelGGL(cell_kth_kernel<16>, per_query, dim3(256), 0, st, b);
   TPQ_LAUNCH_CHECK("cell_kth_kernel");
   const dim3 grid(cell_cand_grid(b, n_cus));
-  return a.ds == 1 ? launch_cand<1, true>(b, grid, cand_wg, st) : launch_cand<2, true>(b, grid, cand_wg, st);
+  return a.ds == 1 ? launch_cand<1, true>(b, grid, st)
+         : single  ? launch_cand<2, true, false, 1>(b, grid, st)
+                   : launch_cand<2, true>(b, grid, st);
 }
 
 }  // namespace tpq
@@ -1228,6 +1388,7 @@ extern "C" int tpq_ivfpq_cell_candidates(const uint8_t* codes, const float* quer
   a.euclid = metric == TPQ_METRIC_NEG_SQ_L2 ? 1 : 0;
   a.p0 = first_probe; a.p_hi = max_nprobe; a.k = 0; a.chunks = capacity / 64; a.epoch = 1; a.rel = cell_delta_rel(ds);
   a.thr_in = threshold;
+  a.products = 3;
   a.keys = out_keys; a.idx = out_addr; a.flags = out_flags; a.ws_delta = out_delta;
   cell_fill_extras(a, workspace, workspace_bytes);  // (with room behind the extras: the slot norms, once per call)
   a.cnt = out_count;

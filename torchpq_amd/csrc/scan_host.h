@@ -26,6 +26,11 @@ static int dump_finish_regs(int k, int64_t slots_hint) {
   const int slack = (slots_hint > 0 && slots_hint <= 16384) ? kBandSlack : 16 + k / 8;
   return pow2_ceil((k + slack + 63) / 64);
 }
+// ... and on the cell-major threshold form's single-product key (scan_cells.hip): its band is three to six times that of
+// three products (SIFT-like data 3.3, Gaussian codebooks 5.8: the bound takes the LARGEST entry of a sub-quantizer), and
+// what lies within it below the k-th best grows with it -- four times the slack above, whatever the slots (k = 100: 256
+// entries instead of 128; k <= 128 stays within the 4 registers the finish kernel is built for beside 8)
+static int cell_single_finish_regs(int k) { return pow2_ceil((k + 4 * (16 + k / 8) + 63) / 64); }
 // Registers of the per-wave lists of the packed scan.  Tiles are dealt round-robin, so a wave's share
 // of the top-k is ~k/NW: the lists are sized for at least 2k entries over the workgroup (64 RL per
 // wave) instead of k + 8 per wave.  Folding 64 candidates into a 512- or 1024-entry sorted list used

@@ -20,17 +20,19 @@ class IVFPQTopk:
 
     def topk_fused(self, data, query, codebook, cell_start, cell_size, is_empty, n_probe_list, k=256,
                    distance="euclidean", packed=None, address2id=None, slots_hint=None, cells=None, n_cells=0,
-                   cell_threshold=True, kept=None):
+                   cell_threshold=True, kept=None, cell_single_product=True):
         """PQCodec.precompute_adc + topk fused: the [m, n_query, 256] table never touches HBM
         (`cells`, `n_cells`: the probed cells, for the cell-major form of a large cell-dense batch; `cell_threshold`:
-        that form may take its threshold from group maxima instead of a query-major pass; `kept`: the provider of the
+        that form may take its threshold from group maxima instead of a query-major pass; `cell_single_product`: the
+        threshold form may select on one fp16 product with a per-query band; `kept`: the provider of the
         form's kept state, IVFPQTopkHip.topk_fused)"""
         assert 0 < k <= 1024
         return self._scan.topk_fused(data=data, query=query, codebook=codebook, is_empty=is_empty,
                                      cell_start=cell_start, cell_size=cell_size,
                                      n_probe_list=n_probe_list, n_candidates=k, distance=distance,
                                      packed=packed, address2id=address2id, slots_hint=slots_hint,
-                                     cells=cells, n_cells=n_cells, cell_threshold=cell_threshold, kept=kept)
+                                     cells=cells, n_cells=n_cells, cell_threshold=cell_threshold, kept=kept,
+                                     cell_single_product=cell_single_product)
 
     def topk_residual(self, data, precomputed, cell_start, cell_size, base_sims, is_empty,
                       n_probe_list, k=256, address2id=None):

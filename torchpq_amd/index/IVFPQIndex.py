@@ -31,6 +31,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
     fused_lut_max_subvector = 4
     use_cell_major = True
     use_cell_threshold = True
+    use_cell_single_product = True
     use_cell_kept = True
 
     def __init__(self, d_vector, n_subvectors=8, n_cells=128, initial_size=None,
@@ -70,6 +71,10 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
         # ... and that form may take its threshold from the candidate kernel's group maxima instead of a query-major pass
         # over the first probes (the library's rule decides, IVFPQTopkHip.last_cell_threshold() tells)
         self.use_cell_threshold = True
+        # ... whose selection key is one fp16 product per k-step with a per-query band (ds = 2); False: three products and
+        # the narrower band -- same results; for data with many rows within that band of the k-th best, whose queries
+        # would overflow their lists and be redone exactly (IVFPQTopkHip.last_cell_products() tells)
+        self.use_cell_single_product = True
         # ... and keeps what it derives from codes, codebook and tombstones alone -- scale, split codebook, slot norms --
         # across searches, rebuilt after add / remove / growth / load_state_dict / a write to the codebook
         # (IVFPQTopkHip.last_cell_kept tells; False: derived again in every call)
@@ -339,7 +344,7 @@ class IVFPQIndex(CoarseProbeMixin, CellContainer):
             found = self._ivfpq_topk.topk_fused(
                 packed=self._scan_layout(), query=x, codebook=self.pq_codec.codebook, k=k, distance=self.distance,
                 slots_hint=slots_hint, cells=cells if self.use_cell_major else None, n_cells=self.n_cells,
-                cell_threshold=self.use_cell_threshold,
+                cell_threshold=self.use_cell_threshold, cell_single_product=self.use_cell_single_product,
                 kept=self._cell_kept_state if self.use_cell_kept and self.use_cell_major else None, **lists)
         else:
             found = self._ivfpq_topk.topk(

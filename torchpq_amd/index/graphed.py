@@ -23,7 +23,7 @@ class GraphedSearch:
     graph's static outputs -- clone them if they must survive the next call."""
 
     KNOBS = ("n_probe", "use_smart_probing", "_smart_probing_temperature", "use_packed_layout",
-             "use_fused_lut", "use_cell_major", "use_cell_threshold", "use_cell_kept", "use_fused_probe", "use_cublas", "_use_precomputed", "pq_use_residual",
+             "use_fused_lut", "use_cell_major", "use_cell_threshold", "use_cell_single_product", "use_cell_kept", "use_fused_probe", "use_cublas", "_use_precomputed", "pq_use_residual",
              "distance", "max_query_batch", "_has_holes", "_codes_version")
 
     @staticmethod

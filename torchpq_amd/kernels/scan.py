@@ -75,6 +75,7 @@ class IVFPQTopkHip:
         self._last_cells = None       # (n_cells, n_slots) when the last call handed over its probed cells
         self._last_withheld = False   # the last call switched the cell-major form's threshold form off
         self.last_cell_kept = None    # "built" / "reused": what the last call did with a kept state; None: it used none
+        self._last_products = None    # tpq_ivfpq_scan_last_cell_products right after the last call
 
     def _tickets(self, n_query, n_split, device):
         """zeroed int32 [>= n_query] for this (device, current stream), or None (unsplit queries need none;
@@ -213,6 +214,13 @@ class IVFPQTopkHip:
             return False
         return self.cell_threshold(self.last_workspace_bytes, *self._last_cells)
 
+    def last_cell_products(self):
+        """diagnostics: the fp16 MFMA products per k-step the candidate kernels of the last topk / topk_fused call ran
+        (tpq_ivfpq_scan_last_cell_products, read right after the call): 1 -- the threshold form's single-product key
+        and its per-query band (csrc/scan_cells.hip, `The single-product key`; ds = 2 with the switch on) --, 3, or 0
+        for a call that did not take the cell-major form"""
+        return self._last_products
+
     def last_cell_threshold_state(self):
         """diagnostics (synchronises; needs keep_workspace and a last call that ran the threshold form): what the form's
         first pass and cell_kth_kernel left in the workspace, as a dict of
@@ -267,7 +275,7 @@ class IVFPQTopkHip:
         return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
 
     def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed,
-              cells=None, n_cells=0, cell_threshold=True, kept=None, **route):
+              cells=None, n_cells=0, cell_threshold=True, kept=None, cell_single_product=True, **route):
         """What topk / topk_fused / topk_residual_packed share once their arguments are checked: the outputs, the
         split, the diagnostics, the workspace and the call of `name` -- its own `inputs`, then the arguments every
         scan entry point of the library ends with (`ticketed`: the symbol takes tickets and the slots hint; `cells`:
@@ -316,11 +324,14 @@ class IVFPQTopkHip:
                     tail += (ptr(kept.buf), kept.buf.numel(), int(kept.valid))
             # (the switch is the library's, process-wide and read on the host during the call: set for this call alone)
             before = lib.tpq_ivfpq_scan_use_cell_threshold(1 if cell_threshold else 0)
+            before_sp = lib.tpq_ivfpq_scan_use_cell_single_product(1 if cell_single_product else 0)
             try:
                 rc = getattr(lib, name)(*inputs, ptr(values), ptr(address), ptr(address2id), ptr(ids), n_data, n_query,
                                         n_probe, self.m, k, n_split, ptr(ws), ws_bytes, *tail, stream_ptr(device))
+                self._last_products = lib.tpq_ivfpq_scan_last_cell_products()
             finally:
                 lib.tpq_ivfpq_scan_use_cell_threshold(before)
+                lib.tpq_ivfpq_scan_use_cell_single_product(before_sp)
             if rc != 0 and ticketed:
                 self._drop_tickets(device)
             check(rc, name)
@@ -376,13 +387,16 @@ class IVFPQTopkHip:
 
     def topk_fused(self, data, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
                    n_candidates, distance="euclidean", packed=None, address2id=None, n_split=None,
-                   slots_hint=None, cells=None, n_cells=0, cell_threshold=True, kept=None):
+                   slots_hint=None, cells=None, n_cells=0, cell_threshold=True, kept=None, cell_single_product=True):
         """precompute_adc + topk in one pass: the LUT is built inside the scan workgroups
         (query [d, n_query] f32, codebook [m, ds, 256] f32); results identical to
         topk(precomputed=AdcLutHip()(query, codebook)).  `cells` [n_query, max_n_probe] int64 -- the probed cells
         behind cell_start / cell_size, ids in [0, n_cells) -- lets a cell-dense large batch at m = 64 take the
         cell-major form (tpq_ivfpq_search_fused_cells; `last_cell_major()`): same results.  `cell_threshold=False`
         keeps that form to its seeded variant (tpq_ivfpq_scan_use_cell_threshold; `last_cell_threshold()`).
+        `cell_single_product=False` keeps the threshold form's selection key on three fp16 products per k-step
+        (tpq_ivfpq_scan_use_cell_single_product; `last_cell_products()`): same results, a narrower band -- for data with
+        many rows within the single product's band of the k-th best, whose lists would overflow.
         `kept`: a callable (n_bytes, device) -> CellKeptState or None, asked only when the call takes that form with slot
         norms: the state of what the form derives from `data`, `codebook` and `is_empty` alone, built by the first call
         that finds it not valid and read by the others (tpq_ivfpq_search_fused_cells_kept; `last_cell_kept`: "built",
@@ -410,7 +424,7 @@ class IVFPQTopkHip:
             require_gpu(cells)
             return self._scan("tpq_ivfpq_search_fused_cells", inputs, data, cell_start, address2id, n_candidates,
                               n_split, slots_hint, packed, True, cells=cells, n_cells=n_cells, cell_threshold=cell_threshold,
-                              kept=kept, ds=ds, has_lut=False)
+                              kept=kept, cell_single_product=cell_single_product, ds=ds, has_lut=False)
         return self._scan("tpq_ivfpq_search_fused_tickets", inputs, data, cell_start, address2id, n_candidates,
                           n_split, slots_hint, packed, True, ds=ds, has_lut=False)
 
