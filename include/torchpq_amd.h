@@ -1167,6 +1167,54 @@ int tpq_flat_range_fill(const float* vectors, const float* query, const int64_t*
                         const int64_t* offsets, float* out_vals, int64_t* out_addr, int64_t* out_ids,
                         int64_t n_slots, int d, int nq, int metric, int n_parts, tpq_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * FlatIndex filtered exact search: tpq_flat_topk and tpq_flat_range_count / _fill among the slots a row of filter
+ * bits allows (no reference counterpart).  The work scales with the number of allowed slots: a workgroup compacts
+ * the set bits of its slot range into a list of addresses and runs the similarity tiles on those gathered rows.
+ * vectors, query, address2id, the outputs, n_slots, d, nq, k, metric, n_parts, threshold, counts and offsets are
+ * those of the unfiltered calls.
+ *
+ * filter_bits          u32 [n_filters][filter_stride_words]   bit (s & 31) of word (s >> 5) of a row: slot s is allowed
+ *                      (the rows of tpq_slot_filter_build); filter_stride_words >= ceil(n_slots / 32); bits at or
+ *                      beyond n_slots are ignored
+ * query_order          i32 [nq]             a permutation of the queries: the groups' members, group after group
+ * group_begin          i32 [n_groups + 1]   group g is query_order[group_begin[g] : group_begin[g + 1]], 1 ... 128 queries
+ * group_row            i32 [n_groups]       the row of filter_bits all of the group's queries use; a row outside
+ *                                           [0, n_filters) allows nothing
+ * Every query of the call is in exactly one group (the caller's duty: a query in no group gets no result, its
+ * outputs and counts are not written).  One workgroup per (group, slot range); lists, counts, offsets and outputs are
+ * indexed by the query's own number, nothing is permuted in memory.
+ *
+ * Contract: the result of every query is what the unfiltered call returns with every slot its row does not allow
+ * tombstoned (address2id < 0) -- the values of tpq_flat_topk (the same fmaf chains: the same bits), its order (value
+ * descending, address ascending) and pads (-inf, -1, -1) for tpq_flat_topk_filtered; the hits, address order and
+ * two-pass protocol of tpq_flat_range_count / _fill for the range pair (segments: tpq_flat_range_segments(nq, n_parts),
+ * every one written by the count pass).  It holds for any n_parts and any grouping.  A slot must be allowed AND live:
+ * liveness is read after the bits, so a stale bit over a tombstone surfaces nothing.
+ * The checks of the unfiltered calls, and n_filters >= 1, filter_stride_words >= ceil(n_slots / 32),
+ * ceil(nq / 128) <= n_groups <= nq (for nq > 0), else TPQ_ERR_INVALID_ARGUMENT.  workspace of the top-k:
+ * tpq_flat_topk_workspace_bytes(nq, k, n_parts).  Two launches (top-k) and one per range pass whatever the number of
+ * rows and groups; no global atomics, deterministic.  The library allocates nothing.
+ * ------------------------------------------------------------------------- */
+#define TPQ_HAS_FLAT_FILTERED 1
+int tpq_flat_topk_filtered(const float* vectors, const float* query, const int64_t* address2id,
+                           const uint32_t* filter_bits, int64_t filter_stride_words, int n_filters,
+                           const int32_t* query_order, const int32_t* group_begin, const int32_t* group_row,
+                           int n_groups, float* out_vals, int64_t* out_addr, int64_t* out_ids, int64_t n_slots, int d,
+                           int nq, int k, int metric, int n_parts, void* workspace, size_t workspace_bytes,
+                           tpq_stream_t stream);
+int tpq_flat_range_filtered_count(const float* vectors, const float* query, const int64_t* address2id,
+                                  const uint32_t* filter_bits, int64_t filter_stride_words, int n_filters,
+                                  const int32_t* query_order, const int32_t* group_begin, const int32_t* group_row,
+                                  int n_groups, const float* threshold, int32_t* counts, int64_t n_slots, int d, int nq,
+                                  int metric, int n_parts, tpq_stream_t stream);
+int tpq_flat_range_filtered_fill(const float* vectors, const float* query, const int64_t* address2id,
+                                 const uint32_t* filter_bits, int64_t filter_stride_words, int n_filters,
+                                 const int32_t* query_order, const int32_t* group_begin, const int32_t* group_row,
+                                 int n_groups, const float* threshold, const int64_t* offsets, float* out_vals,
+                                 int64_t* out_addr, int64_t* out_ids, int64_t n_slots, int d, int nq, int metric,
+                                 int n_parts, tpq_stream_t stream);
+
 /* Measurement utility (no reference counterpart): streams `bytes` of `src` through 16-byte
  * loads from `n_blocks` workgroups of 256 threads (0 = 8 per CU) and discards them.  bench.py
  * times it on a buffer larger than the 256 MiB Infinity Cache to obtain the box's sustained HBM

@@ -154,6 +154,13 @@ SIGNATURES = {
     "tpq_flat_range_segments": (_sz, [_i, _i]),
     "tpq_flat_range_count": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "tpq_flat_range_fill": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    # (vectors, query, address2id, filter_bits, stride, n_filters, query_order, group_begin, group_row, n_groups, ...)
+    "tpq_flat_topk_filtered": (_i, [_vp] * 4 + [_i64, _i] + [_vp] * 3 + [_i] + [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i,
+                                                                                _vp, _sz, _vp]),
+    "tpq_flat_range_filtered_count": (_i, [_vp] * 4 + [_i64, _i] + [_vp] * 3 + [_i] + [_vp, _vp, _i64, _i, _i, _i, _i,
+                                                                                       _vp]),
+    "tpq_flat_range_filtered_fill": (_i, [_vp] * 4 + [_i64, _i] + [_vp] * 3 + [_i] + [_vp] * 5 + [_i64, _i, _i, _i, _i,
+                                                                                                  _vp]),
     "tpq_ubench_stream_read": (_i, [_vp, _sz, _vp, _i, _vp]),
     "tpq_ubench_stream_read_ex": (_i, [_vp, _sz, _vp, _i, _i, _i, _sz, _i, _vp]),
     "tpq_ubench_rows_read": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp]),

@@ -4,7 +4,9 @@ over container/FlatContainer.py).  SURVEY 8(f) rank 4: the ground-truth generato
 search = one library GEMM (rocBLAS, as the reference uses cuBLAS) + the HIP row top-k select
 (tpq_topk_select) + address->id; with `use_fused_search = True` one fused HIP similarity + top-k
 (tpq_flat_topk) that never forms the [n_query, capacity] matrix.  range_search = the same HIP similarity tiles with a
-count and a fill pass (tpq_flat_range_count / tpq_flat_range_fill).  Storage is the reference's dense `_storage [d, capacity, 1]`
+count and a fill pass (tpq_flat_range_count / tpq_flat_range_fill).  search_filtered / range_search_filtered = the same
+two among the ids an IdFilter allows, on gathered tiles (tpq_flat_topk_filtered, tpq_flat_range_filtered_count / _fill):
+exact over the whole database, the work following the number of allowed slots.  Storage is the reference's dense `_storage [d, capacity, 1]`
 with `_address2id`; vectors are appended, removed slots are tombstoned (id -1) and reused.
 """
 import torch
@@ -12,7 +14,8 @@ import torch
 from .. import metric, util
 from ..container.BaseContainer import BaseContainer
 from ..fn import Topk
-from ..kernels import FlatRangeHip, FlatTopkHip
+from ..kernels import FlatRangeFilteredHip, FlatRangeHip, FlatTopkFilteredHip, FlatTopkHip
+from ._filter import IdFilter, checked_filter_rows
 from ._range import sort_range_hits
 
 
@@ -47,11 +50,14 @@ class FlatIndex(BaseContainer):
         else:
             raise NotImplementedError(f"unknown distance metric: {distance}")
         self._n_items = 0
+        self._codes_version = 0      # bumped whenever slots change hands: what an IdFilter's bit rows are valid for
         self.register_buffer("_storage", torch.zeros(d_vector, self.initial_size, 1, device=device,
                                                      dtype=torch.float32))
         self._topk = Topk()
         self._flat_topk = FlatTopkHip()
         self._flat_range = FlatRangeHip()
+        self._flat_topk_filtered = FlatTopkFilteredHip()
+        self._flat_range_filtered = FlatRangeFilteredHip()
 
     @property
     def n_items(self):
@@ -60,6 +66,11 @@ class FlatIndex(BaseContainer):
     def _after_load_state_dict(self):
         super()._after_load_state_dict()
         self._n_items = int((self._address2id >= 0).sum().item())
+        self._codes_version += 1
+
+    def empty(self):
+        super().empty()
+        self._codes_version += 1
 
     def _grow_to(self, needed):
         cap = self.capacity
@@ -76,6 +87,7 @@ class FlatIndex(BaseContainer):
         del self._storage, self._address2id
         self.register_buffer("_storage", storage)
         self.register_buffer("_address2id", a2i)
+        self._codes_version += 1
 
     def add(self, x, ids=None, return_address=False):
         """x [d_vector, n] f32; ids default arange + max_id + 1; free slots are filled in order."""
@@ -96,6 +108,7 @@ class FlatIndex(BaseContainer):
         self._address2id[free] = ids
         self._max_id = max(self._max_id, ids.max().item())
         self._n_items += n
+        self._codes_version += 1
         self._drop_inverse_id_mapping()
         return (ids, free) if return_address else ids
 
@@ -112,6 +125,7 @@ class FlatIndex(BaseContainer):
         self._address2id[address] = -1
         self._storage[:, address] = 0
         self._n_items -= address.shape[0]
+        self._codes_version += 1
         self._drop_inverse_id_mapping()
 
     def search(self, x, k=1, return_address=False):
@@ -192,6 +206,81 @@ class FlatIndex(BaseContainer):
             thr = threshold[q0:q0 + self.max_query_batch] if torch.is_tensor(threshold) else threshold
             lb, vb, ab, ib = self._flat_range(storage, x[:, q0:q0 + self.max_query_batch].contiguous(), thr,
                                               address2id=self._address2id, distance=self.distance)
+            lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
+            vals.append(vb)
+            ids.append(ib)
+            address.append(ab)
+            total += vb.numel()
+        lims = torch.cat(lims)
+        if vals:
+            vals, ids, address = torch.cat(vals), torch.cat(ids), torch.cat(address)
+        else:
+            vals = torch.empty(0, device=self.device, dtype=torch.float32)
+            ids, address = (torch.empty(0, device=self.device, dtype=torch.int64) for _ in range(2))
+        if sort:
+            vals, ids, address = sort_range_hits(lims, vals, ids, address)
+        return (lims, vals, ids, address) if return_address else (lims, vals, ids)
+
+    def id_filter(self, ids):
+        """ids: an int64 tensor -- one set of allowed ids -- or a sequence of them, one filter row each -> IdFilter,
+        what search_filtered and range_search_filtered take.  Ids the index does not hold are ignored; the filter
+        follows later add / remove."""
+        return IdFilter(self, ids)
+
+    def _filtered_batches(self, x, flt, filter_of_query):
+        """what the two filtered searches share: the checks, the "cosine" normalisation of _search_fused, then
+        (q0, queries, rows or None) per batch of max_query_batch -> (storage, bits, batches)"""
+        d_vector, n_query = x.shape
+        assert d_vector == self.d_vector
+        assert util.check_dtype(x, "float32")
+        x = x.to(self.device)
+        rows = checked_filter_rows(self, x, flt, filter_of_query)
+        if self.distance == "cosine":
+            x = x / (x.norm(dim=-2, keepdim=True) + 1e-8)
+        step = self.max_query_batch
+        batches = [(q0, x[:, q0:q0 + step].contiguous(), None if rows is None else rows[q0:q0 + step])
+                   for q0 in range(0, max(n_query, 1), step)]
+        return self._fused_vectors(), flt.bits(self), batches
+
+    def search_filtered(self, x, k, flt, filter_of_query=None, return_address=False):
+        """The k best stored vectors among the ids `flt` (`self.id_filter(ids)`) allows, exactly: the whole database is
+        considered.  x [d_vector, n_query] f32 -> (values [n_query, min(k, capacity)] descending, ids[, address]),
+        (-inf, -1) where fewer are allowed.  `filter_of_query`: an int tensor [n_query], the row of `flt` every query
+        uses (None: row 0); a row outside [0, n_filters) allows nothing.  Always the HIP route
+        (tpq_flat_topk_filtered), whatever use_fused_search says, with that route's values, its "cosine" normalisation
+        and its limit: min(k, capacity) > 1024 raises ValueError.  The result is what search() under use_fused_search
+        returns once every disallowed id is removed.  One tile launch and one merge per batch of max_query_batch,
+        however many rows it names; with `filter_of_query` given, the rows are read on the host once per batch."""
+        assert k >= 1
+        k = min(k, self.capacity)
+        if k > 1024:
+            raise ValueError(f"FlatIndex.search_filtered: min(k, capacity) = {k} is beyond the fused kernel's limit "
+                             "of 1024")
+        storage, bits, batches = self._filtered_batches(x, flt, filter_of_query)
+        parts = [self._flat_topk_filtered(storage, xb, k, bits, rows, address2id=self._address2id,
+                                          distance=self.distance) for _, xb, rows in batches]
+        topk_val, topk_address, topk_ids = parts[0] if len(parts) == 1 else (torch.cat(t, dim=0) for t in zip(*parts))
+        if return_address:
+            return topk_val, topk_ids, topk_address
+        return topk_val, topk_ids
+
+    def range_search_filtered(self, x, threshold, flt, filter_of_query=None, return_address=False, sort=False):
+        """range_search among the ids `flt` allows: (lims, values, ids[, address]) as range_search returns them --
+        every allowed stored vector whose value is >= threshold, exactly, in address order or, with sort=True, by value
+        descending.  `flt` and `filter_of_query` as in search_filtered.  tpq_flat_range_filtered_count / _fill: one
+        count and one fill launch per batch of max_query_batch; synchronises per batch for the number of hits and,
+        with `filter_of_query` given, once more for the rows."""
+        n_query = x.shape[1]
+        if torch.is_tensor(threshold):
+            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+            threshold = threshold.to(self.device)
+        storage, bits, batches = self._filtered_batches(x, flt, filter_of_query)
+        lims = [torch.zeros(1, device=self.device, dtype=torch.int64)]
+        vals, ids, address, total = [], [], [], 0
+        for q0, xb, rows in batches:
+            thr = threshold[q0:q0 + self.max_query_batch] if torch.is_tensor(threshold) else threshold
+            lb, vb, ab, ib = self._flat_range_filtered(storage, xb, thr, bits, rows, address2id=self._address2id,
+                                                       distance=self.distance)
             lims.append(lb[1:] + total)          # a later batch's segments start where the earlier ones end
             vals.append(vb)
             ids.append(ib)

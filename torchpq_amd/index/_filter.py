@@ -1,6 +1,7 @@
 """Id filters for filtered search (IVFPQIndex.search_filtered, IVFPQ4Index.search_filtered, IVFFlatIndex.search_filtered /
-range_search_filtered): sets of ids kept over the container's slot addresses in the form the index's list scan tests --
-rows of bits for IVFPQIndex (csrc/scan_filtered.hip) and IVFPQ4Index (csrc/scan_pq4_filtered.hip), rows of skip bytes
+range_search_filtered, FlatIndex.search_filtered / range_search_filtered): sets of ids kept over the container's slot
+addresses in the form the index's kernels test -- rows of bits for IVFPQIndex (csrc/scan_filtered.hip), IVFPQ4Index
+(csrc/scan_pq4_filtered.hip) and FlatIndex (csrc/flat_filtered.hip, which gathers the set bits), rows of skip bytes
 for IVFFlatIndex (the `is_empty` mask of csrc/scan_flat.hip)."""
 import torch
 
@@ -15,7 +16,8 @@ class IdFilter:
     look-up, and built again whenever the container's `_codes_version` has moved: add, remove, growth and compaction
     all move addresses or liveness, so a filter made before an add stays correct after it.  Ids the container does not
     hold are ignored (a later add of such an id makes it count).  `bits()` is what the filtered scans of IVFPQIndex
-    and IVFPQ4Index read;
+    and IVFPQ4Index and the filtered exact search of FlatIndex read (FlatIndex keeps a `_codes_version` of its own for
+    it, and has no `_is_empty`: `masks()` is not for it);
     `masks()` is the same sets as skip masks, uint8 [n_filters, capacity], which IVFFlatIndex hands its list scan and
     its range search in the place of the tombstones -- kept and rebuilt by the same rule."""
 

@@ -8,12 +8,13 @@ CHUNK = 256          # slots per chunk of the tile kernel (kCsRows, csrc/sims_ch
 QUERY_BLOCK = 128    # queries per workgroup
 
 
-def flat_parts(n_query, n_slots, n_cus):
+def flat_parts(n_query, n_slots, n_cus, groups=None):
     """Slot ranges per query (n_parts of tpq_flat_topk).  The tile kernel's LDS (its 128 per-query queues) admits one
     workgroup per CU, so the grid -- ceil(n_query / 128) x n_parts workgroups -- should come close to a whole number of
     rounds over the CUs: the fewest parts that fill >= 85 % of their rounds (every further part is one more list per
-    query to warm up and to merge), else the best filling among up to two rounds' worth; at least one chunk per part."""
-    groups = -(-n_query // QUERY_BLOCK)
+    query to warm up and to merge), else the best filling among up to two rounds' worth; at least one chunk per part.
+    `groups`: the workgroups per part where they are not ceil(n_query / 128) (the filtered search's query groups)."""
+    groups = -(-n_query // QUERY_BLOCK) if groups is None else groups
     chunks = max(1, -(-n_slots // CHUNK))
     most = max(1, min(1024, chunks, (2 * n_cus) // groups))
     best, best_fill = 1, 0.0
@@ -77,13 +78,13 @@ RANGE_BLOCKS_PER_CU = 2   # workgroups of the range kernels a CU holds (256 regi
 RANGE_ROUNDS = 4          # ... and how many times over the grid should fill them
 
 
-def flat_range_parts(n_query, n_slots, n_cus):
+def flat_range_parts(n_query, n_slots, n_cus, groups=None):
     """Slot ranges per query (n_parts of tpq_flat_range_count / _fill).  A part costs one counter per query and
     nothing else -- no list to warm up, none to merge -- and the fill pass skips every workgroup whose 128 segments are
     empty, so parts are made fine rather than few: the fewest parts that give RANGE_ROUNDS x RANGE_BLOCKS_PER_CU x n_cus
     workgroups (the grid is ceil(n_query / 128) x n_parts; four rounds keep the last, partly filled round a small share
-    of the call), at least one 256-slot chunk per part, at most 1024 parts."""
-    groups = -(-n_query // QUERY_BLOCK)
+    of the call), at least one 256-slot chunk per part, at most 1024 parts.  `groups`: as flat_parts."""
+    groups = -(-n_query // QUERY_BLOCK) if groups is None else groups
     chunks = max(1, -(-n_slots // CHUNK))
     want = -(-(RANGE_ROUNDS * RANGE_BLOCKS_PER_CU * n_cus) // max(groups, 1))
     return max(1, min(1024, chunks, want))
@@ -150,4 +151,139 @@ class FlatRangeHip:
         ids = torch.empty(total, device=device, dtype=torch.int64) if address2id is not None else None
         if total:
             call("tpq_flat_range_fill", device, *inputs, ptr(offsets), ptr(values), ptr(address), ptr(ids), *shape)
+        return offsets[::n_parts].contiguous(), values, address, ids
+
+
+def flat_filter_groups(rows, n_query, n_filters, device="cpu"):
+    """The group tables of the filtered kernels (csrc/flat_filtered.hip): (query_order int32 [n_query], group_begin
+    int32 [n_groups + 1], group_row int32 [n_groups]) on `device`.  A group is at most 128 queries of one filter row,
+    query_order[group_begin[g]:group_begin[g + 1]]; every query is in exactly one group.
+      rows None: every query uses row 0 -- the identity order, cut into 128s, made on `device` without a host copy.
+      rows [n_query] integers: a stable sort of the queries by row, each row's run cut into 128s; a row outside
+      [0, n_filters) becomes -1 (it allows nothing).  The rows are read on the host: one synchronisation."""
+    if rows is None:
+        order = torch.arange(n_query, device=device, dtype=torch.int32)
+        n_groups = -(-n_query // QUERY_BLOCK)
+        begin = (torch.arange(n_groups + 1, device=device, dtype=torch.int32) * QUERY_BLOCK).clamp(max=n_query)
+        return order, begin, torch.zeros(n_groups, device=device, dtype=torch.int32)
+    rows = torch.as_tensor(rows).to("cpu", torch.int64)
+    assert rows.shape == (n_query,)
+    rows = torch.where((rows >= 0) & (rows < n_filters), rows, -1)
+    order = torch.argsort(rows, stable=True)
+    run_row, run_len = torch.unique_consecutive(rows[order], return_counts=True)
+    run_start = torch.cumsum(run_len, 0) - run_len
+    per_run = (run_len + QUERY_BLOCK - 1) // QUERY_BLOCK                   # groups of every run
+    run_of = torch.repeat_interleave(torch.arange(run_row.numel()), per_run)
+    nth = torch.arange(run_of.numel()) - (torch.cumsum(per_run, 0) - per_run)[run_of]   # group within its run
+    begin = torch.nn.functional.pad(run_start[run_of] + QUERY_BLOCK * nth, (0, 1), value=n_query)
+    return tuple(t.to(device=device, dtype=torch.int32) for t in (order, begin, run_row[run_of]))
+
+
+def _filtered_call_inputs(vectors, query, address2id, bits, rows, distance):
+    """the checks the two filtered wrappers share -> (vectors [d, n_slots], query, the group tables, the filter's arguments)"""
+    if vectors.dim() == 3:
+        assert vectors.shape[2] == 1
+        vectors = vectors[:, :, 0]
+    d, n_slots = vectors.shape
+    assert query.dim() == 2 and query.shape[0] == d and d >= 1
+    assert vectors.dtype == query.dtype == torch.float32
+    if address2id is not None:
+        assert address2id.shape == (n_slots,) and address2id.dtype == torch.int64
+    assert distance in ("euclidean", "cosine", "inner")
+    assert bits.dim() == 2 and bits.dtype == torch.int32 and bits.shape[0] >= 1 and bits.shape[1] * 32 >= n_slots
+    bits, query = bits.contiguous(), query.contiguous()
+    require_gpu(vectors, query, address2id, bits)
+    groups = flat_filter_groups(rows, query.shape[1], bits.shape[0], vectors.device)
+    return vectors, query, groups, (ptr(bits), bits.shape[1], bits.shape[0])
+
+
+class FlatTopkFilteredHip:
+    """tpq_flat_topk_filtered (csrc/flat_filtered.hip): FlatTopkHip among the slots a row of filter bits allows -- the
+    kernel compacts the allowed addresses of a slot range and runs the similarity tiles on those gathered rows, so the
+    work follows the number of allowed slots.  The result is FlatTopkHip's with every disallowed slot tombstoned, bit
+    for bit, for any n_parts and any grouping.  One launch of the tile kernel and one of the merge per call, however
+    many rows the batch names."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_parts = None   # diagnostics / tests: slot ranges per query of the last call
+        self.last_n_groups = None  # ... and its query groups
+
+    def __call__(self, vectors, query, k, bits, rows=None, address2id=None, distance="euclidean", n_parts=None):
+        """
+          vectors, query, k, address2id, distance, n_parts: as FlatTopkHip
+          bits: [n_filters, >= ceil(n_slots / 32)] int32, what IdFilter.bits() returns
+          rows: None (every query uses row 0) or [n_query] integers, the row of each query; a row outside the filter
+                allows nothing.  Given, they are read on the host: one synchronisation per call.
+        returns FlatTopkHip's (values, address, ids)
+        """
+        vectors, query, (order, begin, grow), filt = _filtered_call_inputs(vectors, query, address2id, bits, rows, distance)
+        (d, n_slots), n_query, device = vectors.shape, query.shape[1], vectors.device
+        assert 0 < k <= 1024
+        values, address, ids = alloc_topk(n_query, k, device, address2id)
+        if n_query == 0:
+            return values, address, ids
+        n_groups = grow.numel()
+        if n_parts is None:
+            if self.n_cus is None:
+                self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+            n_parts = flat_parts(n_query, n_slots, self.n_cus, groups=n_groups)
+        self.last_n_parts, self.last_n_groups = n_parts, n_groups
+        ws_bytes = load().tpq_flat_topk_workspace_bytes(n_query, k, n_parts)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8)
+        call("tpq_flat_topk_filtered", device, ptr(vectors), ptr(query), ptr(address2id), *filt, ptr(order), ptr(begin),
+             ptr(grow), n_groups, ptr(values), ptr(address), ptr(ids), n_slots, d, n_query, k, metric_code(distance),
+             n_parts, ptr(ws), ws_bytes)
+        return values, address, ids
+
+
+class FlatRangeFilteredHip:
+    """tpq_flat_range_filtered_count / _fill (csrc/flat_filtered.hip): FlatRangeHip among the slots a row of filter bits
+    allows, on the gathered tiles of FlatTopkFilteredHip.  The result is FlatRangeHip's with every disallowed slot
+    tombstoned, bit for bit.  One count launch and one fill launch per call, however many rows the batch names."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_parts = None
+        self.last_n_groups = None
+
+    def __call__(self, vectors, query, threshold, bits, rows=None, address2id=None, distance="euclidean", n_parts=None):
+        """vectors, query, threshold, address2id, distance, n_parts: as FlatRangeHip; bits, rows: as
+        FlatTopkFilteredHip.  Returns FlatRangeHip's (lims, values, address, ids).  Synchronises for the number of
+        hits and, with `rows` given, once more to read them."""
+        vectors, query, (order, begin, grow), filt = _filtered_call_inputs(vectors, query, address2id, bits, rows, distance)
+        (d, n_slots), n_query, device = vectors.shape, query.shape[1], vectors.device
+        per_query = torch.is_tensor(threshold)
+        if per_query:
+            assert threshold.shape == (n_query,) and threshold.dtype == torch.float32
+            threshold = threshold.contiguous()
+            require_gpu(threshold)
+        else:
+            threshold = torch.full((n_query,), float(threshold), device=device, dtype=torch.float32)
+        if n_query == 0:
+            empty = torch.empty(0, device=device, dtype=torch.int64)
+            return (torch.zeros(1, device=device, dtype=torch.int64),
+                    torch.empty(0, device=device, dtype=torch.float32), empty,
+                    None if address2id is None else empty.clone())
+        n_groups = grow.numel()
+        if n_parts is None:
+            if self.n_cus is None:
+                self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+            n_parts = flat_range_parts(n_query, n_slots, self.n_cus, groups=n_groups)
+        self.last_n_parts, self.last_n_groups = n_parts, n_groups
+        n_seg = load().tpq_flat_range_segments(n_query, n_parts)
+        assert n_seg == n_query * n_parts, (n_query, n_parts)
+        inputs = (ptr(vectors), ptr(query), ptr(address2id), *filt, ptr(order), ptr(begin), ptr(grow), n_groups,
+                  ptr(threshold))
+        shape = (n_slots, d, n_query, metric_code(distance), n_parts)
+        counts = torch.empty(n_seg, device=device, dtype=torch.int32)
+        call("tpq_flat_range_filtered_count", device, *inputs, ptr(counts), *shape)
+        offsets = torch.zeros(n_seg + 1, device=device, dtype=torch.int64)
+        offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(offsets[-1].item())     # the host sync a variable-size output needs
+        values = torch.empty(total, device=device, dtype=torch.float32)
+        address = torch.empty(total, device=device, dtype=torch.int64)
+        ids = torch.empty(total, device=device, dtype=torch.int64) if address2id is not None else None
+        if total:
+            call("tpq_flat_range_filtered_fill", device, *inputs, ptr(offsets), ptr(values), ptr(address), ptr(ids), *shape)
         return offsets[::n_parts].contiguous(), values, address, ids
