@@ -709,6 +709,55 @@ int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_
                           int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFFlatIndex list scan + top-k, large batches, CELL-MAJOR (csrc/scan_flat_cells.hip): the outputs of
+ * tpq_ivfflat_scan_topk -- values, addresses, order and pads, bit for bit -- with a probed cell's vectors read once
+ * per block of 128 of the queries that list it instead of once per query.  Stage 1 is tpq_ivfflat_scan_topk over each
+ * query's first `first_probe` probes (their exact top-k lands in the outputs and its k-th value is the query's
+ * threshold); the pairs (query, later probe) are grouped by cell; an fp32-MFMA kernel appends to the query's candidate
+ * list every live slot whose fast value is not below threshold - band (the band is derived in the unit's head); a
+ * finish kernel re-evaluates the candidates with the chain defined above and selects with the seeds of stage 1.
+ *
+ * vectors, query, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, n_slots, d, nq, max_nprobe,
+ * metric: as tpq_ivfflat_scan_topk.
+ * cells        i64 [nq][max_nprobe]  the probed cells behind cell_start / cell_size, values in [0, n_cells); all
+ *                                    queries list a cell with the same extent
+ * first_probe  >= 1                  P0: the probes of the threshold pass
+ * cand_cap     a multiple of 64      entries of a query's candidate list
+ * workspace    tpq_ivf_flat_cells_workspace_bytes(nq, max_nprobe, n_cells, k, cand_cap, first_probe) bytes (0 for
+ *              arguments the entry point declines).  It need NOT be zeroed.  Regions, each a multiple of 256 bytes, in
+ *              this order, and the kernel that writes each first:
+ *                control  i32 [64]   [0] the number of flagged queries, [1] the candidate kernel's item counter:
+ *                                    zeroed by the seed kernel; [0] counted by the finish kernel
+ *                flags    i32 [nq]   seed kernel (every query); set again by the candidate kernel on overflow
+ *                threshold f32 [nq], |q|^2 f32 [nq], candidate counter i32 [nq]   seed kernel
+ *                histogram i32 [n_cells]   zeroed by the seed kernel, counted by the count kernel, then the scatter's cursor
+ *                cell extents i32 [n_cells] x 2   scatter kernel, for the listed cells (nobody reads the others)
+ *                pair / item prefixes i32 [n_cells + 1] x 2   scan kernel
+ *                pairs    i32 [nq (max_nprobe - first_probe)]   scatter kernel
+ *                candidates i32 [nq][cand_cap]   candidate kernel, below each query's counter
+ * Flag protocol: after the call, flags[q] != 0 means row q of the outputs is NOT the result -- it holds stage 1's
+ *              top-k -- and the caller runs tpq_ivfflat_scan_topk for that query.  Flagged: a query with probes beyond
+ *              first_probe and a NaN or +-Inf component or a |q|^2 that is not finite, a threshold of +inf, a listed
+ *              cell outside [0, n_cells), or more than cand_cap candidates.  workspace int32 word 0 is their number; the
+ *              flags are the int32 [nq] at byte 256.  When max_nprobe <= first_probe nothing is flagged.
+ * TPQ_ERR_UNSUPPORTED, nothing launched: k outside [1, 256], n_slots >= 2^31 - 1, cand_cap not a multiple of 64.
+ * TPQ_ERR_WORKSPACE: a workspace that is too small.  The library allocates nothing; all launches are on `stream`.
+ * tpq_ivf_flat_cells_stop_after(stage): a measurement switch, process-wide, read on the host per call: 1 ... 4 ends the
+ *              call behind that stage (the outputs are then NOT the result), 0 -- the default -- runs all five; returns
+ *              the previous setting.
+ * (The symbols are spelled tpq_ivf_flat_cells_*: the tpq_ivfflat_* names are the query-major scan and range search, a
+ * list the signature tests pin symbol by symbol.)
+ * ------------------------------------------------------------------------- */
+#define TPQ_HAS_IVFFLAT_CELLS 1
+size_t tpq_ivf_flat_cells_workspace_bytes(int nq, int max_nprobe, int n_cells, int k, int cand_cap, int first_probe);
+int tpq_ivf_flat_cells_topk(const float* vectors, const float* query, const uint8_t* is_empty, const int64_t* cells,
+                           const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                           float* out_vals, int64_t* out_addr, int64_t n_slots, int n_cells, int d, int nq,
+                           int max_nprobe, int k, int metric, int first_probe, int cand_cap, void* workspace,
+                           size_t workspace_bytes, tpq_stream_t stream);
+int tpq_ivf_flat_cells_stop_after(int stage);
+
+/* ---------------------------------------------------------------------------
  * IVFPQ4Index list scan + top-k: product-quantized lists with 16 centroids per sub-quantizer (4-bit codes; the
  * reference began such a path, top-1 only, and has no index for it).
  *

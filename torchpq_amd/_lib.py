@@ -117,6 +117,9 @@ SIGNATURES = {
     "tpq_ivfflat_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_ivfflat_scan_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz,
                                    _vp]),
+    "tpq_ivf_flat_cells_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "tpq_ivf_flat_cells_topk": (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tpq_ivf_flat_cells_stop_after": (_i, [_i]),
     "tpq_ivfpq4_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_ivfpq4_scan_topk": (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ivfpq4_scan_residual_topk": (_i, [_vp] * 5 + [_i] + [_vp] * 6 + [_i64, _i, _i, _i, _i, _i, _i, _i, _vp, _sz,

@@ -16,7 +16,8 @@
 # row select's device code) rebuilds select, coarse_probe and probe_sims; probe_fast.h rebuilds coarse_probe and
 # probe_sims; mfma_util.h (the MFMA units' shared device helpers) rebuilds the cascade units, assign_fast, coarse_probe,
 # max_sim, centroid_update, kmeans_split, lut, flat_topk, flat_range and flat_filtered; sims_chunk.h (the fp32 similarity tile) rebuilds
-# coarse_probe, flat_topk, flat_range and flat_filtered; flat_merge.h (the exact top-k's queue size and merge kernel) rebuilds
+# coarse_probe, flat_topk, flat_range and flat_filtered; sims_rows.h (the tile on rows the caller names) rebuilds flat_filtered and
+# scan_flat_cells (the cell-major IVFFlat route), which also takes scan_list.h and, with scan_flat.hip, scan_flat_cells.h; flat_merge.h (the exact top-k's queue size and merge kernel) rebuilds
 # flat_topk and flat_filtered.  The exact assign (max_sim.hip) and the centroid update
 # (centroid_update.hip) are units of their own: a change to one does not recompile the other.
 # The library is linked from the objects of the unit list below, not from whatever build/ holds: an object left
@@ -53,14 +54,15 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_flat_cells.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   unit_flags=""
   # flat_filtered.hip is compiled with the packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) switched
   # off for the device: its epilogues are one scalar chain per value (the host pass warns that it does not know the
   # feature and ignores it; tools/kernel_regs.py takes the same flags)
-  [[ "$src" == flat_filtered.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
+  # (scan_flat_cells.hip, the cell-major IVFFlat route, likewise)
+  [[ "$src" == flat_filtered.hip || "$src" == scan_flat_cells.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
   if stale "$obj" "${HERE}/${src}"; then
     cmds+=("'$HIPCC' ${FLAGS[*]} ${unit_flags} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/${src}' -o '$obj' ${EXTRA_FLAGS:-}")
   fi

@@ -7,6 +7,7 @@
 // flat_range_walk with a tile row's slot number read from the address list.  Liveness (address2id >= 0) is tested after
 // the compaction, for allowed slots only, and becomes the chunk's live mask.  The semantics are in include/torchpq_amd.h.
 #include "flat_merge.h"
+#include "sims_rows.h"
 
 namespace tpq {
 
@@ -40,80 +41,6 @@ __device__ __forceinline__ int ff_lane_query(const FfGroups& g, int nq) {
 __device__ __forceinline__ const unsigned* ff_group_bits(const FfGroups& g) {
   const int row = g.group_row[blockIdx.x];
   return (row >= 0 && row < g.n_filters) ? g.bits + (int64_t)row * g.stride : nullptr;
-}
-
-// sims_chunk_mfma (sims_chunk.h) on gathered rows: this thread stages row `row` of C (row < 0: none; such a row's
-// |row|^2 is +inf), everything else -- the slab pipeline, the chains, what staged(cv) may do -- is that function's.
-template <class Staged>
-__device__ __forceinline__ void sims_rows_mfma(const float* __restrict__ xq, bool qvalid, const float* __restrict__ C,
-                                               int row, int d, int nq, int n_cells, float* cs, float* c2s,
-                                               f32x16 (&acc)[8], Staged&& staged) {
-  const int lane = threadIdx.x & 63;
-  const int l31 = lane & 31, half = lane >> 5;
-  const int n_slabs = (d + kCsKC - 1) / kCsKC;
-  const bool cv = row >= 0;
-  const float* __restrict__ Cc = C + (cv ? row : 0);
-  float rs[kCsKC], yc[kCsKC / 2], yn[kCsKC / 2];
-  float csq = 0.f;
-  auto load_slab = [&](int kb) {
-    const float* __restrict__ p = Cc + (int64_t)kb * n_cells;
-#pragma unroll
-    for (int u = 0; u < kCsKC; ++u) {
-      rs[u] = (cv && kb + u < d) ? *p : 0.f;
-      p += n_cells;
-    }
-  };
-  auto square_slab = [&]() {
-#pragma unroll
-    for (int u = 0; u < kCsKC; ++u) csq = fmaf(rs[u], rs[u], csq);
-  };
-  auto store_slab = [&](float* dst) {
-#pragma unroll
-    for (int u = 0; u < kCsKC; ++u) dst[u * kCsRows + threadIdx.x] = rs[u];
-  };
-  auto load_y = [&](int kb, float (&y)[kCsKC / 2]) {
-    const float* __restrict__ p = xq + (int64_t)(kb + half) * nq;
-#pragma unroll
-    for (int j = 0; j < kCsKC / 2; ++j) {
-      y[j] = (qvalid && kb + 2 * j + half < d) ? *p : 0.f;
-      p += 2 * (int64_t)nq;
-    }
-  };
-  load_slab(0);
-  load_y(0, yc);
-  __syncthreads();  // every wave finished the previous chunk (reads of cs, c2s and what staged() wrote)
-  staged(cv);
-  square_slab();
-  if (n_slabs == 1) c2s[threadIdx.x] = cv ? csq : INFINITY;
-  store_slab(cs);
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  __syncthreads();
-  for (int sb = 0; sb < n_slabs; ++sb) {
-    const float* cur = cs + (sb & 1) * kCsSlab;
-    const bool more = sb + 1 < n_slabs;
-    if (more) {
-      load_slab((sb + 1) * kCsKC);
-      load_y((sb + 1) * kCsKC, yn);
-    }
-#pragma unroll
-    for (int j = 0; j < kCsKC / 2; ++j) {
-      const float* crow = cur + (2 * j + half) * kCsRows + l31;  // A operand [row][k]
-#pragma unroll
-      for (int t = 0; t < 8; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(crow[t * 32], yc[j], acc[t], 0, 0, 0);
-    }
-    if (more) {
-      square_slab();
-      if (sb + 2 == n_slabs) c2s[threadIdx.x] = cv ? csq : INFINITY;
-      store_slab(cs + ((sb + 1) & 1) * kCsSlab);
-#pragma unroll
-      for (int j = 0; j < kCsKC / 2; ++j) yc[j] = yn[j];
-    }
-    __syncthreads();
-  }
 }
 
 // The gather.  Part blockIdx.y of the row `bits`: the slots of the 256-slot chunks [p cpp, (p + 1) cpp) below n_chunks

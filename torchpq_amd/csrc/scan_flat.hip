@@ -15,6 +15,7 @@
 //
 // Range search over the same candidates and values (tpq_ivfflat_range_count / _fill) follows the scan.
 #include "scan_device.h"
+#include "scan_flat_cells.h"
 #include "scan_ref.h"
 
 namespace tpq {
@@ -319,11 +320,13 @@ extern "C" size_t tpq_ivfflat_scan_workspace_bytes(int nq, int k, int n_split) {
   return list_ws_bytes(nq, list_regs(k), n_split);
 }
 
-extern "C" int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_t* is_empty,
-                                     const int64_t* cell_start, const int64_t* cell_size,
-                                     const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
-                                     int64_t n_slots, int d, int nq, int max_nprobe, int k, int metric, int n_split,
-                                     void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
+// tpq_ivfflat_scan_topk over each query's first min(n_probe_list[q], probe_cap) probes (ScanArgs::probe_cap; 0: no cap):
+// the threshold pass of the cell-major route (scan_flat_cells.hip) -- the same kernels, checks and launches
+int tpq::ivfflat_scan_topk_capped(const float* vectors, const float* query, const uint8_t* is_empty,
+                                  const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                  float* out_vals, int64_t* out_addr, int64_t n_slots, int d, int nq, int max_nprobe,
+                                  int k, int metric, int n_split, int probe_cap, void* workspace,
+                                  size_t workspace_bytes, tpq_stream_t stream) {
   const char* what = "ivfflat_scan";
   if (int rc = check_batch(what, nq, max_nprobe)) return rc;
   TPQ_REQUIRE(d >= 1, "ivfflat_scan: d=%d", d);
@@ -336,11 +339,21 @@ extern "C" int tpq_ivfflat_scan_topk(const float* vectors, const float* query, c
   const int R = list_regs(k);
   ScanArgs a = flat::flat_args(query, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, n_slots, nq,
                                max_nprobe, k, n_split);
+  a.probe_cap = probe_cap;
   if (int rc = take_list_ws(a, R, workspace, workspace_bytes, what)) return rc;
   const flat::FlatArgs f{vectors, d};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return metric == TPQ_METRIC_NEG_SQ_L2 ? flat::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, f, R, st)
                                         : flat::dispatch<TPQ_METRIC_INNER>(a, f, R, st);
+}
+
+extern "C" int tpq_ivfflat_scan_topk(const float* vectors, const float* query, const uint8_t* is_empty,
+                                     const int64_t* cell_start, const int64_t* cell_size,
+                                     const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
+                                     int64_t n_slots, int d, int nq, int max_nprobe, int k, int metric, int n_split,
+                                     void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
+  return ivfflat_scan_topk_capped(vectors, query, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                                  n_slots, d, nq, max_nprobe, k, metric, n_split, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t tpq_ivfflat_range_segments(int nq, int n_split) {

@@ -15,7 +15,7 @@ of its 4 d bytes of vector, so a tile without an allowed slot costs 64 bytes, no
 import torch
 
 from ..container import CellContainer
-from ..kernels import IVFFlatRangeHip, IVFFlatTopkHip
+from ..kernels import IVFFlatCellTopkHip, IVFFlatRangeHip, IVFFlatTopkHip
 from ._coarse import CoarseProbeMixin
 from ._filter import IdFilter, checked_filter_rows, filtered_search_batches, queries_by_row
 from ._range import range_search_batches
@@ -39,6 +39,13 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         self._init_coarse(n_cells, verbose)
         self._flat_topk = IVFFlatTopkHip()
         self._flat_range = IVFFlatRangeHip()
+        # the cell-major scan of large batches (csrc/scan_flat_cells.hip): the same results bit for bit, so the switch is
+        # a speed setting only; off by default.  `last_route`: "cell_major" / "query_major", the last
+        # search_cells
+        self._flat_cells = IVFFlatCellTopkHip()
+        self.use_cell_major = False
+        self.cell_major_min_batch = 1024
+        self.last_route = None
         self.to(device)
 
     def _after_load_state_dict(self):
@@ -99,10 +106,18 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
     def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
         (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
-        the coarse step already gathered them.)"""
+        the coarse step already gathered them.)  With `use_cell_major` a batch of at least `cell_major_min_batch`
+        queries with k <= 256 and more probes than the route's `first_probe` takes the cell-major scan
+        (IVFFlatCellTopkHip): the same values, ids and addresses; one host synchronisation per call."""
         n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
                                                                                         _extents)
-        vals, address = self._flat_topk(
+        cell_major = (self.use_cell_major and k <= 256 and cells.shape[1] > self._flat_cells.first_probe
+                      and x.shape[1] >= self.cell_major_min_batch)
+        self.last_route = "cell_major" if cell_major else "query_major"
+        scan = self._flat_topk
+        if cell_major:     # (one host read of the redone queries' count per call: IVFFlatCellTopkHip)
+            scan = lambda *args, **kw: self._flat_cells(*args, cells=cells, n_cells=self.n_cells, **kw)  # noqa: E731
+        vals, address = scan(
             self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, k,
             is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
         ids = self.get_id_by_address(address)

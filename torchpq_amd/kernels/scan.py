@@ -1,5 +1,5 @@
 """The list scans and what feeds them: IVFPQ top-k (plain, fused LUT, residual), the LUT and residual tables, the
-IVFPQR re-rank, the IVFFlat scan and range search, the 4-bit IVFPQ4 scan, the IVFPQ range search."""
+IVFPQR re-rank, the IVFFlat scan (query-major and cell-major) and range search, the 4-bit IVFPQ4 scan, the IVFPQ range search."""
 import torch
 
 from .._lib import check, load, ptr, require_gpu, stream_ptr
@@ -769,6 +769,78 @@ class IVFFlatTopkHip:
              ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
              ptr(values), ptr(address), n_slots, d, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
              ws_bytes)
+        return values, address
+
+
+class IVFFlatCellTopkHip:
+    """The cell-major list scan of IVFFlatIndex for large batches (tpq_ivf_flat_cells_topk, csrc/scan_flat_cells.hip):
+    the results of IVFFlatTopkHip bit for bit -- values, addresses, order, pads -- with a probed cell's vectors read
+    once per block of 128 of its queries on the fp32 matrix cores, the survivors re-evaluated exactly.
+
+    A query the library flags (a NaN or Inf component, more than `cand_cap` candidates, ...) is redone by
+    IVFFlatTopkHip: every call reads the number of flagged queries back -- ONE host synchronisation per call, so one per
+    batch of `max_query_batch` queries of an index search.  `last_redone` is that number, `last_route` "cell_major"."""
+
+    # the defaults: the fastest (first_probe, cand_cap) at 10 000 queries in profiles/ivfflat_cell_bench.json
+    FIRST_PROBE = 2
+    CAND_CAP = 1024
+
+    def __init__(self, first_probe=None, cand_cap=None):
+        self.first_probe = self.FIRST_PROBE if first_probe is None else int(first_probe)
+        self.cand_cap = self.CAND_CAP if cand_cap is None else int(cand_cap)
+        self.query_major = IVFFlatTopkHip()
+        self.last_redone = None
+        self.last_route = None
+        self.fill_workspace = None   # tests: a byte the workspace is filled with before the call (it need not be zeroed)
+        self.keep_workspace = False  # diagnostics: keep the last call's workspace in `last_workspace`
+        self.last_workspace = None
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None, distance="euclidean",
+                 cells=None, n_cells=0, first_probe=None, cand_cap=None, slots_hint=None):
+        """
+          vectors, query, cell_start, cell_size, n_probe_list, is_empty, distance: as IVFFlatTopkHip
+          cells: [n_query, max_n_probe] int64, the probed cells behind cell_start / cell_size, in [0, n_cells)
+          first_probe: probes of the query-major threshold pass (>= 1); cand_cap: candidates per query, a multiple of 64
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1); k <= 256
+        """
+        if vectors.dim() == 3:
+            assert vectors.shape[2] == 1
+            vectors = vectors[:, :, 0]
+        first_probe = self.first_probe if first_probe is None else int(first_probe)
+        cand_cap = self.cand_cap if cand_cap is None else int(cand_cap)
+        d, n_slots = vectors.shape
+        n_query, n_probe = cell_start.shape
+        assert query.shape == (d, n_query)
+        assert vectors.dtype == query.dtype == torch.float32
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+        assert cells is not None and cells.shape == (n_query, n_probe) and cells.dtype == torch.int64 and n_cells >= 1
+        assert distance in ("euclidean", "cosine", "inner")
+        assert 0 < k <= 256 and first_probe >= 1 and cand_cap >= 64 and cand_cap % 64 == 0
+        query, cells = query.contiguous(), cells.contiguous()
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(vectors, query, is_empty, cells, cell_start, cell_size, n_probe_list)
+        device = vectors.device
+        values, address = alloc_pair(n_query, k, device)
+        self.last_route, self.last_redone = "cell_major", 0
+        if n_query == 0:
+            return values, address
+        ws_bytes = load().tpq_ivf_flat_cells_workspace_bytes(n_query, n_probe, int(n_cells), k, cand_cap, first_probe)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8)
+        if self.fill_workspace is not None:
+            ws.fill_(int(self.fill_workspace))
+        call("tpq_ivf_flat_cells_topk", device,
+             ptr(vectors), ptr(query), ptr(is_empty), ptr(cells), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+             ptr(values), ptr(address), n_slots, int(n_cells), d, n_query, n_probe, k, metric_code(distance),
+             first_probe, cand_cap, ptr(ws), ws_bytes)
+        if self.keep_workspace:
+            self.last_workspace = ws
+        self.last_redone = int(ws[:4].view(torch.int32).item())      # (the host read)
+        if self.last_redone:
+            redo = ws[256:256 + 4 * n_query].view(torch.int32).nonzero()[:, 0]
+            v, a = self.query_major(vectors, query[:, redo], cell_start[redo], cell_size[redo], n_probe_list[redo], k,
+                                    is_empty=is_empty, distance=distance, slots_hint=slots_hint)
+            values[redo] = v
+            address[redo] = a
         return values, address
 
 
