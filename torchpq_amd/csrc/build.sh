@@ -4,8 +4,8 @@
 # one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
 # k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip, scan_flat.hip and
 # scan_pq4.hip alone (the 4-bit list scan takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it;
-# scan_pq4.h, its word loop and grouped tables, is shared with scan_pq4_filtered.hip, the filtered 4-bit scan, and scan_pq4_range.hip,
-# the 4-bit range search, and rebuilds those three);
+# scan_pq4.h -- the table build, the word loop, the grouped tables, the 4-bit entry points' checks and LDS sizes -- is
+# shared with scan_pq4_filtered.hip, the filtered 4-bit scan, and scan_pq4_range.hip, the 4-bit range search, and rebuilds those three);
 # scan_list.h (the frame of a list kernel) is included by scan_ref.h, scan_range.hip and, for clamped_n_probe, scan_packed_kernel.h,
 # so a change to it rebuilds every scan unit; scan_range.hip (IVFPQ range search) takes scan_list.h, scan_shared.h and
 # scan_args.h only, so the other scan headers -- the packed ones above all -- leave it alone; scan_filtered.hip (the filtered

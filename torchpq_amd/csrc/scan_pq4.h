@@ -1,6 +1,9 @@
-// The device code the 4-bit list scans share (scan_pq4.hip, scan_pq4_filtered.hip): the word loop over a 16-entry table
-// row per sub-quantizer, the grouped per-probe tables of residual codes, and the constants.  Codes, table entry and value
-// are defined in include/torchpq_amd.h; the schedule of the word loop and the group walk in DESIGN 3.13 / 3.13b.
+// What the 4-bit list scans share (scan_pq4.hip, scan_pq4_filtered.hip, scan_pq4_range.hip), each piece written once:
+// the query's table (build_lut), the word loop over a 16-entry table row per sub-quantizer (code_value), the grouped
+// per-probe tables of residual codes (stage_cells, build_group_luts; their walk stays written out in the two kernels
+// that make it, scan_pq4.hip says why), the constants, and the host's payload sizes, argument checks and ScanArgs.
+// Codes, table entry and value are defined in include/torchpq_amd.h; the schedule of the word loop and the group walk
+// in DESIGN 3.13 / 3.13b.
 #pragma once
 #include "scan_device.h"
 #include "scan_ref.h"
@@ -51,6 +54,45 @@ __device__ __forceinline__ float add_words(float v, const uint32_t* __restrict__
   return v;
 }
 
+// the value of the slot whose words start at `col`, looked up in the m x 16 table at `row`: eight words in flight, then
+// the last W mod 8 words, still in ascending order: four, two, one
+__device__ __forceinline__ float code_value(const uint32_t* __restrict__ col, int64_t stride, const float* row, int W) {
+  float v = 0.f;
+  int w = 0;
+  for (; w + kPq4Unroll <= W; w += kPq4Unroll) {
+    v = add_words<kPq4Unroll>(v, col, stride, row);
+    col += (int64_t)kPq4Unroll * stride;
+    row += kPq4Unroll * 128;
+  }
+  if (W & 4) {
+    v = add_words<4>(v, col, stride, row);
+    col += 4 * stride;
+    row += 4 * 128;
+  }
+  if (W & 2) {
+    v = add_words<2>(v, col, stride, row);
+    col += 2 * stride;
+    row += 2 * 128;
+  }
+  if (W & 1) v = add_words<1>(v, col, stride, row);
+  return v;
+}
+
+// The query's m x 16 table: thread t takes entries t, t + 512, ... -- sixteen consecutive threads write one row, and
+// read sixteen consecutive floats of the codebook per dimension; one metric_step chain per entry, i ascending from 0.f
+template <int METRIC>
+__device__ __forceinline__ void build_lut(const ScanArgs& a, const float* xq, float* lut) {
+  const int ds = a.ds;
+  for (int e = threadIdx.x; e < a.m * 16; e += kScanThreads) {
+    const int j = e >> 4;
+    const float* __restrict__ cb = a.codebook + (int64_t)j * ds * 16 + (e & 15);
+    const float* xj = xq + j * ds;
+    float acc = 0.f;
+    for (int i = 0; i < ds; ++i) acc = metric_step<METRIC>(acc, xj[i], cb[i * 16]);
+    lut[e] = acc;
+  }
+}
+
 // ---- residual codes: the table changes with the probe -------------------------------------------------------------
 struct ResidualProbes {
   const float* centroids;  // [n_cells][d]
@@ -76,8 +118,18 @@ __device__ __forceinline__ int next_scanned_probe(const ProbeTable& tab, int p, 
   return n_probe;
 }
 
+// a probe's cell index (one outside [0, n_cells) is the caller's error: clamped, so that nothing outside `centroids` is
+// read), and the cell indices of query q's probes staged into LDS (no barrier: the caller's next one publishes them)
+__device__ __forceinline__ int clamp_cell(int64_t c, int n_cells) {
+  return c < 0 ? 0 : (c >= n_cells ? n_cells - 1 : (int)c);
+}
+__device__ __forceinline__ void stage_cells(const ScanArgs& a, const ResidualProbes& rp, int q, int n_probe, int* cell) {
+  for (int p = threadIdx.x; p < n_probe; p += kScanThreads)
+    cell[p] = clamp_cell(rp.cells[(int64_t)q * a.max_nprobe + p], rp.n_cells);
+}
+
 // The tables of probes g0 ... g0 + cnt - 1 (cnt <= kMaxGroup), table g at lut + g * m * 16: thread t takes entries t,
-// t + 512, ... of every table, as in scan_pq4_kernel; the sixteen threads of a row read the same centroid components
+// t + 512, ... of every table, as in build_lut; the sixteen threads of a row read the same centroid components
 // (one address per probe) and sixteen consecutive floats of the codebook per dimension.  `cell` holds the probes'
 // cell indices, clamped to [0, n_cells) when they were staged.
 template <int METRIC>
@@ -112,28 +164,69 @@ __device__ __forceinline__ void build_group_luts(const ScanArgs& a, const float*
   }
 }
 
-// the value of the slot whose words start at `col`: scan_pq4_kernel's word loop (kept apart from it: that kernel's code
-// is not touched by this one)
-__device__ __forceinline__ float code_value(const uint32_t* __restrict__ col, int64_t stride, const float* row, int W) {
-  float v = 0.f;
-  int w = 0;
-  for (; w + kPq4Unroll <= W; w += kPq4Unroll) {
-    v = add_words<kPq4Unroll>(v, col, stride, row);
-    col += (int64_t)kPq4Unroll * stride;
-    row += kPq4Unroll * 128;
+// ---- host ----------------------------------------------------------------------------------------------------------
+// the payload in front of a kernel's LDS: the query's table, or two buffers of a group's tables; and region0 of a top-k
+// kernel, which the finisher's lists share with it
+__host__ __device__ constexpr size_t table_bytes(int m) { return (size_t)m * 64; }
+static size_t payload_bytes(bool residual, int m, int max_nprobe) {
+  return residual ? 2 * residual_group(m, max_nprobe) * table_bytes(m) : table_bytes(m);
+}
+static size_t region0(bool residual, int m, int max_nprobe, int R) {
+  return list_region0(payload_bytes(residual, m, max_nprobe), R);
+}
+// the LDS of a top-k call: behind the frame `pending` bytes of the filtered kernels' lists, the staged query and, with
+// residual codes, the probes' cell indices
+static size_t topk_lds_bytes(bool residual, int m, int ds, int max_nprobe, int R, size_t pending) {
+  return list_scan_lds_bytes(region0(residual, m, max_nprobe, R), max_nprobe,
+                             pending + ((size_t)m * ds + (residual ? max_nprobe : 0)) * 4);
+}
+
+// the ScanArgs of a 4-bit call (`k` is 0 where there is none)
+static ScanArgs make_args(const uint8_t* codes, const float* query, const float* codebook, const uint8_t* is_empty,
+                          const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                          float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq, int max_nprobe,
+                          int k, int n_split) {
+  ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                         nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split);
+  a.query = query;
+  a.codebook = codebook;
+  a.ds = ds;
+  return a;
+}
+
+// The checks every 4-bit entry point makes on its numbers, in their order: `k` is null where the call has none, `f`
+// where it has no filter.  After them an empty batch returns TPQ_OK; any other goes on to check_pointers.
+static int check_shape(const char* what, const ScanArgs& a, const ResidualProbes* rp, int metric, const int* k,
+                       const filtered::FilterArgs* f) {
+  if (int rc = check_batch(what, a.nq, a.max_nprobe)) return rc;
+  if (a.m < kMinM || a.m > kMaxM || a.m % 8 != 0 || a.ds < 1) {
+    set_error("%s: m=%d, ds=%d: m must be a multiple of 8 in [8, 256], ds >= 1", what, a.m, a.ds);
+    return TPQ_ERR_UNSUPPORTED;
   }
-  if (W & 4) {
-    v = add_words<4>(v, col, stride, row);
-    col += 4 * stride;
-    row += 4 * 128;
+  if (k && (*k < 1 || *k > 1024)) {
+    set_error("%s: k=%d out of range (0, 1024]", what, *k);
+    return TPQ_ERR_UNSUPPORTED;
   }
-  if (W & 2) {
-    v = add_words<2>(v, col, stride, row);
-    col += 2 * stride;
-    row += 2 * 128;
+  if (int rc = check_lists(what, metric, a.n_split, a.n_slots)) return rc;
+  if ((int64_t)a.m * a.ds > (1 << 20)) {  // (far beyond the LDS; keeps m * ds * 4 inside an int)
+    set_error("%s: d = m * ds = %lld is not supported", what, (long long)a.m * a.ds);
+    return TPQ_ERR_UNSUPPORTED;
   }
-  if (W & 1) v = add_words<1>(v, col, stride, row);
-  return v;
+  if (rp) TPQ_REQUIRE(rp->n_cells >= 1, "%s: n_cells=%d", what, rp->n_cells);
+  if (f) {
+    TPQ_REQUIRE(f->n_filters >= 1, "%s: n_filters=%d", what, f->n_filters);
+    TPQ_REQUIRE(f->stride >= (a.n_slots + 31) / 32, "%s: filter_stride=%lld < ceil(n_slots / 32) = %lld", what,
+                (long long)f->stride, (long long)((a.n_slots + 31) / 32));
+  }
+  return TPQ_OK;
+}
+// ... and, for a batch that is not empty: the inputs every call reads, `others` (the call's own pointers), the grid of
+// `groups` workgroups per query
+static int check_pointers(const char* what, const ScanArgs& a, const ResidualProbes* rp, bool others, int groups) {
+  return check_grid(what,
+                    a.codes && a.query && a.codebook && a.cell_start && a.cell_size && a.n_probe_list && others &&
+                        (!rp || (rp->centroids && rp->cells)),
+                    a.nq, groups);
 }
 
 }  // namespace pq4

@@ -35,22 +35,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_kernel(ScanArgs a, size
   const int part = blockIdx.x - q * a.n_split;
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
-  const int ds = a.ds;
   const int n_probe = clamped_n_probe(a, q);
 
   lds.init(a, q, n_probe, wave, lane);
-  for (int i = threadIdx.x; i < a.m * ds; i += kScanThreads) xq[i] = a.query[(int64_t)i * a.nq + q];
-  __syncthreads();
-  // the table: thread t takes entries t, t + 512, ... -- sixteen consecutive threads write one row, and read sixteen
-  // consecutive floats of the codebook per dimension
-  for (int e = threadIdx.x; e < a.m * 16; e += kScanThreads) {
-    const int j = e >> 4;
-    const float* __restrict__ cb = a.codebook + (int64_t)j * ds * 16 + (e & 15);
-    const float* xj = xq + j * ds;
-    float acc = 0.f;
-    for (int i = 0; i < ds; ++i) acc = metric_step<METRIC>(acc, xj[i], cb[i * 16]);
-    lut[e] = acc;
-  }
+  stage_query(a, q, xq, kScanThreads);
+  build_lut<METRIC>(a, xq, lut);
   __syncthreads();
 
   WaveSelector<R> sel;
@@ -71,26 +60,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_kernel(ScanArgs a, size
     bool live = valid;
     if (valid) {
       if (a.is_empty) live = (a.is_empty[s] == 0);
-      const uint32_t* __restrict__ col = codes32 + s;
-      const float* row = lut;
-      int w = 0;
-      for (; w + kPq4Unroll <= W; w += kPq4Unroll) {
-        v = add_words<kPq4Unroll>(v, col, stride, row);
-        col += (int64_t)kPq4Unroll * stride;
-        row += kPq4Unroll * 128;
-      }
-      // the last W mod 8 words, still in ascending order: four, two, one
-      if (W & 4) {
-        v = add_words<4>(v, col, stride, row);
-        col += 4 * stride;
-        row += 4 * 128;
-      }
-      if (W & 2) {
-        v = add_words<2>(v, col, stride, row);
-        col += 2 * stride;
-        row += 2 * 128;
-      }
-      if (W & 1) v = add_words<1>(v, col, stride, row);
+      v = code_value(codes32 + s, stride, lut, W);
     }
     admit(sel, lds.tau_key, live, v, s);
   }
@@ -137,12 +107,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_residual_kernel(ScanArg
   const int n_probe = clamped_n_probe(a, q);
 
   lds.init(a, q, n_probe, wave, lane);
+  // (the query's staging is written out in the two residual kernels: stage_query ends in a barrier of its own, and ONE
+  // barrier publishes the query and the cells here; with the cells staged ahead of stage_query the filtered kernel ran
+  // 1 % slower, profiles/pq4_fold_ab.json)
   for (int i = threadIdx.x; i < a.m * a.ds; i += kScanThreads) xq[i] = a.query[(int64_t)i * a.nq + q];
-  // (a cell index outside [0, n_cells) is the caller's error: clamped, so that nothing outside `centroids` is read)
-  for (int p = threadIdx.x; p < n_probe; p += kScanThreads) {
-    const int64_t c = rp.cells[(int64_t)q * a.max_nprobe + p];
-    cell[p] = c < 0 ? 0 : (c >= rp.n_cells ? rp.n_cells - 1 : (int)c);
-  }
+  stage_cells(a, rp, q, n_probe, cell);
   __syncthreads();
 
   WaveSelector<R> sel;
@@ -153,6 +122,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_residual_kernel(ScanArg
   const int W = a.m >> 3;
   const uint32_t* __restrict__ codes32 = reinterpret_cast<const uint32_t*>(a.codes);
 
+  // The group walk is written out here and in scan_pq4_filtered_residual_kernel, line for line: behind one function that
+  // takes the tile loop as its body both kernels compiled to the same registers, LDS and barriers but another scalar
+  // schedule, and ran 1.5 to 2 % slower (profiles/pq4_fold_ab.json).  Two rules: nothing stays pending
+  // across a group's barrier, which lets the other waves overwrite that buffer one group later; the last group has
+  // no barrier here -- the finisher's opening barrier ends it.
   // the part's probes: from the first with a tile of the part to the last (the same two numbers in every thread)
   int g0 = next_scanned_probe(lds.tab, 0, n_probe, t);
   int p_end = g0;
@@ -184,7 +158,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_residual_kernel(ScanArg
       }
       admit(sel, lds.tau_key, live, v, s);
     }
-    if (g_next >= p_end) break;  // (the finisher's opening barrier ends the last group)
+    if (g_next >= p_end) break;
     __syncthreads();
     g0 = g_next;
     cur ^= 1;
@@ -195,23 +169,15 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_residual_kernel(ScanArg
 }
 
 template <int METRIC>
-static int dispatch(const ScanArgs& a, int R, hipStream_t st) {
+static int dispatch(const ScanArgs& a, const ResidualProbes* rp, int R, hipStream_t st) {
   return with_list_regs(R, [&](auto r_c) {
     constexpr int RC = decltype(r_c)::value;
-    const size_t region0 = list_region0((size_t)a.m * 64, RC);
-    return launch_list_scan(scan_pq4_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_pq4_kernel", a,
-                            list_scan_lds_bytes(region0, a.max_nprobe, (size_t)a.m * a.ds * 4), st, region0);
-  });
-}
-
-template <int METRIC>
-static int dispatch_residual(const ScanArgs& a, const ResidualProbes& rp, int R, hipStream_t st) {
-  return with_list_regs(R, [&](auto r_c) {
-    constexpr int RC = decltype(r_c)::value;
-    const size_t region0 = list_region0((size_t)2 * residual_group(a.m, a.max_nprobe) * a.m * 64, RC);  // two buffers
-    return launch_list_scan(scan_pq4_residual_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_pq4_residual_kernel", a,
-                            list_scan_lds_bytes(region0, a.max_nprobe, ((size_t)a.m * a.ds + a.max_nprobe) * 4), st,
-                            region0, rp);
+    const size_t r0 = region0(rp != nullptr, a.m, a.max_nprobe, RC);
+    const size_t lds = topk_lds_bytes(rp != nullptr, a.m, a.ds, a.max_nprobe, RC, 0);
+    if (rp)
+      return launch_list_scan(scan_pq4_residual_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_pq4_residual_kernel",
+                              a, lds, st, r0, *rp);
+    return launch_list_scan(scan_pq4_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_pq4_kernel", a, lds, st, r0);
   });
 }
 
@@ -225,46 +191,18 @@ extern "C" size_t tpq_ivfpq4_scan_workspace_bytes(int nq, int k, int n_split) {
   return list_ws_bytes(nq, list_regs(k), n_split);
 }
 
-// both entry points: `rp` is null for plain codes
-static int pq4_scan_topk(const char* what, const pq4::ResidualProbes* rp, const uint8_t* codes, const float* query,
-                         const float* codebook, const uint8_t* is_empty, const int64_t* cell_start,
-                         const int64_t* cell_size, const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
-                         int64_t n_slots, int m, int ds, int nq, int max_nprobe, int k, int metric, int n_split,
-                         void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
-  if (int rc = check_batch(what, nq, max_nprobe)) return rc;
-  if (m < pq4::kMinM || m > pq4::kMaxM || m % 8 != 0 || ds < 1) {
-    set_error("%s: m=%d, ds=%d: m must be a multiple of 8 in [8, 256], ds >= 1", what, m, ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (k < 1 || k > 1024) {
-    set_error("%s: k=%d out of range (0, 1024]", what, k);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (int rc = check_lists(what, metric, n_split, n_slots)) return rc;
-  if ((int64_t)m * ds > (1 << 20)) {  // (far beyond the LDS; keeps m * ds * 4 inside an int)
-    set_error("%s: d = m * ds = %lld is not supported", what, (long long)m * ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (rp) TPQ_REQUIRE(rp->n_cells >= 1, "%s: n_cells=%d", what, rp->n_cells);
-  if (nq == 0) return TPQ_OK;
-  if (int rc = check_grid(what,
-                          codes && query && codebook && cell_start && cell_size && n_probe_list && out_vals &&
-                              out_addr && (!rp || (rp->centroids && rp->cells)),
-                          nq, n_split))
-    return rc;
-  const int R = list_regs(k);
-  ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
-                         nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split);
-  a.query = query;
-  a.codebook = codebook;
-  a.ds = ds;
+// both entry points: `rp` is null for plain codes.  The workspace comes before the LDS here, which the launch checks
+// under the kernel's name.
+static int pq4_scan_topk(const char* what, const pq4::ResidualProbes* rp, ScanArgs a, int metric, void* workspace,
+                         size_t workspace_bytes, tpq_stream_t stream) {
+  if (int rc = pq4::check_shape(what, a, rp, metric, &a.k, nullptr)) return rc;
+  if (a.nq == 0) return TPQ_OK;
+  if (int rc = pq4::check_pointers(what, a, rp, a.out_vals && a.out_addr, a.n_split)) return rc;
+  const int R = list_regs(a.k);
   if (int rc = take_list_ws(a, R, workspace, workspace_bytes, what)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (rp)
-    return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch_residual<TPQ_METRIC_NEG_SQ_L2>(a, *rp, R, st)
-                                          : pq4::dispatch_residual<TPQ_METRIC_INNER>(a, *rp, R, st);
-  return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, R, st)
-                                        : pq4::dispatch<TPQ_METRIC_INNER>(a, R, st);
+  return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, rp, R, st)
+                                        : pq4::dispatch<TPQ_METRIC_INNER>(a, rp, R, st);
 }
 
 extern "C" int tpq_ivfpq4_scan_topk(const uint8_t* codes, const float* query, const float* codebook,
@@ -272,9 +210,10 @@ extern "C" int tpq_ivfpq4_scan_topk(const uint8_t* codes, const float* query, co
                                     const int64_t* n_probe_list, float* out_vals, int64_t* out_addr, int64_t n_slots,
                                     int m, int ds, int nq, int max_nprobe, int k, int metric, int n_split,
                                     void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
-  return pq4_scan_topk("ivfpq4_scan", nullptr, codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
-                       out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, metric, n_split, workspace,
-                       workspace_bytes, stream);
+  return pq4_scan_topk("ivfpq4_scan", nullptr,
+                       pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list, out_vals,
+                                      out_addr, n_slots, m, ds, nq, max_nprobe, k, n_split),
+                       metric, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tpq_ivfpq4_scan_residual_topk(const uint8_t* codes, const float* query, const float* codebook,
@@ -285,7 +224,8 @@ extern "C" int tpq_ivfpq4_scan_residual_topk(const uint8_t* codes, const float* 
                                              int k, int metric, int n_split, void* workspace, size_t workspace_bytes,
                                              tpq_stream_t stream) {
   const pq4::ResidualProbes rp{centroids, cells, n_cells};
-  return pq4_scan_topk("ivfpq4_scan_residual", &rp, codes, query, codebook, is_empty, cell_start, cell_size,
-                       n_probe_list, out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, metric, n_split, workspace,
-                       workspace_bytes, stream);
+  return pq4_scan_topk("ivfpq4_scan_residual", &rp,
+                       pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list, out_vals,
+                                      out_addr, n_slots, m, ds, nq, max_nprobe, k, n_split),
+                       metric, workspace, workspace_bytes, stream);
 }

@@ -4,7 +4,8 @@
 // A filter is a row of bits over the slot addresses, bit s & 31 of word s >> 5 for slot s; every query names its row
 // (scan_list.h: FilterArgs, the format of scan_filtered.hip).  Candidates, values, order and padding are those of
 // tpq_ivfpq4_scan_topk / _residual_topk called with is_empty | ~allowed_row(q) as the tombstone mask of query q, bit for
-// bit: the frame, the table build, the word loop (scan_pq4.h: code_value) and the finisher are those kernels' own.
+// bit: the frame, the table build, the word loop, the grouped tables (scan_pq4.h: build_lut, code_value, build_group_luts) and
+// the finisher are those kernels' own.
 //
 // What differs is the tile loop, that of scan_filtered.hip, which tests a slot's bit BEFORE it touches the slot's m / 2
 // bytes of code:
@@ -63,12 +64,6 @@ struct TablePending {
   }
 };
 
-// the payload sizes, one expression for host and device
-__host__ __device__ constexpr size_t plain_tail_bytes(int m, int ds) { return kPendingBytes + (size_t)m * ds * 4; }
-__host__ __device__ constexpr size_t residual_tail_bytes(int m, int ds, int max_nprobe) {
-  return kTablePendingBytes + ((size_t)m * ds + max_nprobe) * 4;
-}
-
 // the tombstones of the members: read only where the bit is set
 __device__ __forceinline__ void drop_tombstones(const ScanArgs& a, Member (&mb)[kTilesAhead]) {
   if (a.is_empty) {
@@ -103,24 +98,14 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_kernel(ScanArg
   const int part = blockIdx.x - q * a.n_split;
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
-  const int ds = a.ds;
   const uint32_t* __restrict__ row = filter_row(f, q);  // (uniform)
   const int n_probe = row ? clamped_n_probe(a, q) : 0;   // no row: no tile, no table, k pads
 
   lds.init(a, q, n_probe, wave, lane);
-  if (row)
-    for (int i = threadIdx.x; i < a.m * ds; i += kScanThreads) xq[i] = a.query[(int64_t)i * a.nq + q];
-  __syncthreads();
-  // the table, as scan_pq4_kernel builds it
-  if (row)
-    for (int e = threadIdx.x; e < a.m * 16; e += kScanThreads) {
-      const int j = e >> 4;
-      const float* __restrict__ cb = a.codebook + (int64_t)j * ds * 16 + (e & 15);
-      const float* xj = xq + j * ds;
-      float acc = 0.f;
-      for (int i = 0; i < ds; ++i) acc = metric_step<METRIC>(acc, xj[i], cb[i * 16]);
-      lut[e] = acc;
-    }
+  if (row) {  // (uniform: every thread takes stage_query's barrier, or none does)
+    stage_query(a, q, xq, kScanThreads);
+    build_lut<METRIC>(a, xq, lut);
+  }
   __syncthreads();
 
   WaveSelector<R> sel;
@@ -189,13 +174,10 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_residual_kerne
   const int n_probe = row ? clamped_n_probe(a, q) : 0;   // no row: no tile, no table, k pads
 
   lds.init(a, q, n_probe, wave, lane);
+  // (written out as in scan_pq4_residual_kernel, which says why: one barrier for the query and the cells)
   if (row)
     for (int i = threadIdx.x; i < a.m * a.ds; i += kScanThreads) xq[i] = a.query[(int64_t)i * a.nq + q];
-  // (a cell index outside [0, n_cells) is the caller's error: clamped, so that nothing outside `centroids` is read)
-  for (int p = threadIdx.x; p < n_probe; p += kScanThreads) {
-    const int64_t c = rp.cells[(int64_t)q * a.max_nprobe + p];
-    cell[p] = c < 0 ? 0 : (c >= rp.n_cells ? rp.n_cells - 1 : (int)c);
-  }
+  stage_cells(a, rp, q, n_probe, cell);
   __syncthreads();
 
   WaveSelector<R> sel;
@@ -204,7 +186,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_residual_kerne
 
   const TileRange t = part_tiles(lds.tab.tile_begin[n_probe], part, a.n_split);
 
-  // the part's probes and their groups: scan_pq4_residual_kernel's walk (the same numbers in every thread)
+  // scan_pq4_residual_kernel's group walk, line for line (written out in both, and why: see there)
+  // the part's probes: from the first with a tile of the part to the last (the same two numbers in every thread)
   int g0 = next_scanned_probe(lds.tab, 0, n_probe, t);
   int p_end = g0;
   while (p_end < n_probe && lds.tab.tile_begin[p_end] < t.end) ++p_end;
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_residual_kerne
   while (g0 < p_end) {
     const int g1 = min(g0 + G, p_end);  // this group: probes [g0, g1)
     const int g_next = next_scanned_probe(lds.tab, g1, p_end, t);
-    // (the other buffer was last read before the barrier that ended the previous group: every wave had drained)
+    // (the other buffer was last read before the barrier that ended the previous group)
     if (g_next < p_end)
       build_group_luts<METRIC>(a, rp.centroids, cell, g_next, min(G, p_end - g_next), xq,
                                lut + (cur ^ 1) * G * lut_floats);
@@ -245,7 +228,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_residual_kerne
     }
     // the group's tables are read for the last time here: nothing stays pending across the barrier
     if (pend.n > 0) value_pending<R>(a, tables, lut_floats, pend, pend.n, sel, lds.tau_key);
-    if (g_next >= p_end) break;  // (the finisher's opening barrier ends the last group)
+    if (g_next >= p_end) break;
     __syncthreads();
     g0 = g_next;
     cur ^= 1;
@@ -256,33 +239,19 @@ __global__ __launch_bounds__(kScanThreads) void scan_pq4_filtered_residual_kerne
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static size_t plain_region0(int m, int R) { return list_region0((size_t)m * 64, R); }
-static size_t residual_region0(int m, int max_nprobe, int R) {
-  return list_region0((size_t)2 * residual_group(m, max_nprobe) * m * 64, R);  // two buffers
-}
-// the LDS of a call, for the check that comes before any HIP call and for the launch
-static size_t lds_bytes(bool residual, int m, int ds, int max_nprobe, int R) {
-  return residual ? list_scan_lds_bytes(residual_region0(m, max_nprobe, R), max_nprobe,
-                                        residual_tail_bytes(m, ds, max_nprobe))
-                  : list_scan_lds_bytes(plain_region0(m, R), max_nprobe, plain_tail_bytes(m, ds));
-}
+static size_t pending_bytes(bool residual) { return residual ? kTablePendingBytes : kPendingBytes; }
 
 template <int METRIC>
-static int dispatch(const ScanArgs& a, const FilterArgs& f, int R, hipStream_t st) {
+static int dispatch(const ScanArgs& a, const ResidualProbes* rp, const FilterArgs& f, int R, hipStream_t st) {
   return with_list_regs(R, [&](auto r_c) {
     constexpr int RC = decltype(r_c)::value;
+    const size_t r0 = region0(rp != nullptr, a.m, a.max_nprobe, RC);
+    const size_t lds = topk_lds_bytes(rp != nullptr, a.m, a.ds, a.max_nprobe, RC, pending_bytes(rp != nullptr));
+    if (rp)
+      return launch_list_scan(scan_pq4_filtered_residual_kernel<RC, METRIC>, scan_merge_kernel<RC>,
+                              "scan_pq4_filtered_residual_kernel", a, lds, st, r0, *rp, f);
     return launch_list_scan(scan_pq4_filtered_kernel<RC, METRIC>, scan_merge_kernel<RC>, "scan_pq4_filtered_kernel", a,
-                            lds_bytes(false, a.m, a.ds, a.max_nprobe, RC), st, plain_region0(a.m, RC), f);
-  });
-}
-
-template <int METRIC>
-static int dispatch_residual(const ScanArgs& a, const ResidualProbes& rp, const FilterArgs& f, int R, hipStream_t st) {
-  return with_list_regs(R, [&](auto r_c) {
-    constexpr int RC = decltype(r_c)::value;
-    return launch_list_scan(scan_pq4_filtered_residual_kernel<RC, METRIC>, scan_merge_kernel<RC>,
-                            "scan_pq4_filtered_residual_kernel", a, lds_bytes(true, a.m, a.ds, a.max_nprobe, RC), st,
-                            residual_region0(a.m, a.max_nprobe, RC), rp, f);
+                            lds, st, r0, f);
   });
 }
 
@@ -291,54 +260,22 @@ static int dispatch_residual(const ScanArgs& a, const ResidualProbes& rp, const 
 
 using namespace tpq;
 
-// both entry points: `rp` is null for plain codes.  The checks of tpq_ivfpq4_scan_topk in its order, the filter's, then
-// the LDS; all of them before any HIP call.
-static int pq4_scan_filtered_topk(const char* what, const pq4::ResidualProbes* rp, const uint8_t* codes,
-                                  const float* query, const float* codebook, const uint8_t* is_empty,
-                                  const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
-                                  const uint32_t* filter_bits, const int32_t* filter_of_query, int n_filters,
-                                  int64_t filter_stride, float* out_vals, int64_t* out_addr, int64_t n_slots, int m,
-                                  int ds, int nq, int max_nprobe, int k, int metric, int n_split, void* workspace,
-                                  size_t workspace_bytes, tpq_stream_t stream) {
-  if (int rc = check_batch(what, nq, max_nprobe)) return rc;
-  if (m < pq4::kMinM || m > pq4::kMaxM || m % 8 != 0 || ds < 1) {
-    set_error("%s: m=%d, ds=%d: m must be a multiple of 8 in [8, 256], ds >= 1", what, m, ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (k < 1 || k > 1024) {
-    set_error("%s: k=%d out of range (0, 1024]", what, k);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (int rc = check_lists(what, metric, n_split, n_slots)) return rc;
-  if ((int64_t)m * ds > (1 << 20)) {  // (far beyond the LDS; keeps m * ds * 4 inside an int)
-    set_error("%s: d = m * ds = %lld is not supported", what, (long long)m * ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (rp) TPQ_REQUIRE(rp->n_cells >= 1, "%s: n_cells=%d", what, rp->n_cells);
-  TPQ_REQUIRE(n_filters >= 1, "%s: n_filters=%d", what, n_filters);
-  TPQ_REQUIRE(filter_stride >= (n_slots + 31) / 32, "%s: filter_stride=%lld < ceil(n_slots / 32) = %lld", what,
-              (long long)filter_stride, (long long)((n_slots + 31) / 32));
-  if (nq == 0) return TPQ_OK;
-  if (int rc = check_grid(what,
-                          codes && query && codebook && cell_start && cell_size && n_probe_list && out_vals &&
-                              out_addr && filter_bits && (!rp || (rp->centroids && rp->cells)),
-                          nq, n_split))
+// both entry points: `rp` is null for plain codes.  The LDS is checked under the entry point's name, before the
+// workspace; every check comes before any HIP call.
+static int pq4_scan_filtered_topk(const char* what, const pq4::ResidualProbes* rp, ScanArgs a,
+                                  const filtered::FilterArgs& f, int metric, void* workspace, size_t workspace_bytes,
+                                  tpq_stream_t stream) {
+  if (int rc = pq4::check_shape(what, a, rp, metric, &a.k, &f)) return rc;
+  if (a.nq == 0) return TPQ_OK;
+  if (int rc = pq4::check_pointers(what, a, rp, a.out_vals && a.out_addr && f.bits, a.n_split)) return rc;
+  const int R = list_regs(a.k);
+  if (int rc = check_lds(what, pq4::topk_lds_bytes(rp != nullptr, a.m, a.ds, a.max_nprobe, R,
+                                                   pq4::pending_bytes(rp != nullptr))))
     return rc;
-  const int R = list_regs(k);
-  if (int rc = check_lds(what, pq4::lds_bytes(rp != nullptr, m, ds, max_nprobe, R))) return rc;
-  ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
-                         nullptr, nullptr, n_slots, nq, max_nprobe, m, k, n_split);
-  a.query = query;
-  a.codebook = codebook;
-  a.ds = ds;
   if (int rc = take_list_ws(a, R, workspace, workspace_bytes, what)) return rc;
-  const filtered::FilterArgs f{filter_bits, filter_of_query, filter_stride, n_filters};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (rp)
-    return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch_residual<TPQ_METRIC_NEG_SQ_L2>(a, *rp, f, R, st)
-                                          : pq4::dispatch_residual<TPQ_METRIC_INNER>(a, *rp, f, R, st);
-  return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, f, R, st)
-                                        : pq4::dispatch<TPQ_METRIC_INNER>(a, f, R, st);
+  return metric == TPQ_METRIC_NEG_SQ_L2 ? pq4::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, rp, f, R, st)
+                                        : pq4::dispatch<TPQ_METRIC_INNER>(a, rp, f, R, st);
 }
 
 extern "C" int tpq_ivfpq4_scan_filtered_topk(const uint8_t* codes, const float* query, const float* codebook,
@@ -349,9 +286,10 @@ extern "C" int tpq_ivfpq4_scan_filtered_topk(const uint8_t* codes, const float* 
                                              int64_t n_slots, int m, int ds, int nq, int max_nprobe, int k, int metric,
                                              int n_split, void* workspace, size_t workspace_bytes,
                                              tpq_stream_t stream) {
-  return pq4_scan_filtered_topk("ivfpq4_scan_filtered", nullptr, codes, query, codebook, is_empty, cell_start,
-                                cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                                out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, metric, n_split, workspace,
+  return pq4_scan_filtered_topk("ivfpq4_scan_filtered", nullptr,
+                                pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                               out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, n_split),
+                                {filter_bits, filter_of_query, filter_stride, n_filters}, metric, workspace,
                                 workspace_bytes, stream);
 }
 
@@ -362,8 +300,9 @@ extern "C" int tpq_ivfpq4_scan_filtered_residual_topk(
     int64_t filter_stride, float* out_vals, int64_t* out_addr, int64_t n_slots, int m, int ds, int nq, int max_nprobe,
     int k, int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
   const pq4::ResidualProbes rp{centroids, cells, n_cells};
-  return pq4_scan_filtered_topk("ivfpq4_scan_filtered_residual", &rp, codes, query, codebook, is_empty, cell_start,
-                                cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                                out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, metric, n_split, workspace,
+  return pq4_scan_filtered_topk("ivfpq4_scan_filtered_residual", &rp,
+                                pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                               out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, k, n_split),
+                                {filter_bits, filter_of_query, filter_stride, n_filters}, metric, workspace,
                                 workspace_bytes, stream);
 }

@@ -3,8 +3,8 @@
 //
 // Every candidate of the 4-bit top-k scan (scan_pq4.hip) whose value is >= the query's threshold, in scan order.  The
 // parts are those units' own: the codes are read as CellContainer stores them (u32 [m / 8][n_slots], a lane owns one
-// slot of a 64-slot tile), the table is built in the workgroup entry for entry as scan_pq4_kernel / build_group_luts
-// build it, the value is pq4::code_value's ascending-j fp32 sum from 0.f -- so a hit carries the bits `search` returns
+// slot of a 64-slot tile), the table is built in the workgroup by those kernels' own pq4::build_lut /
+// build_group_luts, the value is pq4::code_value's ascending-j fp32 sum from 0.f -- so a hit carries the bits `search` returns
 // for that slot under that probe.  Two passes over the same tiles on the protocol of scan_range.hip (Segment<FILL>,
 // scan_list.h): the count pass counts each wave's hits, the caller turns the counts into offsets, the fill pass
 // computes the values again and appends each wave's hits at its offset.  No global atomic, no sort, no selector.
@@ -36,8 +36,8 @@ using filtered::filter_row;
 using filtered::Member;
 using filtered::member;
 using pq4::ResidualProbes;
+using pq4::table_bytes;
 
-__host__ __device__ constexpr size_t table_bytes(int m) { return (size_t)m * 64; }
 __host__ __device__ constexpr size_t query_bytes(int m, int ds) { return align16((size_t)m * ds * 4); }
 static size_t lds_bytes(int m, int ds, int probe_entries) {
   return table_bytes(m) + query_bytes(m, ds) + (probe_entries ? align16(probe_table_bytes(probe_entries)) : 0);
@@ -48,21 +48,6 @@ template <bool FILL>
 __device__ __forceinline__ void no_counts(const RangeArgs& r, int64_t seg) {
   if constexpr (!FILL) {
     if (threadIdx.x < kScanWaves) r.wave_counts[seg + threadIdx.x] = 0;
-  }
-}
-
-// The query's table, as scan_pq4_kernel builds it: thread t takes entries t, t + 512, ...; the same metric_step chain,
-// i ascending from 0.f.  (That kernel keeps its own loop: its code is not touched by this unit.)
-template <int METRIC>
-__device__ __forceinline__ void build_lut(const ScanArgs& a, const float* xq, float* lut) {
-  const int ds = a.ds;
-  for (int e = threadIdx.x; e < a.m * 16; e += kScanThreads) {
-    const int j = e >> 4;
-    const float* __restrict__ cb = a.codebook + (int64_t)j * ds * 16 + (e & 15);
-    const float* xj = xq + j * ds;
-    float acc = 0.f;
-    for (int i = 0; i < ds; ++i) acc = metric_step<METRIC>(acc, xj[i], cb[i * 16]);
-    lut[e] = acc;
   }
 }
 
@@ -116,7 +101,7 @@ __device__ __forceinline__ void plain_body(const ScanArgs& a, const RangeArgs& r
   const int n_probe = clamped_n_probe(a, q);
   if (wave == 0) build_probe_table(a, q, n_probe, tab);
   stage_query(a, q, xq, kScanThreads);
-  build_lut<METRIC>(a, xq, lut);
+  pq4::build_lut<METRIC>(a, xq, lut);
   __syncthreads();
   if (out.empty()) return;  // no code is read
   // the part's tiles are scan_pq4_kernel's; the wave's chunk of them is contiguous
@@ -177,9 +162,7 @@ __device__ __forceinline__ void residual_body(const ScanArgs& a, const ResidualP
   // the probe's table, entry for entry as scan_pq4_residual_kernel builds it: a group of one
   float* lut = reinterpret_cast<float*>(smem);
   float* xq = reinterpret_cast<float*>(smem + table_bytes(a.m));
-  // (a cell index outside [0, n_cells) is the caller's error: clamped, so that nothing outside `centroids` is read)
-  const int64_t c64 = rp.cells[at];
-  const int cell = c64 < 0 ? 0 : (c64 >= rp.n_cells ? rp.n_cells - 1 : (int)c64);
+  const int cell = pq4::clamp_cell(rp.cells[at], rp.n_cells);
   stage_query(a, q, xq, kScanThreads);
   pq4::build_group_luts<METRIC>(a, rp.centroids, &cell, 0, 1, xq, lut);
   __syncthreads();
@@ -222,54 +205,26 @@ static int launch_metric(int metric, const ScanArgs& a, const ResidualProbes* rp
                                         : launch<FILL, FILTERED, TPQ_METRIC_INNER>(a, rp, r, f, lds, st);
 }
 
-// The four entry points: `rp` is null for plain codes, `fill` chooses the pass.  The checks of tpq_ivfpq4_scan_topk in
-// its order, the filter's when there is one, the pointers, the grid, the LDS; all of them before any HIP call.
-static int range_pass(const char* what, const ResidualProbes* rp, bool fill, const uint8_t* codes, const float* query,
-                      const float* codebook, const uint8_t* is_empty, const int64_t* cell_start,
-                      const int64_t* cell_size, const int64_t* n_probe_list, const uint32_t* filter_bits,
-                      const int32_t* filter_of_query, int n_filters, int64_t filter_stride, const float* threshold,
-                      int32_t* wave_counts, const int64_t* wave_offsets, float* out_vals, int64_t* out_addr,
-                      int64_t n_slots, int m, int ds, int nq, int max_nprobe, int metric, int n_split,
+// The four entry points: `rp` is null for plain codes, `fill` chooses the pass; `a` holds the outputs of the fill
+// pass.  The checks of tpq_ivfpq4_scan_topk in its order (there is no k), the filter's when there is one, the pointers,
+// the grid, the LDS; all of them before any HIP call.
+static int range_pass(const char* what, const ResidualProbes* rp, bool fill, const ScanArgs& a, const FilterArgs& f,
+                      const float* threshold, int32_t* wave_counts, const int64_t* wave_offsets, int metric,
                       tpq_stream_t stream) {
-  if (int rc = check_batch(what, nq, max_nprobe)) return rc;
-  if (m < pq4::kMinM || m > pq4::kMaxM || m % 8 != 0 || ds < 1) {
-    set_error("%s: m=%d, ds=%d: m must be a multiple of 8 in [8, 256], ds >= 1", what, m, ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (int rc = check_lists(what, metric, n_split, n_slots)) return rc;
-  if ((int64_t)m * ds > (1 << 20)) {  // (far beyond the LDS; keeps m * ds * 4 inside an int)
-    set_error("%s: d = m * ds = %lld is not supported", what, (long long)m * ds);
-    return TPQ_ERR_UNSUPPORTED;
-  }
-  if (rp) TPQ_REQUIRE(rp->n_cells >= 1, "%s: n_cells=%d", what, rp->n_cells);
-  if (filter_bits) {
-    TPQ_REQUIRE(n_filters >= 1, "%s: n_filters=%d", what, n_filters);
-    TPQ_REQUIRE(filter_stride >= (n_slots + 31) / 32, "%s: filter_stride=%lld < ceil(n_slots / 32) = %lld", what,
-                (long long)filter_stride, (long long)((n_slots + 31) / 32));
-  }
-  if (nq == 0) return TPQ_OK;
-  const int groups = rp ? max_nprobe : n_split;  // workgroups per query
-  if (int rc = check_grid(what,
-                          codes && query && codebook && cell_start && cell_size && n_probe_list && threshold &&
-                              (fill ? (wave_offsets && out_vals && out_addr) : wave_counts != nullptr) &&
-                              (!rp || (rp->centroids && rp->cells)),
-                          nq, groups))
-    return rc;
-  const size_t lds = lds_bytes(m, ds, rp ? 0 : max_nprobe);
+  if (int rc = pq4::check_shape(what, a, rp, metric, nullptr, f.bits ? &f : nullptr)) return rc;
+  if (a.nq == 0) return TPQ_OK;
+  const bool outputs = fill ? (wave_offsets && a.out_vals && a.out_addr) : wave_counts != nullptr;
+  // (workgroups per query: the probes of residual codes, the parts of plain ones)
+  if (int rc = pq4::check_pointers(what, a, rp, threshold && outputs, rp ? a.max_nprobe : a.n_split)) return rc;
+  const size_t lds = lds_bytes(a.m, a.ds, rp ? 0 : a.max_nprobe);
   if (int rc = check_lds(what, lds)) return rc;
-  ScanArgs a = scan_args(codes, nullptr, nullptr, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
-                         nullptr, nullptr, n_slots, nq, max_nprobe, m, 0, n_split);
-  a.query = query;
-  a.codebook = codebook;
-  a.ds = ds;
   const RangeArgs r{threshold, wave_counts, fill ? wave_offsets : nullptr};
-  const FilterArgs f{filter_bits, filter_of_query, filter_stride, n_filters};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (fill)
-    return filter_bits ? launch_metric<true, true>(metric, a, rp, r, f, lds, st)
-                       : launch_metric<true, false>(metric, a, rp, r, f, lds, st);
-  return filter_bits ? launch_metric<false, true>(metric, a, rp, r, f, lds, st)
-                     : launch_metric<false, false>(metric, a, rp, r, f, lds, st);
+    return f.bits ? launch_metric<true, true>(metric, a, rp, r, f, lds, st)
+                  : launch_metric<true, false>(metric, a, rp, r, f, lds, st);
+  return f.bits ? launch_metric<false, true>(metric, a, rp, r, f, lds, st)
+                : launch_metric<false, false>(metric, a, rp, r, f, lds, st);
 }
 
 }  // namespace pq4range
@@ -293,10 +248,11 @@ extern "C" int tpq_ivfpq4_range_count(const uint8_t* codes, const float* query, 
                                       const int32_t* filter_of_query, int n_filters, int64_t filter_stride,
                                       const float* threshold, int32_t* wave_counts, int64_t n_slots, int m, int ds,
                                       int nq, int max_nprobe, int metric, int n_split, tpq_stream_t stream) {
-  return pq4range::range_pass("ivfpq4_range_count", nullptr, false, codes, query, codebook, is_empty, cell_start,
-                              cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                              threshold, wave_counts, nullptr, nullptr, nullptr, n_slots, m, ds, nq, max_nprobe,
-                              metric, n_split, stream);
+  return pq4range::range_pass("ivfpq4_range_count", nullptr, false,
+                              pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                             nullptr, nullptr, n_slots, m, ds, nq, max_nprobe, 0, n_split),
+                              {filter_bits, filter_of_query, filter_stride, n_filters}, threshold, wave_counts, nullptr,
+                              metric, stream);
 }
 
 extern "C" int tpq_ivfpq4_range_fill(const uint8_t* codes, const float* query, const float* codebook,
@@ -306,10 +262,11 @@ extern "C" int tpq_ivfpq4_range_fill(const uint8_t* codes, const float* query, c
                                      const float* threshold, const int64_t* wave_offsets, float* out_vals,
                                      int64_t* out_addr, int64_t n_slots, int m, int ds, int nq, int max_nprobe,
                                      int metric, int n_split, tpq_stream_t stream) {
-  return pq4range::range_pass("ivfpq4_range_fill", nullptr, true, codes, query, codebook, is_empty, cell_start,
-                              cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                              threshold, nullptr, wave_offsets, out_vals, out_addr, n_slots, m, ds, nq, max_nprobe,
-                              metric, n_split, stream);
+  return pq4range::range_pass("ivfpq4_range_fill", nullptr, true,
+                              pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                             out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, 0, n_split),
+                              {filter_bits, filter_of_query, filter_stride, n_filters}, threshold, nullptr, wave_offsets,
+                              metric, stream);
 }
 
 extern "C" int tpq_ivfpq4_range_residual_count(const uint8_t* codes, const float* query, const float* codebook,
@@ -321,10 +278,11 @@ extern "C" int tpq_ivfpq4_range_residual_count(const uint8_t* codes, const float
                                                int32_t* wave_counts, int64_t n_slots, int m, int ds, int nq,
                                                int max_nprobe, int metric, tpq_stream_t stream) {
   const pq4::ResidualProbes rp{centroids, cells, n_cells};
-  return pq4range::range_pass("ivfpq4_range_residual_count", &rp, false, codes, query, codebook, is_empty, cell_start,
-                              cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                              threshold, wave_counts, nullptr, nullptr, nullptr, n_slots, m, ds, nq, max_nprobe,
-                              metric, 1, stream);
+  return pq4range::range_pass("ivfpq4_range_residual_count", &rp, false,
+                              pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                             nullptr, nullptr, n_slots, m, ds, nq, max_nprobe, 0, 1),
+                              {filter_bits, filter_of_query, filter_stride, n_filters}, threshold, wave_counts, nullptr,
+                              metric, stream);
 }
 
 extern "C" int tpq_ivfpq4_range_residual_fill(const uint8_t* codes, const float* query, const float* codebook,
@@ -337,8 +295,9 @@ extern "C" int tpq_ivfpq4_range_residual_fill(const uint8_t* codes, const float*
                                               int64_t n_slots, int m, int ds, int nq, int max_nprobe, int metric,
                                               tpq_stream_t stream) {
   const pq4::ResidualProbes rp{centroids, cells, n_cells};
-  return pq4range::range_pass("ivfpq4_range_residual_fill", &rp, true, codes, query, codebook, is_empty, cell_start,
-                              cell_size, n_probe_list, filter_bits, filter_of_query, n_filters, filter_stride,
-                              threshold, nullptr, wave_offsets, out_vals, out_addr, n_slots, m, ds, nq, max_nprobe,
-                              metric, 1, stream);
+  return pq4range::range_pass("ivfpq4_range_residual_fill", &rp, true,
+                              pq4::make_args(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
+                                             out_vals, out_addr, n_slots, m, ds, nq, max_nprobe, 0, 1),
+                              {filter_bits, filter_of_query, filter_stride, n_filters}, threshold, nullptr, wave_offsets,
+                              metric, stream);
 }

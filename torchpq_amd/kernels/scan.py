@@ -41,7 +41,79 @@ class CellKeptState:
         self.builds += 1
 
 
-class IVFPQTopkHip:
+class _ListScan:
+    """What the list-scan wrappers share: the device's CU count, read once, and the workgroups per query of the last
+    call.  `_workgroups` says how many workgroups of how many waves one CU holds."""
+
+    def __init__(self):
+        self.n_cus = None
+        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last (plain) call
+
+    def _n_split(self, n_query, device, slots_hint=None):
+        """Workgroups per query so that small batches still fill the chip, see workgroups_per_query."""
+        if self.n_cus is None:
+            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
+        return workgroups_per_query(n_query, self.n_cus, *self._workgroups(), slots_hint)
+
+    def _workgroups(self):
+        """the IVFFlat and 4-bit kernels: two 8-wave workgroups per CU"""
+        return 2, 8
+
+
+class _IVFPQListScan(_ListScan):
+    """the kernels over 8-bit codes (csrc/scan_packed_kernel.h packed_waves), m sub-quantizers"""
+
+    def __init__(self, m=8):
+        super().__init__()
+        assert m % 4 == 0
+        self.m = m
+
+    def _workgroups(self):
+        # four 4-wave workgroups per CU for short codes (m <= 32), two 8-wave ones while the LUT is
+        # <= 64 KiB, one 16-wave workgroup above
+        return (4, 4) if self.m <= 32 else (2, 8) if self.m <= 64 else (1, 16)
+
+    def _check_lists(self, data, is_empty, cell_start, cell_size, n_probe_list):
+        n_data = data.shape[1]
+        n_query, n_probe = cell_start.shape
+        assert data.shape == (self.m // 4, n_data, 4) and data.dtype == torch.uint8
+        _check_lists(n_data, is_empty, cell_start, cell_size, n_probe_list)
+        return n_data, n_query, n_probe
+
+    def _check_fused(self, query, codebook, n_query):
+        """(query, codebook, ds) of a table built in the workgroup"""
+        m, ds, kk = codebook.shape
+        assert m == self.m and kk == 256 and query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        return query.contiguous(), codebook.contiguous(), ds
+
+    def _plain_table(self, precomputed, query, codebook, n_query):
+        """the table of a plain call: precomputed [m, n_query, 256], or query and codebook from which the workgroup
+        builds it -> (precomputed, query, codebook, ds), the ones not used None"""
+        if precomputed is not None:
+            assert precomputed.shape == (self.m, n_query, 256) and precomputed.dtype == torch.float32
+            return precomputed.contiguous(), None, None, 0
+        assert query is not None and codebook is not None
+        return (None, *self._check_fused(query, codebook, n_query))
+
+    def _residual_tables(self, full, part1, part2, cells, query, codebook, n_query, n_probe):
+        """the tables of a residual call: full, or part2 + cells with part1 or (query, codebook)
+        -> (part1, query, codebook, ds, part2, full, cells), the ones not used None"""
+        if full is not None:
+            assert full.shape == (n_query, n_probe, self.m, 256) and full.dtype == torch.float32
+            return None, None, None, 0, None, full.contiguous(), None
+        assert part2 is not None and cells is not None
+        assert part2.shape[1:] == (self.m, 256) and part2.dtype == torch.float32
+        assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+        part2, cells = part2.contiguous(), cells.contiguous()
+        if part1 is not None:
+            assert part1.shape == (n_query, self.m, 256) and part1.dtype == torch.float32
+            return part1.contiguous(), None, None, 0, part2, None, cells
+        assert query is not None and codebook is not None
+        return (None, *self._check_fused(query, codebook, n_query), part2, None, cells)
+
+
+class IVFPQTopkHip(_IVFPQListScan):
     """IVF list scan + top-k.  Mirrors IVFPQTopkCuda (kernels/IVFPQTopkCuda.py:9-142);
     ``tpb``/``stack_capacity``/``sm_size`` are accepted for signature compatibility and
     ignored (the workgroup shape is fixed by the gfx950 kernel)."""
@@ -49,16 +121,13 @@ class IVFPQTopkHip:
     def __init__(self, m=8, k=256, tpb=256, n_cs=4, stack_capacity=2, sm_size=None):
         assert k == 256  # 8-bit PQ only (IVFPQTopkCuda.py:21)
         assert n_cs == 4
-        assert m % n_cs == 0
-        self.m = m
+        super().__init__(m)
         self.k = k
         self.tpb = tpb
         self.n_cs = n_cs
-        self.n_cus = None
         # measurement hook (bench.py): when a list, every call appends a (start, stop) pair of
         # timing events recorded on the launch stream around the scan kernel(s)
         self.record_events = None
-        self.last_n_split = None
         # tickets of the one-launch finish of split queries (tpq_ivfpq_*_tickets): caller-owned int32 [n_query],
         # zero between calls.  One buffer per (device, stream) -- calls that share a buffer must be ordered;
         # `ticket_buffer` overrides it (GraphedSearch hands in the buffer its graph owns).
@@ -264,15 +333,6 @@ class IVFPQTopkHip:
         survived = stored & (cap - 1 - e >= cand.clamp(max=cap)[:, None])
         return dict(count=count, maxima=maxima, survived=survived, threshold=thr, band=band, qnorm=qnorm,
                     candidates=cand)
-
-    def _n_split(self, n_query, device, slots_hint=None):
-        """Workgroups per query so that small batches still fill the chip (256 CUs x 2), see workgroups_per_query."""
-        if self.n_cus is None:
-            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
-        # four 4-wave workgroups per CU for short codes (m <= 32), two 8-wave ones while the LUT is
-        # <= 64 KiB, one 16-wave workgroup above (csrc/scan_packed_kernel.h packed_waves)
-        per_cu, waves = (4, 4) if self.m <= 32 else (2, 8) if self.m <= 64 else (1, 16)
-        return workgroups_per_query(n_query, self.n_cus, per_cu, waves, slots_hint)
 
     def _scan(self, name, inputs, data, cell_start, address2id, k, n_split, slots_hint, packed, ticketed,
               cells=None, n_cells=0, cell_threshold=True, kept=None, cell_single_product=True, **route):
@@ -724,19 +784,71 @@ def _split_and_workspace(scan, workspace_bytes, n_query, k, n_split, slots_hint,
     return n_split, ws, ws_bytes
 
 
-class IVFFlatTopkHip:
+class _IVFPQ4Scan(_ListScan):
+    """the wrappers of the 4-bit kernels (csrc/scan_pq4*.hip), m sub-quantizers"""
+
+    def __init__(self, m=8):
+        super().__init__()
+        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
+        self.m = m
+
+    def _inputs(self, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, is_empty, distance,
+                filter_bits=None, filter_of_query=None):
+        """What every 4-bit call checks and makes contiguous; `residual` is () or (centroids, cells), the filter
+        optional.  Returns (the library's arguments up to n_probe_list, the filter's four arguments,
+        (n_slots, m, ds, n_query, n_probe), the tensors to check with require_gpu -- the caller keeps them until it
+        has launched: they own what the pointers name)."""
+        n_slots = codes.shape[1]
+        m, ds, kk = codebook.shape
+        n_query, n_probe = cell_start.shape
+        assert m == self.m and kk == 16 and ds >= 1
+        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
+        assert query.shape == (m * ds, n_query)
+        assert query.dtype == codebook.dtype == torch.float32
+        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+        flt = (None, None, 0, 0)
+        if filter_bits is not None:
+            filter_of_query = IVFPQFilteredTopkHip._check_filter(filter_bits, filter_of_query, n_slots, n_query)
+            assert filter_bits.is_contiguous()
+            flt = (ptr(filter_bits), ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1])
+        else:
+            assert filter_of_query is None, "filter_of_query without filter_bits"
+        tables = ()
+        if residual:
+            centroids, cells = residual
+            assert centroids.dtype == torch.float32
+            assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
+            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
+            residual = (centroids.contiguous(), cells.contiguous())
+            tables = (ptr(residual[0]), ptr(residual[1]), centroids.shape[0])
+        assert distance in ("euclidean", "cosine", "inner")
+        query, codebook = query.contiguous(), codebook.contiguous()
+        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
+        tensors = (codes, query, codebook, *residual, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
+                   filter_of_query)
+        inputs = (ptr(codes), ptr(query), ptr(codebook), *tables, ptr(is_empty), ptr(cell_start), ptr(cell_size),
+                  ptr(n_probe_list))
+        return inputs, flt, (n_slots, m, ds, n_query, n_probe), tensors
+
+    def _topk(self, symbol, k, n_split, slots_hint, distance, inputs, flt, shape, tensors):
+        """the top-k calls once `_inputs` has checked them; `flt` is () for a scan without a filter"""
+        assert 0 < k <= 1024
+        require_gpu(*tensors)
+        device = tensors[0].device
+        n_query = shape[3]
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
+        call(symbol, device, *inputs, *flt, ptr(values), ptr(address), *shape, k, metric_code(distance), n_split,
+             ptr(ws), ws_bytes)
+        return values, address
+
+
+class IVFFlatTopkHip(_ListScan):
     """The list scan of IVFFlatIndex (tpq_ivfflat_scan_topk, csrc/scan_flat.hip): the probed cells hold the vectors
     themselves; value and order are defined in include/torchpq_amd.h."""
-
-    def __init__(self):
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
-
-    def _n_split(self, n_query, device, slots_hint=None):
-        """Workgroups per query: two 8-wave workgroups per CU, see workgroups_per_query."""
-        if self.n_cus is None:
-            self.n_cus = torch.cuda.get_device_properties(device).multi_processor_count
-        return workgroups_per_query(n_query, self.n_cus, 2, 8, slots_hint)
 
     def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None,
                  distance="euclidean", n_split=None, slots_hint=None):
@@ -844,17 +956,9 @@ class IVFFlatCellTopkHip:
         return values, address
 
 
-class IVFPQ4TopkHip:
+class IVFPQ4TopkHip(_IVFPQ4Scan):
     """The list scan of IVFPQ4Index (tpq_ivfpq4_scan_topk, csrc/scan_pq4.hip): 4-bit product-quantized lists, the
     table built inside the scan workgroup; codes, table entry, value and order are defined in include/torchpq_amd.h."""
-
-    def __init__(self, m=8):
-        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
-
-    _n_split = IVFFlatTopkHip._n_split
 
     def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, k, is_empty=None,
                  distance="euclidean", n_split=None, slots_hint=None):
@@ -865,45 +969,15 @@ class IVFPQ4TopkHip:
           is_empty: [n_slots] uint8, or None when no slot inside a cell is a tombstone
         returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
         """
-        n_slots = codes.shape[1]
-        m, ds, kk = codebook.shape
-        n_query, n_probe = cell_start.shape
-        assert m == self.m and kk == 16 and ds >= 1
-        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
-        assert query.shape == (m * ds, n_query)
-        assert query.dtype == codebook.dtype == torch.float32
-        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
-        assert distance in ("euclidean", "cosine", "inner")
-        assert 0 < k <= 1024
-        query = query.contiguous()
-        codebook = codebook.contiguous()
-        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
-        require_gpu(codes, query, codebook, is_empty, cell_start, cell_size, n_probe_list)
-        device = codes.device
-        values, address = alloc_pair(n_query, k, device)
-        if n_query == 0:
-            return values, address
-        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
-                                                     n_split, slots_hint, device)
-        call("tpq_ivfpq4_scan_topk", device,
-             ptr(codes), ptr(query), ptr(codebook), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
-             ptr(values), ptr(address), n_slots, m, ds, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
-             ws_bytes)
-        return values, address
+        inputs, _, shape, tensors = self._inputs(codes, query, codebook, (), cell_start, cell_size, n_probe_list,
+                                                 is_empty, distance)
+        return self._topk("tpq_ivfpq4_scan_topk", k, n_split, slots_hint, distance, inputs, (), shape, tensors)
 
 
-class IVFPQ4ResidualTopkHip:
+class IVFPQ4ResidualTopkHip(_IVFPQ4Scan):
     """The list scan of IVFPQ4Index(pq_use_residual=True) (tpq_ivfpq4_scan_residual_topk, csrc/scan_pq4.hip): 4-bit
     codes of x - centroid(cell); the table of every scanned probe is built inside the scan workgroup from the query,
     the codebook and the probed cell's centroid; defined in include/torchpq_amd.h."""
-
-    def __init__(self, m=8):
-        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
-
-    _n_split = IVFFlatTopkHip._n_split
 
     def __call__(self, codes, query, codebook, centroids, cells, cell_start, cell_size, n_probe_list, k,
                  is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
@@ -913,46 +987,16 @@ class IVFPQ4ResidualTopkHip:
           cells: [n_query, max_n_probe] int64, the probed cells (values in [0, n_cells))
         returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
         """
-        n_slots = codes.shape[1]
-        m, ds, kk = codebook.shape
-        n_query, n_probe = cell_start.shape
-        assert m == self.m and kk == 16 and ds >= 1
-        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
-        assert query.shape == (m * ds, n_query)
-        assert query.dtype == codebook.dtype == centroids.dtype == torch.float32
-        assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
-        assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
-        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
-        assert distance in ("euclidean", "cosine", "inner")
-        assert 0 < k <= 1024
-        query = query.contiguous()
-        codebook = codebook.contiguous()
-        centroids = centroids.contiguous()
-        cells, cell_start, cell_size = cells.contiguous(), cell_start.contiguous(), cell_size.contiguous()
-        require_gpu(codes, query, codebook, centroids, cells, is_empty, cell_start, cell_size, n_probe_list)
-        device = codes.device
-        values, address = alloc_pair(n_query, k, device)
-        if n_query == 0:
-            return values, address
-        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
-                                                     n_split, slots_hint, device)
-        call("tpq_ivfpq4_scan_residual_topk", device,
-             ptr(codes), ptr(query), ptr(codebook), ptr(centroids), ptr(cells), centroids.shape[0], ptr(is_empty),
-             ptr(cell_start), ptr(cell_size), ptr(n_probe_list), ptr(values), ptr(address), n_slots, m, ds, n_query,
-             n_probe, k, metric_code(distance), n_split, ptr(ws), ws_bytes)
-        return values, address
+        inputs, _, shape, tensors = self._inputs(codes, query, codebook, (centroids, cells), cell_start, cell_size,
+                                                 n_probe_list, is_empty, distance)
+        return self._topk("tpq_ivfpq4_scan_residual_topk", k, n_split, slots_hint, distance, inputs, (), shape,
+                          tensors)
 
 
-class IVFFlatRangeHip:
+class IVFFlatRangeHip(_ListScan):
     """Range search over the lists of IVFFlatIndex (tpq_ivfflat_range_count / tpq_ivfflat_range_fill,
     csrc/scan_flat.hip): every candidate of IVFFlatTopkHip whose value is >= the query's threshold, in scan order;
     the semantics are defined in include/torchpq_amd.h."""
-
-    def __init__(self):
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
-
-    _n_split = IVFFlatTopkHip._n_split
 
     def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, threshold, is_empty=None,
                  distance="euclidean", n_split=None, slots_hint=None):
@@ -990,33 +1034,11 @@ class IVFFlatRangeHip:
         return _range_two_pass(n_query, device, threshold, passes)
 
 
-class IVFPQRangeHip:
+class IVFPQRangeHip(_IVFPQListScan):
     """Range search over the lists of IVFPQIndex (tpq_ivfpq_range_count / _fill and their residual forms,
     csrc/scan_range.hip): every candidate of IVFPQTopkHip whose value is >= the query's threshold, in scan order, the
     value being that of the exact reference-layout scan; the semantics are defined in include/torchpq_amd.h.  The scan
     reads CellContainer._storage itself: there is no scan-layout route."""
-
-    def __init__(self, m=8):
-        assert m % 4 == 0
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
-
-    _n_split = IVFPQTopkHip._n_split
-
-    def _check_lists(self, data, is_empty, cell_start, cell_size, n_probe_list):
-        n_data = data.shape[1]
-        n_query, n_probe = cell_start.shape
-        assert data.shape == (self.m // 4, n_data, 4) and data.dtype == torch.uint8
-        _check_lists(n_data, is_empty, cell_start, cell_size, n_probe_list)
-        return n_data, n_query, n_probe
-
-    def _check_fused(self, query, codebook, n_query):
-        """(query, codebook, ds) of a table built in the workgroup"""
-        m, ds, kk = codebook.shape
-        assert m == self.m and kk == 256 and query.shape == (m * ds, n_query)
-        assert query.dtype == codebook.dtype == torch.float32
-        return query.contiguous(), codebook.contiguous(), ds
 
     def __call__(self, data, cell_start, cell_size, n_probe_list, threshold, precomputed=None, query=None,
                  codebook=None, distance="euclidean", is_empty=None, n_split=None, slots_hint=None):
@@ -1032,13 +1054,7 @@ class IVFPQRangeHip:
         Synchronises once: the number of hits sizes the outputs.
         """
         n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
-        ds = 0
-        if precomputed is not None:
-            assert precomputed.shape == (self.m, n_query, 256) and precomputed.dtype == torch.float32
-            precomputed, query, codebook = precomputed.contiguous(), None, None
-        else:
-            assert query is not None and codebook is not None
-            query, codebook, ds = self._check_fused(query, codebook, n_query)
+        precomputed, query, codebook, ds = self._plain_table(precomputed, query, codebook, n_query)
         assert distance in ("euclidean", "cosine", "inner")
         threshold = _checked_threshold(threshold, n_query)
         require_gpu(data, precomputed, query, codebook, is_empty, cell_start, cell_size, n_probe_list,
@@ -1071,21 +1087,8 @@ class IVFPQRangeHip:
         n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
         assert base_sims.shape == (n_query, n_probe) and base_sims.dtype == torch.float32
         base_sims = base_sims.contiguous()
-        ds = 0
-        if full is not None:
-            assert full.shape == (n_query, n_probe, self.m, 256) and full.dtype == torch.float32
-            full, part1, part2, cells, query, codebook = full.contiguous(), None, None, None, None, None
-        else:
-            assert part2 is not None and cells is not None
-            assert part2.shape[1:] == (self.m, 256) and part2.dtype == torch.float32
-            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
-            part2, cells = part2.contiguous(), cells.contiguous()
-            if part1 is not None:
-                assert part1.shape == (n_query, self.m, 256) and part1.dtype == torch.float32
-                part1, query, codebook = part1.contiguous(), None, None
-            else:
-                assert query is not None and codebook is not None
-                query, codebook, ds = self._check_fused(query, codebook, n_query)
+        part1, query, codebook, ds, part2, full, cells = self._residual_tables(full, part1, part2, cells, query,
+                                                                               codebook, n_query, n_probe)
         threshold = _checked_threshold(threshold, n_query)
         require_gpu(data, part1, query, codebook, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
                     n_probe_list, _tensor_or_none(threshold))
@@ -1118,22 +1121,12 @@ class SlotFilterBuildHip:
         return bits
 
 
-class IVFPQFilteredTopkHip:
+class IVFPQFilteredTopkHip(_IVFPQListScan):
     """Filtered top-k over the lists of IVFPQIndex (tpq_ivfpq_scan_filtered_topk / _residual_topk,
     csrc/scan_filtered.hip): the k best candidates of IVFPQRangeHip whose slot is allowed by the query's row of filter
     bits, by (value descending, address ascending), the value being that of the exact reference-layout scan; the
     semantics are defined in include/torchpq_amd.h.  The scan reads CellContainer._storage itself: there is no
     scan-layout route."""
-
-    def __init__(self, m=8):
-        assert m % 4 == 0
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
-
-    _n_split = IVFPQTopkHip._n_split
-    _check_lists = IVFPQRangeHip._check_lists
-    _check_fused = IVFPQRangeHip._check_fused
 
     @staticmethod
     def _check_filter(filter_bits, filter_of_query, n_data, n_query):
@@ -1158,13 +1151,7 @@ class IVFPQFilteredTopkHip:
         """
         n_data, n_query, n_probe = self._check_lists(data, is_empty, cell_start, cell_size, n_probe_list)
         filter_of_query = self._check_filter(filter_bits, filter_of_query, n_data, n_query)
-        ds = 0
-        if precomputed is not None:
-            assert precomputed.shape == (self.m, n_query, 256) and precomputed.dtype == torch.float32
-            precomputed, query, codebook = precomputed.contiguous(), None, None
-        else:
-            assert query is not None and codebook is not None
-            query, codebook, ds = self._check_fused(query, codebook, n_query)
+        precomputed, query, codebook, ds = self._plain_table(precomputed, query, codebook, n_query)
         assert distance in ("euclidean", "cosine", "inner")
         assert 0 < k <= 1024
         cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
@@ -1192,21 +1179,8 @@ class IVFPQFilteredTopkHip:
         filter_of_query = self._check_filter(filter_bits, filter_of_query, n_data, n_query)
         assert base_sims.shape == (n_query, n_probe) and base_sims.dtype == torch.float32
         base_sims = base_sims.contiguous()
-        ds = 0
-        if full is not None:
-            assert full.shape == (n_query, n_probe, self.m, 256) and full.dtype == torch.float32
-            full, part1, part2, cells, query, codebook = full.contiguous(), None, None, None, None, None
-        else:
-            assert part2 is not None and cells is not None
-            assert part2.shape[1:] == (self.m, 256) and part2.dtype == torch.float32
-            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
-            part2, cells = part2.contiguous(), cells.contiguous()
-            if part1 is not None:
-                assert part1.shape == (n_query, self.m, 256) and part1.dtype == torch.float32
-                part1, query, codebook = part1.contiguous(), None, None
-            else:
-                assert query is not None and codebook is not None
-                query, codebook, ds = self._check_fused(query, codebook, n_query)
+        part1, query, codebook, ds, part2, full, cells = self._residual_tables(full, part1, part2, cells, query,
+                                                                               codebook, n_query, n_probe)
         assert 0 < k <= 1024
         cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
         require_gpu(data, part1, query, codebook, part2, full, cells, base_sims, is_empty, cell_start, cell_size,
@@ -1222,60 +1196,19 @@ class IVFPQFilteredTopkHip:
         return topk_result(values, address, ids)
 
 
-class IVFPQ4FilteredTopkHip:
+class IVFPQ4FilteredTopkHip(_IVFPQ4Scan):
     """Filtered top-k over the lists of IVFPQ4Index (tpq_ivfpq4_scan_filtered_topk / _residual_topk,
     csrc/scan_pq4_filtered.hip): the result of IVFPQ4TopkHip / IVFPQ4ResidualTopkHip among the slots the query's row of
     filter bits allows, bit for bit what those give with `is_empty | ~allowed_row` as the tombstone mask; the semantics
     are defined in include/torchpq_amd.h."""
 
-    def __init__(self, m=8):
-        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last call
-
-    _n_split = IVFFlatTopkHip._n_split
-
     def _scan(self, symbol, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, k, filter_bits,
               filter_of_query, is_empty, distance, n_split, slots_hint):
         """both calls; `residual` is () or (centroids, cells)"""
-        n_slots = codes.shape[1]
-        m, ds, kk = codebook.shape
-        n_query, n_probe = cell_start.shape
-        assert m == self.m and kk == 16 and ds >= 1
-        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
-        assert query.shape == (m * ds, n_query)
-        assert query.dtype == codebook.dtype == torch.float32
-        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
-        filter_of_query = IVFPQFilteredTopkHip._check_filter(filter_bits, filter_of_query, n_slots, n_query)
-        assert filter_bits.is_contiguous()
-        tables = ()
-        if residual:
-            centroids, cells = residual
-            assert centroids.dtype == torch.float32
-            assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
-            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
-            centroids, cells = centroids.contiguous(), cells.contiguous()
-            tables = (ptr(centroids), ptr(cells), centroids.shape[0])
-        assert distance in ("euclidean", "cosine", "inner")
-        assert 0 < k <= 1024
-        query = query.contiguous()
-        codebook = codebook.contiguous()
-        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
-        require_gpu(codes, query, codebook, *residual, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
-                    filter_of_query)
-        device = codes.device
-        values, address = alloc_pair(n_query, k, device)
-        if n_query == 0:
-            return values, address
-        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfpq4_scan_workspace_bytes, n_query, k,
-                                                     n_split, slots_hint, device)
-        call(symbol, device,
-             ptr(codes), ptr(query), ptr(codebook), *tables, ptr(is_empty), ptr(cell_start), ptr(cell_size),
-             ptr(n_probe_list), ptr(filter_bits), ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1],
-             ptr(values), ptr(address), n_slots, m, ds, n_query, n_probe, k, metric_code(distance), n_split, ptr(ws),
-             ws_bytes)
-        return values, address
+        assert filter_bits is not None
+        inputs, flt, shape, tensors = self._inputs(codes, query, codebook, residual, cell_start, cell_size,
+                                                   n_probe_list, is_empty, distance, filter_bits, filter_of_query)
+        return self._topk(symbol, k, n_split, slots_hint, distance, inputs, flt, shape, tensors)
 
     def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, k, filter_bits,
                  filter_of_query=None, is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
@@ -1297,60 +1230,22 @@ class IVFPQ4FilteredTopkHip:
                           n_split, slots_hint)
 
 
-class IVFPQ4RangeHip:
+class IVFPQ4RangeHip(_IVFPQ4Scan):
     """Range search over the lists of IVFPQ4Index (tpq_ivfpq4_range_count / _fill and their residual forms,
     csrc/scan_pq4_range.hip): every candidate of IVFPQ4TopkHip / IVFPQ4ResidualTopkHip whose value is >= the query's
     threshold, in scan order, optionally among the slots the query's row of filter bits allows; a hit carries the bits
     those scans return for the slot; the semantics are defined in include/torchpq_amd.h."""
 
-    def __init__(self, m=8):
-        assert m % 8 == 0 and 8 <= m <= 256, "4-bit codes are stored 8 sub-quantizers per word; 8 <= m <= 256"
-        self.m = m
-        self.n_cus = None
-        self.last_n_split = None   # diagnostics / tests: workgroups per query of the last plain call
-
-    _n_split = IVFFlatTopkHip._n_split
-
-    def _inputs(self, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, threshold, filter_bits,
-                filter_of_query, is_empty, distance):
-        """the checks both calls share; `residual` is () or (centroids, cells) -> (the count / fill arguments in
-        front of the threshold, the checked threshold, (n_slots, m, ds, n_query, n_probe, metric), device)"""
-        n_slots = codes.shape[1]
-        m, ds, kk = codebook.shape
-        n_query, n_probe = cell_start.shape
-        assert m == self.m and kk == 16 and ds >= 1
-        assert codes.shape == (m // 8, n_slots, 4) and codes.dtype == torch.uint8 and codes.is_contiguous()
-        assert query.shape == (m * ds, n_query)
-        assert query.dtype == codebook.dtype == torch.float32
-        _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
-        flt = (None, None, 0, 0)
-        if filter_bits is not None:
-            filter_of_query = IVFPQFilteredTopkHip._check_filter(filter_bits, filter_of_query, n_slots, n_query)
-            assert filter_bits.is_contiguous()
-            flt = (ptr(filter_bits), ptr(filter_of_query), filter_bits.shape[0], filter_bits.shape[1])
-        else:
-            assert filter_of_query is None, "filter_of_query without filter_bits"
-        tables = ()
-        if residual:
-            centroids, cells = residual
-            assert centroids.dtype == torch.float32
-            assert centroids.dim() == 2 and centroids.shape[0] >= 1 and centroids.shape[1] == m * ds
-            assert cells.shape == (n_query, n_probe) and cells.dtype == torch.int64
-            centroids, cells = centroids.contiguous(), cells.contiguous()
-            tables = (ptr(centroids), ptr(cells), centroids.shape[0])
-            residual = (centroids, cells)
-        assert distance in ("euclidean", "cosine", "inner")
-        threshold = _checked_threshold(threshold, n_query)
-        query = query.contiguous()
-        codebook = codebook.contiguous()
-        cell_start, cell_size = cell_start.contiguous(), cell_size.contiguous()
-        require_gpu(codes, query, codebook, *residual, is_empty, cell_start, cell_size, n_probe_list, filter_bits,
-                    filter_of_query, _tensor_or_none(threshold))
-        # (the tensors made contiguous above live until the passes have been launched: the closure holds them)
-        keep = (query, codebook, residual, cell_start, cell_size, filter_of_query)
-        inputs = (ptr(codes), ptr(query), ptr(codebook), *tables, ptr(is_empty), ptr(cell_start), ptr(cell_size),
-                  ptr(n_probe_list), *flt)
-        return inputs, threshold, (n_slots, m, ds, n_query, n_probe, metric_code(distance)), codes.device, keep
+    def _range_inputs(self, codes, query, codebook, residual, cell_start, cell_size, n_probe_list, threshold,
+                      filter_bits, filter_of_query, is_empty, distance):
+        """both calls; `residual` is () or (centroids, cells) -> (the count / fill arguments in front of the
+        threshold, the checked threshold, (n_slots, m, ds, n_query, n_probe, metric), device, the tensors those
+        arguments point into)"""
+        inputs, flt, shape, keep = self._inputs(codes, query, codebook, residual, cell_start, cell_size, n_probe_list,
+                                                is_empty, distance, filter_bits, filter_of_query)
+        threshold = _checked_threshold(threshold, shape[3])
+        require_gpu(*keep, _tensor_or_none(threshold))
+        return (*inputs, *flt), threshold, (*shape, metric_code(distance)), codes.device, keep
 
     def __call__(self, codes, query, codebook, cell_start, cell_size, n_probe_list, threshold, filter_bits=None,
                  filter_of_query=None, is_empty=None, distance="euclidean", n_split=None, slots_hint=None):
@@ -1363,7 +1258,7 @@ class IVFPQ4RangeHip:
         values[lims[q]:lims[q+1]] / address[lims[q]:lims[q+1]], probe rank ascending, then address ascending.
         Synchronises once: the number of hits sizes the outputs.
         """
-        inputs, threshold, shape, device, keep = self._inputs(
+        inputs, threshold, shape, device, keep = self._range_inputs(
             codes, query, codebook, (), cell_start, cell_size, n_probe_list, threshold, filter_bits, filter_of_query,
             is_empty, distance)
         n_query = shape[3]
@@ -1382,7 +1277,7 @@ class IVFPQ4RangeHip:
                  filter_bits=None, filter_of_query=None, is_empty=None, distance="euclidean"):
         """Residual codes: centroids [n_cells, d] and cells [n_query, max_n_probe] as IVFPQ4ResidualTopkHip, everything
         else, and the result, as __call__; one workgroup per (query, probe): there is no n_split"""
-        inputs, threshold, shape, device, keep = self._inputs(
+        inputs, threshold, shape, device, keep = self._range_inputs(
             codes, query, codebook, (centroids, cells), cell_start, cell_size, n_probe_list, threshold, filter_bits,
             filter_of_query, is_empty, distance)
         n_query, n_probe = shape[3], shape[4]
