@@ -758,6 +758,47 @@ int tpq_ivf_flat_cells_topk(const float* vectors, const float* query, const uint
 int tpq_ivf_flat_cells_stop_after(int stage);
 
 /* ---------------------------------------------------------------------------
+ * IVFFlat16Index list scan + top-k and range search (csrc/scan_flat_f16.hip): the probed cells hold the vectors as
+ * fp16 -- half the bytes of tpq_ivfflat_scan_topk per scanned slot, nothing trained.
+ *
+ * vectors      u32 [rows][n_slots], rows = ceil(d / 2): dword r of a slot holds component 2r as an IEEE half in its
+ *              low 16 bits and component 2r + 1 in its high 16 bits; for odd d the last high half is stored as +0 and
+ *              is never read into a value.  It is CellContainer._storage of code_size = 4 rows, contiguous_size = 4
+ *              (u8 [rows][n_slots][4]) read as 32-bit words: row-major over dimension pairs, slot-contiguous.
+ * Every other argument is that of tpq_ivfflat_scan_topk / tpq_ivfflat_range_count / tpq_ivfflat_range_fill, the
+ * query f32 [d][nq] included.
+ *
+ * Value of a slot: x32_i = the stored half of component i converted to fp32 (exact; fp16 subnormals keep their value),
+ * then the chain of tpq_ivfflat_scan_topk unchanged -- all fp32, no fma, i ascending, acc starts at 0.f:
+ *       TPQ_METRIC_NEG_SQ_L2:  t = q_i - x32_i;  acc = acc - t*t
+ *       TPQ_METRIC_INNER:      acc = acc + q_i * x32_i
+ * Candidates, NaN exclusion, -inf handling, order (value descending, address ascending), pads (-inf, -1), the skipped
+ * repeated probe start and the mask contract (the byte of a slot before any byte of its vector) are those of
+ * tpq_ivfflat_scan_topk; hits, scan order and the count / offsets / fill protocol those of tpq_ivfflat_range_count /
+ * _fill.  In one sentence: the result is bit for bit what the fp32 entry points return over the same slots holding
+ * float(half(x)).
+ * The list frame is the fp32 scan's, so its size functions serve: the workspace is
+ * tpq_ivfflat_scan_workspace_bytes(nq, k, n_split) bytes and the segments are tpq_ivfflat_range_segments(nq, n_split).
+ * The argument checks are the same, in the same order, all before any HIP call.  Any d >= 1; 1 <= k <= 1024;
+ * n_slots < 2^31 - 1, else TPQ_ERR_UNSUPPORTED.  The range result is the same for any n_split; no global atomics.
+ * (The symbols are spelled tpq_ivf_flat16_* for the reason tpq_ivf_flat_cells_* are.)
+ * ------------------------------------------------------------------------- */
+#define TPQ_HAS_IVFFLAT_F16 1
+int tpq_ivf_flat16_scan_topk(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                             const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                             float* out_vals, int64_t* out_addr, int64_t n_slots, int d, int nq, int max_nprobe, int k,
+                             int metric, int n_split, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+int tpq_ivf_flat16_range_count(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                               const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                               const float* threshold, int32_t* wave_counts, int64_t n_slots, int d, int nq,
+                               int max_nprobe, int metric, int n_split, tpq_stream_t stream);
+int tpq_ivf_flat16_range_fill(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                              const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                              const float* threshold, const int64_t* wave_offsets, float* out_vals, int64_t* out_addr,
+                              int64_t n_slots, int d, int nq, int max_nprobe, int metric, int n_split,
+                              tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * IVFPQ4Index list scan + top-k: product-quantized lists with 16 centroids per sub-quantizer (4-bit codes; the
  * reference began such a path, top-1 only, and has no index for it).
  *

@@ -4,6 +4,7 @@
 # one of the scan headers (scan_device.h and the per-stage scan_*.h it includes) rebuilds the scan units only -- not the
 # k-means / cascade units, which take the longest -- and scan_ref.h (the reference-layout kernels) scan.hip, scan_flat.hip and
 # scan_pq4.hip alone (the 4-bit list scan takes scan_device.h and scan_ref.h as scan_flat.hip does, so every scan header rebuilds it;
+# scan_flat_f16.hip, the fp16 list scan of IVFFlat16Index, takes the same two;
 # scan_pq4.h -- the table build, the word loop, the grouped tables, the 4-bit entry points' checks and LDS sizes -- is
 # shared with scan_pq4_filtered.hip, the filtered 4-bit scan, and scan_pq4_range.hip, the 4-bit range search, and rebuilds those three);
 # scan_list.h (the frame of a list kernel) is included by scan_ref.h, scan_range.hip and, for clamped_n_probe, scan_packed_kernel.h,
@@ -54,15 +55,15 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_flat_cells.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_flat_f16.hip scan_flat_cells.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   unit_flags=""
   # flat_filtered.hip is compiled with the packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) switched
   # off for the device: its epilogues are one scalar chain per value (the host pass warns that it does not know the
   # feature and ignores it; tools/kernel_regs.py takes the same flags)
-  # (scan_flat_cells.hip, the cell-major IVFFlat route, likewise)
-  [[ "$src" == flat_filtered.hip || "$src" == scan_flat_cells.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
+  # (scan_flat_cells.hip, the cell-major IVFFlat route, and scan_flat_f16.hip, the fp16 list scan, likewise)
+  [[ "$src" == flat_filtered.hip || "$src" == scan_flat_cells.hip || "$src" == scan_flat_f16.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
   if stale "$obj" "${HERE}/${src}"; then
     cmds+=("'$HIPCC' ${FLAGS[*]} ${unit_flags} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/${src}' -o '$obj' ${EXTRA_FLAGS:-}")
   fi

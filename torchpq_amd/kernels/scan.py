@@ -1034,6 +1034,84 @@ class IVFFlatRangeHip(_ListScan):
         return _range_two_pass(n_query, device, threshold, passes)
 
 
+def _flat16_inputs(vectors, query, cell_start, cell_size, n_probe_list, is_empty, distance):
+    """What the two fp16 list-scan wrappers check: vectors int32 [ceil(d / 2), n_slots] (or [.., n_slots, 1]:
+    CellContainer._storage.view(torch.int32)), two halves per word; d is the query's.  Returns (vectors, query,
+    (n_slots, d, n_query, n_probe)) -- the caller keeps the tensors until it has launched."""
+    if vectors.dim() == 3:
+        assert vectors.shape[2] == 1
+        vectors = vectors[:, :, 0]
+    rows, n_slots = vectors.shape
+    d, n_query = query.shape
+    n_probe = cell_start.shape[1]
+    assert d >= 1 and rows == (d + 1) // 2, (rows, d)
+    assert vectors.dtype == torch.int32 and query.dtype == torch.float32
+    assert cell_start.shape[0] == n_query
+    _check_lists(n_slots, is_empty, cell_start, cell_size, n_probe_list)
+    assert distance in ("euclidean", "cosine", "inner")
+    return vectors, query.contiguous(), (n_slots, d, n_query, n_probe)
+
+
+class IVFFlat16TopkHip(_ListScan):
+    """The list scan of IVFFlat16Index (tpq_ivf_flat16_scan_topk, csrc/scan_flat_f16.hip): the probed cells hold the
+    vectors as fp16, two components per 32-bit word; the value -- IVFFlatTopkHip's over float(half(x)), bit for bit --
+    is defined in include/torchpq_amd.h."""
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          vectors: [ceil(d / 2), n_slots] int32: word r of a slot holds component 2r (low half) and 2r + 1 (high half)
+          query: [d, n_query] float32 (normalised by the caller for "cosine")
+          cell_start, cell_size, n_probe_list, is_empty: as IVFFlatTopkHip
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1)
+        """
+        vectors, query, shape = _flat16_inputs(vectors, query, cell_start, cell_size, n_probe_list, is_empty, distance)
+        assert 0 < k <= 1024
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list)
+        device = vectors.device
+        n_query = shape[2]
+        values, address = alloc_pair(n_query, k, device)
+        if n_query == 0:
+            return values, address
+        n_split, ws, ws_bytes = _split_and_workspace(self, load().tpq_ivfflat_scan_workspace_bytes, n_query, k,
+                                                     n_split, slots_hint, device)
+        call("tpq_ivf_flat16_scan_topk", device,
+             ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+             ptr(values), ptr(address), *shape, k, metric_code(distance), n_split, ptr(ws), ws_bytes)
+        return values, address
+
+
+class IVFFlat16RangeHip(_ListScan):
+    """Range search over the lists of IVFFlat16Index (tpq_ivf_flat16_range_count / tpq_ivf_flat16_range_fill,
+    csrc/scan_flat_f16.hip): every candidate of IVFFlat16TopkHip whose value is >= the query's threshold, in scan order."""
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, threshold, is_empty=None,
+                 distance="euclidean", n_split=None, slots_hint=None):
+        """
+          vectors, query, cell_start, cell_size, n_probe_list, is_empty: as IVFFlat16TopkHip
+          threshold: a Python float, or [n_query] float32 -- one per query
+        returns (lims [n_query + 1] int64, values [total] float32, address [total] int64), as IVFFlatRangeHip.
+        Synchronises once: the number of hits sizes the outputs.
+        """
+        vectors, query, shape = _flat16_inputs(vectors, query, cell_start, cell_size, n_probe_list, is_empty, distance)
+        n_query = shape[2]
+        threshold = _checked_threshold(threshold, n_query)
+        require_gpu(vectors, query, is_empty, cell_start, cell_size, n_probe_list, _tensor_or_none(threshold))
+        device = vectors.device
+        inputs = (ptr(vectors), ptr(query), ptr(is_empty), ptr(cell_start), ptr(cell_size), ptr(n_probe_list))
+
+        def passes():
+            split = self._n_split(n_query, device, slots_hint) if n_split is None else n_split
+            self.last_n_split = split
+            n_seg = load().tpq_ivfflat_range_segments(n_query, split)
+            assert n_seg == n_query * split * 8, (n_query, split)
+            tail = (*shape, metric_code(distance), split)
+            return (n_seg,
+                    lambda thr, counts: call("tpq_ivf_flat16_range_count", device, *inputs, thr, counts, *tail),
+                    lambda thr, *out: call("tpq_ivf_flat16_range_fill", device, *inputs, thr, *out, *tail))
+        return _range_two_pass(n_query, device, threshold, passes)
+
+
 class IVFPQRangeHip(_IVFPQListScan):
     """Range search over the lists of IVFPQIndex (tpq_ivfpq_range_count / _fill and their residual forms,
     csrc/scan_range.hip): every candidate of IVFPQTopkHip whose value is >= the query's threshold, in scan order, the
