@@ -799,6 +799,30 @@ int tpq_ivf_flat16_range_fill(const uint32_t* vectors, const float* query, const
                               tpq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * IVFFlat16Index list scan + top-k, large batches, CELL-MAJOR (csrc/scan_flat_f16_cells.hip): the outputs of
+ * tpq_ivf_flat16_scan_topk -- values, addresses, order and pads, bit for bit -- by the five stages of
+ * tpq_ivf_flat_cells_topk.  Stage 1 is tpq_ivf_flat16_scan_topk over each query's first `first_probe` probes; the
+ * candidate kernel feeds the stored halves to v_mfma_f32_32x32x16_f16 as they lie, against the query scaled by a power
+ * of two per query and rounded to halves (one product; the band is derived in the unit's head); the finish kernel
+ * re-evaluates the candidates with the chain of tpq_ivf_flat16_scan_topk.
+ *
+ * vectors      u32 [d / 2][n_slots], the layout of tpq_ivf_flat16_scan_topk; d a multiple of 8.
+ * Every other argument, the flag protocol (flags i32 [nq] at byte 256 of the workspace, their number in word 0; the
+ * caller runs tpq_ivf_flat16_scan_topk for a flagged query) and the errors are those of tpq_ivf_flat_cells_topk.  A
+ * finite query of any magnitude is served; it is not flagged for its range.
+ * workspace    tpq_ivf_flat16_cells_workspace_bytes(...) bytes: the regions of tpq_ivf_flat_cells_topk in their order,
+ *              then the queries' scale exponents i32 [nq] (seed kernel).  It need NOT be zeroed.
+ * TPQ_ERR_UNSUPPORTED, nothing launched, also for a d that is not a multiple of 8.
+ * ------------------------------------------------------------------------- */
+#define TPQ_HAS_IVFFLAT_F16_CELLS 1
+size_t tpq_ivf_flat16_cells_workspace_bytes(int nq, int max_nprobe, int n_cells, int k, int cand_cap, int first_probe);
+int tpq_ivf_flat16_cells_topk(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                              const int64_t* cells, const int64_t* cell_start, const int64_t* cell_size,
+                              const int64_t* n_probe_list, float* out_vals, int64_t* out_addr, int64_t n_slots,
+                              int n_cells, int d, int nq, int max_nprobe, int k, int metric, int first_probe,
+                              int cand_cap, void* workspace, size_t workspace_bytes, tpq_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * IVFPQ4Index list scan + top-k: product-quantized lists with 16 centroids per sub-quantizer (4-bit codes; the
  * reference began such a path, top-1 only, and has no index for it).
  *

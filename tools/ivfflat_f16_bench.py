@@ -5,10 +5,13 @@ the same coarse codebook, at the shape of DESIGN 3.8, through the public API, al
 Per step, interleaved (HIP-event timed, median / min / max over the steps), for every batch size of --batches:
   fp32 query-major          IVFFlatIndex.search(k), use_cell_major off
   fp32 cell-major           IVFFlatIndex.search(k), use_cell_major on
-  fp16 query-major          IVFFlat16Index.search(k)
+  fp16 query-major          IVFFlat16Index.search(k), use_cell_major off
+  fp16 cell-major           IVFFlat16Index.search(k), use_cell_major on (csrc/scan_flat_f16_cells.hip)
 and, on the coarse step's cells, the two list scans alone (IVFFlatTopkHip, IVFFlat16TopkHip) with the bytes they scan:
 sum over (query, probe) of cell_size x code_size -- what the algorithm reads, served mostly by the caches, so not an HBM
-rate.  Also: the device bytes of both storages and the mean overlap of the fp16 index's top-k ids with the fp32 index's.
+rate.  Also: whether each cell-major route returns its query-major route's ids, the candidates per query of both
+cell-major routes (the `cnt` words of a kept workspace from one more, untimed search: the fp16 route's band is wider,
+and this is where it shows), the device bytes of both storages and the mean overlap of the fp16 index's top-k ids with the fp32 index's.
 Prints one JSON line and writes it to --out.
 
     python tools/ivfflat_f16_bench.py [--n 1000000 --k 100 --steps 10 --warmup 3 --out profiles/ivfflat_f16_bench.json]
@@ -64,11 +67,23 @@ def main():
     for idx in (f32, f16):
         idx.release_spare()
         idx.n_probe = args.n_probe
-    f32.cell_major_min_batch = 1
+        idx.cell_major_min_batch = 1
 
-    def search32(x, cell_major):
-        f32.use_cell_major = cell_major
-        return f32.search(x, k=args.k)
+    def search(idx, x, cell_major):
+        idx.use_cell_major = cell_major
+        return idx.search(x, k=args.k)
+
+    def candidates(idx, x):
+        """mean and maximum candidates per query of the index's cell-major route: the i32 [nq] `cnt` region of the
+        workspace (behind the control words, the flags, the thresholds and |q|^2: include/torchpq_amd.h)"""
+        idx._flat_cells.keep_workspace = True
+        search(idx, x, True)
+        nq = x.shape[1]
+        at = 256 + 3 * ((4 * nq + 255) // 256 * 256)
+        cnt = idx._flat_cells.last_workspace[at:at + 4 * nq].view(torch.int32).double()
+        idx._flat_cells.keep_workspace, idx._flat_cells.last_workspace = False, None
+        return {"mean": round(cnt.mean().item(), 1), "max": int(cnt.max().item()),
+                "redone": int(idx._flat_cells.last_redone), "cand_cap": idx._flat_cells.cand_cap}
 
     def scan_leg(idx, x):
         """the list scan alone on the index's own coarse cells -> (call, scanned bytes)"""
@@ -88,9 +103,9 @@ def main():
         x = queries[:, :nq].contiguous()
         scan32, bytes32 = scan_leg(f32, x)
         scan16, bytes16 = scan_leg(f16, x)
-        legs = {"fp32_query_major": lambda: search32(x, False), "fp32_cell_major": lambda: search32(x, True),
-                "fp16_query_major": lambda: f16.search(x, k=args.k), "fp32_scan_kernel": scan32,
-                "fp16_scan_kernel": scan16}
+        legs = {"fp32_query_major": lambda: search(f32, x, False), "fp32_cell_major": lambda: search(f32, x, True),
+                "fp16_query_major": lambda: search(f16, x, False), "fp16_cell_major": lambda: search(f16, x, True),
+                "fp32_scan_kernel": scan32, "fp16_scan_kernel": scan16}
         events = {name: [] for name in legs}
         out = {}
         for step in range(args.warmup + args.steps):
@@ -104,14 +119,20 @@ def main():
             rec[name]["scanned_bytes"] = nbytes
             rec[name]["scanned_gbytes_per_s"] = round(nbytes / (rec[name]["median_ms"] * 1e-3) / 1e9, 1)
         for a, b in (("fp32_query_major", "fp16_query_major"), ("fp32_scan_kernel", "fp16_scan_kernel"),
-                     ("fp32_cell_major", "fp16_query_major")):
+                     ("fp32_cell_major", "fp16_query_major"), ("fp16_query_major", "fp16_cell_major"),
+                     ("fp32_cell_major", "fp16_cell_major")):
             rec[f"ratio_{a}_over_{b}"] = round(rec[a]["median_ms"] / rec[b]["median_ms"], 3)
         rec["cell_major_ids_equal_query_major"] = bool(torch.equal(out["fp32_cell_major"][1],
                                                                    out["fp32_query_major"][1]))
+        rec["fp16_cell_major_ids_equal_query_major"] = bool(torch.equal(out["fp16_cell_major"][1],
+                                                                        out["fp16_query_major"][1]))
+        rec["fp16_cell_major_values_equal_query_major"] = bool(torch.equal(
+            out["fp16_cell_major"][0].view(torch.int32), out["fp16_query_major"][0].view(torch.int32)))
+        rec["candidates_per_query"] = {"fp32_cell_major": candidates(f32, x), "fp16_cell_major": candidates(f16, x)}
         rec["topk_id_overlap_fp16_with_fp32"] = recall(out["fp16_query_major"][1], out["fp32_query_major"][1])
         result["batches"][str(nq)] = rec
         del out
-    f32.use_cell_major = False
+    f32.use_cell_major = f16.use_cell_major = False
     line = json.dumps(result)
     print(line)
     if args.out:

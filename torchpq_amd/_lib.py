@@ -123,6 +123,8 @@ SIGNATURES = {
     "tpq_ivf_flat16_scan_topk": (_i, [_vp] * 8 + [_i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ivf_flat16_range_count": (_i, [_vp] * 8 + [_i64, _i, _i, _i, _i, _i, _vp]),
     "tpq_ivf_flat16_range_fill": (_i, [_vp] * 10 + [_i64, _i, _i, _i, _i, _i, _vp]),
+    "tpq_ivf_flat16_cells_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "tpq_ivf_flat16_cells_topk": (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ivfpq4_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "tpq_ivfpq4_scan_topk": (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tpq_ivfpq4_scan_residual_topk": (_i, [_vp] * 5 + [_i] + [_vp] * 6 + [_i64, _i, _i, _i, _i, _i, _i, _i, _vp, _sz,

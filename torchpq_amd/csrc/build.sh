@@ -18,7 +18,9 @@
 # probe_sims; mfma_util.h (the MFMA units' shared device helpers) rebuilds the cascade units, assign_fast, coarse_probe,
 # max_sim, centroid_update, kmeans_split, lut, flat_topk, flat_range and flat_filtered; sims_chunk.h (the fp32 similarity tile) rebuilds
 # coarse_probe, flat_topk, flat_range and flat_filtered; sims_rows.h (the tile on rows the caller names) rebuilds flat_filtered and
-# scan_flat_cells (the cell-major IVFFlat route), which also takes scan_list.h and, with scan_flat.hip, scan_flat_cells.h; flat_merge.h (the exact top-k's queue size and merge kernel) rebuilds
+# scan_flat_cells (the cell-major IVFFlat route), which also takes scan_list.h and, with scan_flat.hip, scan_flat_cells.h;
+# scan_flat_cells_stages.h (the cell-major routes' shared stages) rebuilds scan_flat_cells and scan_flat_f16_cells, scan_flat_f16.h
+# (the fp16 value of a slot, the capped fp16 scan) scan_flat_f16 and scan_flat_f16_cells; flat_merge.h (the exact top-k's queue size and merge kernel) rebuilds
 # flat_topk and flat_filtered.  The exact assign (max_sim.hip) and the centroid update
 # (centroid_update.hip) are units of their own: a change to one does not recompile the other.
 # The library is linked from the objects of the unit list below, not from whatever build/ holds: an object left
@@ -55,7 +57,7 @@ for m in 64 120 128 96 56 48 40 32 28 24 20 16 12 8 4; do  # = TPQ_PACKED_M_LIST
     cmds+=("'$HIPCC' ${FLAGS[*]} -DTPQ_PACKED_M=${m} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/scan_packed.hip' -o '$obj' ${EXTRA_FLAGS:-}")
   fi
 done
-for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_flat_f16.hip scan_flat_cells.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
+for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_update.hip assign_cascade.hip assign_fast.hip probe_sims.hip lloyd.hip scan.hip scan_order.hip scan_cells.hip scan_flat.hip scan_flat_f16.hip scan_flat_cells.hip scan_flat_f16_cells.hip scan_pq4.hip scan_pq4_filtered.hip scan_pq4_range.hip scan_range.hip scan_filtered.hip kmeans_split.hip container.hip lut.hip pack.hip rerank.hip flat_topk.hip flat_range.hip flat_filtered.hip ubench.hip api.cpp; do
   obj="${HERE}/build/${src%.*}.o"
   objs+=("$obj")
   unit_flags=""
@@ -63,7 +65,8 @@ for src in cascade_core.hip select.hip coarse_probe.hip max_sim.hip centroid_upd
   # off for the device: its epilogues are one scalar chain per value (the host pass warns that it does not know the
   # feature and ignores it; tools/kernel_regs.py takes the same flags)
   # (scan_flat_cells.hip, the cell-major IVFFlat route, and scan_flat_f16.hip, the fp16 list scan, likewise)
-  [[ "$src" == flat_filtered.hip || "$src" == scan_flat_cells.hip || "$src" == scan_flat_f16.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
+  # (scan_flat_f16_cells.hip, the fp16 lists' cell-major route, shares their kernels and value code: the same flags)
+  [[ "$src" == flat_filtered.hip || "$src" == scan_flat_cells.hip || "$src" == scan_flat_f16.hip || "$src" == scan_flat_f16_cells.hip ]] && unit_flags="-Xclang -target-feature -Xclang -packed-fp32-ops"
   if stale "$obj" "${HERE}/${src}"; then
     cmds+=("'$HIPCC' ${FLAGS[*]} ${unit_flags} -MD -MF '${obj%.o}.d' -x hip -c '${HERE}/${src}' -o '$obj' ${EXTRA_FLAGS:-}")
   fi

@@ -18,13 +18,15 @@
 // scan_device.h); the masked form keeps scan_flat.hip's contract -- mask byte before any vector byte, an empty tile reads
 // nothing, a tile below kCompactBelow live slots goes through the pending list, any other is valued in place.
 // Range search: count and fill passes over a wave's contiguous chunk of tiles with the same value code; no global atomic.
+// (low_half / high_half, pair_step and slot_value are in scan_flat_f16.h: the cell-major route's finish kernel,
+// scan_flat_f16_cells.hip, values its candidates with the same definition.)
 #include "scan_device.h"
+#include "scan_flat_f16.h"
 #include "scan_ref.h"
 
 namespace tpq {
 namespace flat16 {
 
-constexpr int kRowsInFlight = 8;    // dword loads in flight per lane: 16 dimensions, 8 x 256 B per wave
 constexpr int kMaskTilesAhead = 4;  // tiles whose mask bytes are loaded together (as scan_flat.hip)
 constexpr int kCompactBelow = 4;    // a tile with fewer live slots than this is compacted (as scan_flat.hip)
 
@@ -34,45 +36,6 @@ struct Flat16Args {
 };
 
 __host__ __device__ constexpr size_t query_bytes(int d) { return align16((size_t)d * 4); }
-
-__device__ __forceinline__ float low_half(uint32_t w) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
-}
-__device__ __forceinline__ float high_half(uint32_t w) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
-}
-
-// the two components of one dword, at xq[0] and xq[1] of the query
-template <int METRIC>
-__device__ __forceinline__ float pair_step(float v, const float* xq, uint32_t w) {
-  v = metric_step<METRIC>(v, xq[0], low_half(w));
-  return metric_step<METRIC>(v, xq[1], high_half(w));
-}
-
-// The value of a slot: `col` is its dword of row 0, rows are `stride` dwords apart.  GROUPS groups of kRowsInFlight
-// rows per trip (the order of the sum does not depend on it); rows left over one by one; the low half alone of the
-// last row when d is odd.
-template <int METRIC, int GROUPS>
-__device__ __forceinline__ float slot_value(const uint32_t* __restrict__ col, const float* xq, int d, int64_t stride) {
-  float v = 0.f;
-  const int pairs = d >> 1;
-  int r = 0;
-#pragma unroll GROUPS
-  for (; r + kRowsInFlight <= pairs; r += kRowsInFlight) {
-    uint32_t w[kRowsInFlight];
-#pragma unroll
-    for (int u = 0; u < kRowsInFlight; ++u) w[u] = col[(int64_t)u * stride];
-    col += (int64_t)kRowsInFlight * stride;
-#pragma unroll
-    for (int u = 0; u < kRowsInFlight; ++u) v = pair_step<METRIC>(v, xq + 2 * (r + u), w[u]);
-  }
-  for (; r < pairs; ++r) {
-    v = pair_step<METRIC>(v, xq + 2 * r, *col);
-    col += stride;
-  }
-  if (d & 1) v = metric_step<METRIC>(v, xq[d - 1], low_half(*col));
-  return v;
-}
 
 // every thread of the workgroup takes its share of the query's d floats (the caller's barrier publishes them)
 __device__ __forceinline__ void stage_query(const ScanArgs& a, int q, int d, float* xq) {
@@ -283,11 +246,13 @@ static int range_pass(const char* what, const uint32_t* vectors, const float* qu
 
 using namespace tpq;
 
-extern "C" int tpq_ivf_flat16_scan_topk(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
-                                        const int64_t* cell_start, const int64_t* cell_size,
-                                        const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
-                                        int64_t n_slots, int d, int nq, int max_nprobe, int k, int metric, int n_split,
-                                        void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
+// tpq_ivf_flat16_scan_topk over each query's first min(n_probe_list[q], probe_cap) probes (ScanArgs::probe_cap; 0: no
+// cap): the threshold pass of the cell-major route (scan_flat_f16_cells.hip) -- the same kernels, checks and launches
+int tpq::ivf_flat16_scan_topk_capped(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                                     const int64_t* cell_start, const int64_t* cell_size, const int64_t* n_probe_list,
+                                     float* out_vals, int64_t* out_addr, int64_t n_slots, int d, int nq, int max_nprobe,
+                                     int k, int metric, int n_split, int probe_cap, void* workspace,
+                                     size_t workspace_bytes, tpq_stream_t stream) {
   const char* what = "ivf_flat16_scan";
   if (int rc = check_batch(what, nq, max_nprobe)) return rc;
   TPQ_REQUIRE(d >= 1, "ivf_flat16_scan: d=%d", d);
@@ -300,11 +265,22 @@ extern "C" int tpq_ivf_flat16_scan_topk(const uint32_t* vectors, const float* qu
   const int R = list_regs(k);
   ScanArgs a = flat16::list_args(query, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr, n_slots, nq,
                                  max_nprobe, k, n_split);
+  a.probe_cap = probe_cap;
   if (int rc = take_list_ws(a, R, workspace, workspace_bytes, what)) return rc;
   const flat16::Flat16Args f{vectors, d};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return metric == TPQ_METRIC_NEG_SQ_L2 ? flat16::dispatch<TPQ_METRIC_NEG_SQ_L2>(a, f, R, st)
                                         : flat16::dispatch<TPQ_METRIC_INNER>(a, f, R, st);
+}
+
+extern "C" int tpq_ivf_flat16_scan_topk(const uint32_t* vectors, const float* query, const uint8_t* is_empty,
+                                        const int64_t* cell_start, const int64_t* cell_size,
+                                        const int64_t* n_probe_list, float* out_vals, int64_t* out_addr,
+                                        int64_t n_slots, int d, int nq, int max_nprobe, int k, int metric, int n_split,
+                                        void* workspace, size_t workspace_bytes, tpq_stream_t stream) {
+  return ivf_flat16_scan_topk_capped(vectors, query, is_empty, cell_start, cell_size, n_probe_list, out_vals, out_addr,
+                                     n_slots, d, nq, max_nprobe, k, metric, n_split, 0, workspace, workspace_bytes,
+                                     stream);
 }
 
 extern "C" int tpq_ivf_flat16_range_count(const uint32_t* vectors, const float* query, const uint8_t* is_empty,

@@ -11,13 +11,16 @@ remove / tombstones / `_address2id` / state_dict and the IdFilter masks work on 
 Values are those of IVFFlatIndex over the rounded vectors, bit for bit: every result equals what an IVFFlatIndex with
 the same coarse codebook returns after add(x.half().float()) (include/torchpq_amd.h).
 
-`use_cell_major` exists, as on IVFFlatIndex, but the route is never taken and `last_route` is always "query_major":
-the cell-major scan's tile loader (sims_rows_mfma) reads fp32 rows; an fp16 tile loader is not part of this index yet.
+`use_cell_major` (off by default) works as on IVFFlatIndex: a batch of at least `cell_major_min_batch` queries with
+k <= 256 and more probes than the route's `first_probe` takes the cell-major scan (tpq_ivf_flat16_cells_topk,
+csrc/scan_flat_f16_cells.hip), which feeds the stored halves to the fp16 matrix cores as they lie and returns the same
+values, ids and addresses bit for bit.  The fp16 tile takes whole groups of 8 dimensions: with a `d_vector` that is not
+a multiple of 8 the switch changes nothing.  `last_route` is "cell_major" or "query_major", the last search's route.
 """
 import torch
 
 from ..container import CellContainer
-from ..kernels import IVFFlat16RangeHip, IVFFlat16TopkHip
+from ..kernels import IVFFlat16CellTopkHip, IVFFlat16RangeHip, IVFFlat16TopkHip
 from .IVFFlatIndex import IVFFlatIndex
 
 
@@ -40,7 +43,7 @@ class IVFFlat16Index(IVFFlatIndex):
         self._init_coarse(n_cells, verbose)
         self._flat_topk = IVFFlat16TopkHip()
         self._flat_range = IVFFlat16RangeHip()
-        self._flat_cells = None            # no cell-major route (the module's docstring)
+        self._flat_cells = IVFFlat16CellTopkHip()   # the cell-major route (the module's docstring); off by default
         self.use_cell_major = False
         self.cell_major_min_batch = 1024
         self.last_route = None
@@ -87,14 +90,7 @@ class IVFFlat16Index(IVFFlatIndex):
         return super().reconstruct(ids=ids, address=address)[:self.d_vector]
 
     # ---- search ----------------------------------------------------------------------------------------
-    def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
-        """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]), as
-        IVFFlatIndex.search_cells.  Always the query-major scan, whatever `use_cell_major` says."""
-        n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
-                                                                                        _extents)
-        self.last_route = "query_major"
-        vals, address = self._flat_topk(
-            self._vectors(), x, cell_start.contiguous(), cell_size.contiguous(), n_probe_list, k,
-            is_empty=is_empty, distance=self.distance, slots_hint=slots_hint)
-        ids = self.get_id_by_address(address)
-        return (vals, ids, address) if return_address else (vals, ids)
+    # (search_cells is IVFFlatIndex's: `_flat_topk`, `_flat_cells` and `_vectors()` are this storage's)
+    def _cell_major_serves_d(self):
+        """the fp16 tile takes whole k-groups of 8 dimensions: any other d_vector keeps the query-major scan"""
+        return self.d_vector % 8 == 0

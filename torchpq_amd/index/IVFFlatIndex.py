@@ -103,6 +103,10 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         return self.codes_to_vectors(self.get_data_by_address(address))
 
     # ---- search ----------------------------------------------------------------------------------------
+    def _cell_major_serves_d(self):
+        """whether the cell-major scan of this storage takes d_vector (fp32 lists: any; IVFFlat16Index: multiples of 8)"""
+        return True
+
     def search_cells(self, x, cells, base_sims=None, n_probe_list=None, k=1, return_address=False, _extents=None):
         """Scan the given cells [n_query, n_probe] for each query; (values, ids[, address]).
         (`base_sims` is accepted for IVFPQIndex's signature and unused; `_extents`: the cells' (start, size) when
@@ -112,7 +116,7 @@ class IVFFlatIndex(CoarseProbeMixin, CellContainer):
         n_probe_list, cell_start, cell_size, slots_hint, is_empty = self._scan_preamble(x, cells, n_probe_list,
                                                                                         _extents)
         cell_major = (self.use_cell_major and k <= 256 and cells.shape[1] > self._flat_cells.first_probe
-                      and x.shape[1] >= self.cell_major_min_batch)
+                      and x.shape[1] >= self.cell_major_min_batch and self._cell_major_serves_d())
         self.last_route = "cell_major" if cell_major else "query_major"
         scan = self._flat_topk
         if cell_major:     # (one host read of the redone queries' count per call: IVFFlatCellTopkHip)

@@ -944,6 +944,14 @@ class IVFFlatCellTopkHip:
              ptr(vectors), ptr(query), ptr(is_empty), ptr(cells), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
              ptr(values), ptr(address), n_slots, int(n_cells), d, n_query, n_probe, k, metric_code(distance),
              first_probe, cand_cap, ptr(ws), ws_bytes)
+        self._redo_flagged(ws, values, address, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty,
+                           distance, slots_hint)
+        return values, address
+
+    def _redo_flagged(self, ws, values, address, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty,
+                      distance, slots_hint):
+        """the host read of the number of flagged queries (workspace word 0), and their rows from `query_major`"""
+        n_query = query.shape[1]
         if self.keep_workspace:
             self.last_workspace = ws
         self.last_redone = int(ws[:4].view(torch.int32).item())      # (the host read)
@@ -953,7 +961,6 @@ class IVFFlatCellTopkHip:
                                     is_empty=is_empty, distance=distance, slots_hint=slots_hint)
             values[redo] = v
             address[redo] = a
-        return values, address
 
 
 class IVFPQ4TopkHip(_IVFPQ4Scan):
@@ -1110,6 +1117,52 @@ class IVFFlat16RangeHip(_ListScan):
                     lambda thr, counts: call("tpq_ivf_flat16_range_count", device, *inputs, thr, counts, *tail),
                     lambda thr, *out: call("tpq_ivf_flat16_range_fill", device, *inputs, thr, *out, *tail))
         return _range_two_pass(n_query, device, threshold, passes)
+
+
+class IVFFlat16CellTopkHip(IVFFlatCellTopkHip):
+    """The cell-major list scan of IVFFlat16Index for large batches (tpq_ivf_flat16_cells_topk,
+    csrc/scan_flat_f16_cells.hip): the results of IVFFlat16TopkHip bit for bit, a probed cell's stored halves fed to the
+    fp16 matrix cores once per block of 128 of its queries, the survivors re-evaluated with the scan's own chain.
+    d must be a multiple of 8 (the library declines any other).  Contract -- first_probe, cand_cap, last_route,
+    last_redone, fill_workspace, keep_workspace, one host read per call -- as IVFFlatCellTopkHip; a flagged query is
+    redone by IVFFlat16TopkHip."""
+
+    def __init__(self, first_probe=None, cand_cap=None):
+        super().__init__(first_probe, cand_cap)
+        self.query_major = IVFFlat16TopkHip()
+
+    def __call__(self, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty=None, distance="euclidean",
+                 cells=None, n_cells=0, first_probe=None, cand_cap=None, slots_hint=None):
+        """
+          vectors, query, cell_start, cell_size, n_probe_list, is_empty, distance: as IVFFlat16TopkHip
+          cells, n_cells, first_probe, cand_cap: as IVFFlatCellTopkHip
+        returns (values [n_query, k] descending, address [n_query, k]); unfilled = (-inf, -1); k <= 256
+        """
+        vectors, query, (n_slots, d, n_query, n_probe) = _flat16_inputs(vectors, query, cell_start, cell_size,
+                                                                         n_probe_list, is_empty, distance)
+        first_probe = self.first_probe if first_probe is None else int(first_probe)
+        cand_cap = self.cand_cap if cand_cap is None else int(cand_cap)
+        assert cells is not None and cells.shape == (n_query, n_probe) and cells.dtype == torch.int64 and n_cells >= 1
+        assert 0 < k <= 256 and first_probe >= 1 and cand_cap >= 64 and cand_cap % 64 == 0
+        cells, cell_start, cell_size = cells.contiguous(), cell_start.contiguous(), cell_size.contiguous()
+        require_gpu(vectors, query, is_empty, cells, cell_start, cell_size, n_probe_list)
+        device = vectors.device
+        values, address = alloc_pair(n_query, k, device)
+        self.last_route, self.last_redone = "cell_major", 0
+        if n_query == 0:
+            return values, address
+        ws_bytes = load().tpq_ivf_flat16_cells_workspace_bytes(n_query, n_probe, int(n_cells), k, cand_cap,
+                                                               first_probe)
+        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8)
+        if self.fill_workspace is not None:
+            ws.fill_(int(self.fill_workspace))
+        call("tpq_ivf_flat16_cells_topk", device,
+             ptr(vectors), ptr(query), ptr(is_empty), ptr(cells), ptr(cell_start), ptr(cell_size), ptr(n_probe_list),
+             ptr(values), ptr(address), n_slots, int(n_cells), d, n_query, n_probe, k, metric_code(distance),
+             first_probe, cand_cap, ptr(ws), ws_bytes)
+        self._redo_flagged(ws, values, address, vectors, query, cell_start, cell_size, n_probe_list, k, is_empty,
+                           distance, slots_hint)
+        return values, address
 
 
 class IVFPQRangeHip(_IVFPQListScan):
